@@ -11,8 +11,16 @@ interleaved 32x32 tiles (the reference's tile schedule, src/GLRenderer.cpp:335-3
 them; the resolved RGBA8 tiles are gathered to rank 0 over RCCL and rank 0 unpacks them into the W x H
 RGB8 image.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...   (one process per GPU)
+
+A plain run does what the headline figure needs: scene setup, W warmup steps (+ the two calls in which a
+launch graph is captured), the K timed steps, and one JSON line with the headline fields.  `--full` adds
+every other measurement and check of the line, each in untimed passes of its own after the timed steps:
+the visit-count pass and the rooflines, the output check, the stage / render / gather timings, the
+one-chain, one-stream and graph-replay passes, the side-stream overlap probe, the interactive 1-spp legs
+and the CPU baseline.  `--dump-outputs DIR` writes what the last timed step handed its caller (the H x W x 3
+RGB8 image rank 0 unpacked) as float32 DIR/image.npy; the inputs are fixed by the arguments.
 
 `--gpus N` without a torch.distributed environment launches the N ranks itself: a child
 `torch.distributed.run` of a fresh interpreter, started before this process touches the GPU (this
@@ -429,6 +437,25 @@ def interactive(steps):
     return out
 
 
+DUMP_BYTES_MAX = 64 << 20  # --dump-outputs: at most this many bytes in all
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array as float32 <path>/<name>.npy.  Arrays that together would pass
+    DUMP_BYTES_MAX are cut to a fixed sample each: the flattened elements at seeded (0) sorted indices,
+    the same in every run."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES_MAX // 4 // max(1, len(arrays))  # elements per array
+    whole = sum(a.size for a in arrays.values()) * 4 <= DUMP_BYTES_MAX
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if not whole and a.size > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def _free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -490,8 +517,16 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="c2", choices=sorted(workloads.WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-interactive", action="store_true", help="skip the 1-spp progressive-frame leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other measurement and check of the line (rooflines, "
+                         "output check, stage timings, one-chain / one-stream / graph-replay passes, interactive "
+                         "legs, CPU baseline); a plain run times the steps and prints the headline fields only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output (the RGB8 image rank 0 unpacked) as float32 "
+                         "DIR/image.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-interactive", action="store_true",
+                    help="with --full: skip the 1-spp progressive-frame leg")
     ap.add_argument("--dry-run", action="store_true", help="CPU/gloo check of the rank launch + tile gather")
     ap.add_argument("--wave-paths", type=int, default=0)
     ap.add_argument("--leaf-size", type=int, default=0)
@@ -523,6 +558,8 @@ def main():
 
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -570,7 +607,7 @@ def main():
         r.set_pixel_lanes(args.pixel_lanes)
     # does the library's side stream run beside the render stream on this device (its own hardware
     # queue)?  Two 200-us one-wave spins, serial vs forked (sptr_overlap_probe)
-    probe = r.overlap_probe()
+    probe = r.overlap_probe() if args.full else None
     flat = workloads.setup(r, wl)
     layout, info = r.scene_layout(), r.scene_info()
     env_bytes = 6 * 512 * 512 * 16 if wl.hdr_env else 0  # workloads.hdr_env_faces(): 512^2 faces, float4 on the device
@@ -619,6 +656,194 @@ def main():
             ev[2].record()
         return src
 
+    def full_passes(timed, last_tiles):
+        """--full: every measurement and check beside the headline, each an untimed pass of its own after
+        the timed steps (last_tiles: the last timed step's tiles).  Returns the figures the line reports."""
+        # The last timed step's output against an untimed render of the same frame (default flags, the
+        # library's own stream, synchronous: the call shape tests/test_gpu_golden.py checks against the oracle):
+        # this rank's resolved tiles, and on one GPU the unpacked RGB8 image, byte for byte.
+        tiles_timed = last_tiles.clone()
+        image_timed = image.clone() if rank == 0 else None
+        torch.cuda.synchronize()
+        r.render(cam, W, H, spp=frames, max_depth=wl.max_depth, shard_rank=shard, shard_count=shards,
+                 integrator=integ, samples_per_frame=4)
+        ref_ptr, ref_bytes = r.tiles_device()
+        ref_tiles = torch.as_tensor(_DevArray(ref_ptr, ref_bytes), device=dev)
+        n_cmp = min(ref_tiles.numel(), tiles_timed.numel())
+        tile_words_differing = int((ref_tiles[:n_cmp] != tiles_timed[:n_cmp]).sum().item()) + \
+            abs(ref_tiles.numel() - tiles_timed.numel())
+        image_bytes_differing = None
+        if rank == 0 and shards == 1:
+            ref_rgb = torch.from_numpy(r.read_rgb8().reshape(-1)).to(dev)
+            image_bytes_differing = int((ref_rgb != image_timed).sum().item())
+        if distributed:  # every rank's differing tile words
+            diff = torch.tensor([tile_words_differing], dtype=torch.int64, device=dev)
+            dist.all_reduce(diff)
+            tile_words_differing = int(diff.item())
+        output_check = {"reference": "untimed render of the same frame, default flags, synchronous",
+                        "identical": tile_words_differing == 0 and not image_bytes_differing,
+                        "tile_words_differing": tile_words_differing, "image_bytes_differing": image_bytes_differing}
+
+        # Launch durations for the roofline: an untimed pass of the same K steps in which the trace, fused-bounce
+        # and shadow launches time themselves (SPTR_FRAME_TIMING_TRACE; such calls always run as direct launches).
+        # Counts (rays, visits) are the same as the timed steps'; the durations are these launches' own.
+        timing = (sptr.SPTR_FRAME_TIMING if args.stage_timing else sptr.SPTR_FRAME_TIMING_TRACE) | sptr.SPTR_FRAME_RECULL
+        for _ in range(2):
+            step(timing)
+        r.collect_stats()
+        torch.cuda.synchronize()
+        tr0 = time.perf_counter()
+        for i in range(args.steps):
+            step(timing)
+        torch.cuda.synchronize()
+        rf_elapsed = time.perf_counter() - tr0
+        stats_rf = [r.collect_stats()]
+
+        # render / gather split of a step: an untimed pass of the same K steps with three torch events per step.
+        # (The timed steps carry none: each event record between two launches idles the GPU for several
+        # microseconds, r06: the 8-way C2 shard 0.478 ms/step with them, 0.458 without.)
+        evs = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(args.steps)]
+        for i in range(args.steps):
+            step(timed, evs[i])
+        torch.cuda.synchronize()
+        r.collect_stats()
+        render_ms = sum(e[0].elapsed_time(e[1]) for e in evs) / args.steps
+        gather_ms = sum(e[1].elapsed_time(e[2]) for e in evs) / args.steps
+
+        # one untimed step with events around every stage (the timed steps record them around the trace and
+        # shadow launches only: each record between two launches idles the GPU for several microseconds)
+        step(sptr.SPTR_FRAME_TIMING | sptr.SPTR_FRAME_RECULL)
+        st_full = r.collect_stats()
+        stage_full = {k: round(getattr(st_full, "ms_" + k), 3)
+                      for k in ("total", "cull", "trace0", "trace", "shade0", "shade", "shadow", "tail", "accum")}
+
+        # pixel lanes (sptr_set_pixel_lanes): the timed calls' two launch chains share the GPU, so their launch
+        # durations include each other's time; an untimed pass of the same steps as one chain gives the
+        # launches' own durations (roofline_one_chain)
+        lanes_info = r.pixel_lanes_info()
+        stats_one, one_elapsed = None, 0.0
+        one_chain_pass = lanes_info["active"] and not args.no_serial_pass and args.integrator == "wavefront"
+        if distributed:  # (its steps gather: every rank runs it or none)
+            flag = torch.tensor([1 if one_chain_pass else 0], dtype=torch.int32, device=dev)
+            dist.all_reduce(flag, op=dist.ReduceOp.MIN)
+            one_chain_pass = bool(flag.item())
+        if one_chain_pass:
+            r.set_pixel_lanes(1)
+            step(timing)
+            r.collect_stats()
+            torch.cuda.synchronize()
+            to0 = time.perf_counter()
+            for i in range(args.steps):
+                step(timing)
+            torch.cuda.synchronize()
+            one_elapsed = time.perf_counter() - to0
+            stats_one = [r.collect_stats()]
+            r.set_pixel_lanes(args.pixel_lanes)
+
+        # untimed one-stream pass (launch mode 2) for scenes whose launches overlap on the side streams: the
+        # trace and shadow launches' own durations, with nothing beside them (roofline_serial)
+        stats_serial, serial_elapsed = None, 0.0
+        residency = _residency(layout)[0]
+        if world == 1 and residency != "lds" and not args.no_serial_pass and args.launch_mode == 0 and \
+                args.integrator == "wavefront":
+            r.set_launch_mode(2)
+            step(timing)
+            r.collect_stats()
+            torch.cuda.synchronize()
+            ts0 = time.perf_counter()
+            for i in range(args.steps):
+                step(timing)
+            torch.cuda.synchronize()
+            serial_elapsed = time.perf_counter() - ts0
+            stats_serial = [r.collect_stats()]
+            r.set_launch_mode(0)
+
+        # untimed pass of the same steps without stage events, launch mode 3: the call shape is captured
+        # into a launch graph on its second call and replayed from then on (stage spans inside a graph would need
+        # external event-record nodes, which torch's HIP 7.0 runtime refuses inside a capture: calls with
+        # stage timing, like the timed steps above, run as direct launches)
+        graph_replay = None
+        if world == 1 and args.launch_mode == 0 and args.integrator == "wavefront" and not args.no_serial_pass:
+            r.set_launch_mode(3)  # (mode 0 launches a large call with side-stream launches directly)
+            for _ in range(2):
+                step(sptr.SPTR_FRAME_RECULL)
+            r.collect_stats()
+            torch.cuda.synchronize()
+            tg0 = time.perf_counter()
+            for i in range(args.steps):
+                step(sptr.SPTR_FRAME_RECULL)
+            torch.cuda.synchronize()
+            graph_elapsed = time.perf_counter() - tg0
+            gst = r.collect_stats()
+            g = r.graph_info()
+            r.set_launch_mode(0)
+            graph_replay = {"ms_per_step": round(graph_elapsed / args.steps * 1e3, 3),
+                            "mrays_per_s": round((gst.rays_closest + gst.rays_shadow) / graph_elapsed / 1e6, 2),
+                            "graph": {k: g[k] for k in ("valid", "nodes", "edges", "depth", "captures")},
+                            "capture_error": g["capture_error"] or None}
+        return {"output_check": output_check, "stats_rf": stats_rf, "rf_elapsed": rf_elapsed, "render_ms": render_ms,
+                "gather_ms": gather_ms, "stage_full": stage_full, "lanes_info": lanes_info, "stats_one": stats_one,
+                "one_elapsed": one_elapsed, "stats_serial": stats_serial, "serial_elapsed": serial_elapsed,
+                "graph_replay": graph_replay}
+
+    def full_fields(line, x, stats, per_rank_render, render_ms, gather_ms, elapsed, samples):
+        """--full: what full_passes (x) measured, added to rank 0's line."""
+        # the committed counter summaries (profiles/r*_pmc_<wl>_*.json) describe the workload's default line; an
+        # emulated shard or a one-chain pass runs other launches, so they take no counter fractions
+        prof = wl.name if not args.emulate_shards else f"{wl.name}_shard{args.emulate_shards}"
+        stats_rf, stage_full, lanes_info = x["stats_rf"], x["stage_full"], x["lanes_info"]
+        stage_ms = {k: round(sum(getattr(s, "ms_" + k) for s in stats_rf) / args.steps, 3)
+                    for k in (("trace0", "trace", "shade0", "shade", "shadow", "tail", "accum", "cull")
+                              if args.stage_timing else ("trace0", "trace", "shadow"))}
+        line.update({
+            "roofline": roofline(cnt, stats_rf, layout, prof, args.steps, env_bytes=env_bytes),
+            "shadow_roofline": shadow_roofline(cnt, stats_rf, layout, prof, args.steps),
+            # the launch durations above come from this untimed pass of the same steps
+            "roofline_pass": {"flags": "SPTR_FRAME_TIMING_TRACE | SPTR_FRAME_RECULL (direct launches)",
+                              "ms_per_step": round(x["rf_elapsed"] / args.steps * 1e3, 3)},
+            "output_check": x["output_check"],
+            "overlap_probe": probe,
+            "stage_ms_per_step": stage_ms,  # (the roofline pass's)
+            # all stages of one untimed step, events around each (stage spans overlap on L2/HBM scenes)
+            "stage_ms_untimed_step": stage_full,
+            "cull_ms": stage_full["cull"],
+            # per step: max over ranks of render (+ tile copy) and of gather (+ rank-0 unpack), HIP events
+            # (an untimed pass of the same steps)
+            "render_ms": round(render_ms, 4),
+            "gather_ms": round(gather_ms, 4),
+            "render_ms_per_rank": [round(v, 4) for v in per_rank_render],
+            "cpu_baseline": None,
+        })
+        if args.integrator == "wavefront":
+            line["step_roofline"] = step_roofline(cnt, stats, args.steps, elapsed / args.steps * 1e3, line["roofline"],
+                                                  line["shadow_roofline"], samples / max(1, args.steps) / wl.spp / world,
+                                                  wl.spp, env_bytes=env_bytes)
+        if x["stats_serial"]:
+            rs = roofline(cnt, x["stats_serial"], layout, wl.name, args.steps, env_bytes=env_bytes)
+            ss = shadow_roofline(cnt, x["stats_serial"], layout, wl.name, args.steps)
+            line["roofline_serial"] = {
+                "note": "untimed pass with every launch on one stream (launch mode 2): launch durations with nothing "
+                        "beside them; the headline value is the overlapped run's",
+                "ms_per_step": round(x["serial_elapsed"] / args.steps * 1e3, 3),
+                "trace": {k: rs[k] for k in ("achieved", "frac", "avg_launch_us", "launches_per_step", "bytes_per_launch")},
+                "shadow": {k: ss[k] for k in ("achieved", "frac", "avg_launch_us", "launches_per_step", "bytes_per_launch")}
+                if ss else None}
+        line["pixel_lanes"] = {"requested": lanes_info["requested"], "active": lanes_info["active"],
+                               "note": "two lanes: the shard's even and odd tiles as two concurrent launch chains; "
+                                       "each launch's duration (avg_launch_us) includes the other chain's time, so "
+                                       "roofline.achieved divides the trace bytes by the trace launches' busy time "
+                                       "(the union of their intervals over both lanes, busy_us_per_launch)"
+                               if lanes_info["active"] else "one launch chain"}
+        if x["stats_one"]:
+            ro = roofline(cnt, x["stats_one"], layout, wl.name + "_one_chain", args.steps, env_bytes=env_bytes)
+            line["roofline_one_chain"] = {
+                "note": "untimed pass of the same steps as one launch chain (sptr_set_pixel_lanes 1): the trace "
+                        "launches' own durations; the headline value is the two-lane run's",
+                "ms_per_step": round(x["one_elapsed"] / args.steps * 1e3, 3),
+                "trace": {k: ro[k] for k in ("achieved", "frac", "avg_launch_us", "launches_per_step", "bytes_per_launch")}}
+        if x["graph_replay"]:
+            line["graph_replay"] = x["graph_replay"]
+
     # The timed steps are the calls a default caller makes: no stage-timing flag, so the library launches
     # them as it launches any render (launch mode 0: a captured graph where one replays faster, DESIGN.md
     # §6).  Every timed step recomputes the bounce-0 cull mask (SPTR_FRAME_RECULL): it is a per-camera
@@ -628,9 +853,11 @@ def main():
     for _ in range(args.warmup):
         step(timed)
     r.collect_stats()
-    # untimed instrumented pass: BVH node / primitive fetch counts for the algorithmic-bytes model
-    step(sptr.SPTR_FRAME_COUNT_VISITS)
-    cnt = r.collect_stats()
+    cnt = None
+    if args.full:
+        # untimed instrumented pass: BVH node / primitive fetch counts for the algorithmic-bytes model
+        step(sptr.SPTR_FRAME_COUNT_VISITS)
+        cnt = r.collect_stats()
     # the timed call shape seen twice right before timing (a graph, where mode 0 captures one, is captured
     # on the second call)
     for _ in range(2):
@@ -649,135 +876,17 @@ def main():
     elapsed = time.perf_counter() - t0
     stats = [r.collect_stats()]  # the K timed steps' counters, summed
 
-    # The last timed step's output against an untimed render of the same frame (default flags, the
-    # library's own stream, synchronous: the call shape tests/test_gpu_golden.py checks against the oracle):
-    # this rank's resolved tiles, and on one GPU the unpacked RGB8 image, byte for byte.
-    tiles_timed = last_tiles.clone()
-    image_timed = image.clone() if rank == 0 else None
-    torch.cuda.synchronize()
-    r.render(cam, W, H, spp=frames, max_depth=wl.max_depth, shard_rank=shard, shard_count=shards,
-             integrator=integ, samples_per_frame=4)
-    ref_ptr, ref_bytes = r.tiles_device()
-    ref_tiles = torch.as_tensor(_DevArray(ref_ptr, ref_bytes), device=dev)
-    n_cmp = min(ref_tiles.numel(), tiles_timed.numel())
-    tile_words_differing = int((ref_tiles[:n_cmp] != tiles_timed[:n_cmp]).sum().item()) + \
-        abs(ref_tiles.numel() - tiles_timed.numel())
-    image_bytes_differing = None
-    if rank == 0 and shards == 1:
-        ref_rgb = torch.from_numpy(r.read_rgb8().reshape(-1)).to(dev)
-        image_bytes_differing = int((ref_rgb != image_timed).sum().item())
-    if distributed:  # every rank's differing tile words
-        diff = torch.tensor([tile_words_differing], dtype=torch.int64, device=dev)
-        dist.all_reduce(diff)
-        tile_words_differing = int(diff.item())
-    output_check = {"reference": "untimed render of the same frame, default flags, synchronous",
-                    "identical": tile_words_differing == 0 and not image_bytes_differing,
-                    "tile_words_differing": tile_words_differing, "image_bytes_differing": image_bytes_differing}
+    if args.dump_outputs and rank == 0:  # (before any later pass renders into the same buffers)
+        dump_outputs(args.dump_outputs, {"image": image.reshape(H, W, 3).cpu().numpy()})
 
-    # Launch durations for the roofline: an untimed pass of the same K steps in which the trace, fused-bounce
-    # and shadow launches time themselves (SPTR_FRAME_TIMING_TRACE; such calls always run as direct launches).
-    # Counts (rays, visits) are the same as the timed steps'; the durations are these launches' own.
-    timing = (sptr.SPTR_FRAME_TIMING if args.stage_timing else sptr.SPTR_FRAME_TIMING_TRACE) | sptr.SPTR_FRAME_RECULL
-    for _ in range(2):
-        step(timing)
-    r.collect_stats()
-    torch.cuda.synchronize()
-    tr0 = time.perf_counter()
-    for i in range(args.steps):
-        step(timing)
-    torch.cuda.synchronize()
-    rf_elapsed = time.perf_counter() - tr0
-    stats_rf = [r.collect_stats()]
-
-    # render / gather split of a step: an untimed pass of the same K steps with three torch events per step.
-    # (The timed steps carry none: each event record between two launches idles the GPU for several
-    # microseconds, r06: the 8-way C2 shard 0.478 ms/step with them, 0.458 without.)
-    evs = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(args.steps)]
-    for i in range(args.steps):
-        step(timed, evs[i])
-    torch.cuda.synchronize()
-    r.collect_stats()
-    render_ms = sum(e[0].elapsed_time(e[1]) for e in evs) / args.steps
-    gather_ms = sum(e[1].elapsed_time(e[2]) for e in evs) / args.steps
-
-    # one untimed step with events around every stage (the timed steps record them around the trace and
-    # shadow launches only: each record between two launches idles the GPU for several microseconds)
-    step(sptr.SPTR_FRAME_TIMING | sptr.SPTR_FRAME_RECULL)
-    st_full = r.collect_stats()
-    stage_full = {k: round(getattr(st_full, "ms_" + k), 3)
-                  for k in ("total", "cull", "trace0", "trace", "shade0", "shade", "shadow", "tail", "accum")}
-
-    # pixel lanes (sptr_set_pixel_lanes): the timed calls' two launch chains share the GPU, so their launch
-    # durations include each other's time; an untimed pass of the same steps as one chain gives the
-    # launches' own durations (roofline_one_chain)
-    lanes_info = r.pixel_lanes_info()
-    stats_one = None
-    one_chain_pass = lanes_info["active"] and not args.no_serial_pass and args.integrator == "wavefront"
-    if distributed:  # (its steps gather: every rank runs it or none)
-        flag = torch.tensor([1 if one_chain_pass else 0], dtype=torch.int32, device=dev)
-        dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-        one_chain_pass = bool(flag.item())
-    if one_chain_pass:
-        r.set_pixel_lanes(1)
-        step(timing)
-        r.collect_stats()
-        torch.cuda.synchronize()
-        to0 = time.perf_counter()
-        for i in range(args.steps):
-            step(timing)
-        torch.cuda.synchronize()
-        one_elapsed = time.perf_counter() - to0
-        stats_one = [r.collect_stats()]
-        r.set_pixel_lanes(args.pixel_lanes)
-
-    # untimed one-stream pass (launch mode 2) for scenes whose launches overlap on the side streams: the
-    # trace and shadow launches' own durations, with nothing beside them (roofline_serial)
-    stats_serial = None
-    residency = _residency(layout)[0]
-    # the committed counter summaries (profiles/r*_pmc_<wl>_*.json) describe the workload's default line; an
-    # emulated shard or a one-chain pass runs other launches, so they take no counter fractions
-    prof = wl.name if not args.emulate_shards else f"{wl.name}_shard{args.emulate_shards}"
-    if world == 1 and residency != "lds" and not args.no_serial_pass and args.launch_mode == 0 and \
-            args.integrator == "wavefront":
-        r.set_launch_mode(2)
-        step(timing)
-        r.collect_stats()
-        torch.cuda.synchronize()
-        ts0 = time.perf_counter()
-        for i in range(args.steps):
-            step(timing)
-        torch.cuda.synchronize()
-        serial_elapsed = time.perf_counter() - ts0
-        stats_serial = [r.collect_stats()]
-        r.set_launch_mode(0)
-
-    # untimed pass of the same steps without stage events, launch mode 3: the call shape is captured
-    # into a launch graph on its second call and replayed from then on (stage spans inside a graph would need
-    # external event-record nodes, which torch's HIP 7.0 runtime refuses inside a capture: calls with
-    # stage timing, like the timed steps above, run as direct launches)
-    graph_replay = None
-    if world == 1 and args.launch_mode == 0 and args.integrator == "wavefront" and not args.no_serial_pass:
-        r.set_launch_mode(3)  # (mode 0 launches a large call with side-stream launches directly)
-        for _ in range(2):
-            step(sptr.SPTR_FRAME_RECULL)
-        r.collect_stats()
-        torch.cuda.synchronize()
-        tg0 = time.perf_counter()
-        for i in range(args.steps):
-            step(sptr.SPTR_FRAME_RECULL)
-        torch.cuda.synchronize()
-        graph_elapsed = time.perf_counter() - tg0
-        gst = r.collect_stats()
-        g = r.graph_info()
-        r.set_launch_mode(0)
-        graph_replay = {"ms_per_step": round(graph_elapsed / args.steps * 1e3, 3),
-                        "mrays_per_s": round((gst.rays_closest + gst.rays_shadow) / graph_elapsed / 1e6, 2),
-                        "graph": {k: g[k] for k in ("valid", "nodes", "edges", "depth", "captures")},
-                        "capture_error": g["capture_error"] or None}
+    extra = full_passes(timed, last_tiles) if args.full else None
 
     rays = sum(s.rays_closest + s.rays_shadow for s in stats)
     samples = sum(s.samples for s in stats)
     traced_p = sum(s.traced_primary for s in stats)
+    # render_ms / gather_ms (and the per-rank list) exist only under --full: a plain run carries zeros
+    # through the same reductions and reports none of them
+    render_ms, gather_ms = (extra["render_ms"], extra["gather_ms"]) if extra else (0.0, 0.0)
     t = torch.tensor([elapsed, float(rays), float(samples), float(traced_p), render_ms, gather_ms],
                      dtype=torch.float64, device=dev)
     per_rank_render = [render_ms]
@@ -796,9 +905,6 @@ def main():
         assert int(tsum[2]) == want, (int(tsum[2]), want)
 
     if rank == 0:
-        stage_ms = {k: round(sum(getattr(s, "ms_" + k) for s in stats_rf) / args.steps, 3)
-                    for k in (("trace0", "trace", "shade0", "shade", "shadow", "tail", "accum", "cull")
-                              if args.stage_timing else ("trace0", "trace", "shadow"))}
         knobs = {k: os.environ[k] for k in KNOB_VARS if os.environ.get(k)}
         if args.launch_mode:
             knobs["launch_mode"] = args.launch_mode
@@ -829,17 +935,6 @@ def main():
             "world_size": world,
             "collective": ("RCCL gather of the RGBA8 tiles to rank 0 (point-to-point over xGMI), once per step" if distributed
                            else "none (1 rank)"),
-            "roofline": roofline(cnt, stats_rf, layout, prof, args.steps, env_bytes=env_bytes),
-            "shadow_roofline": shadow_roofline(cnt, stats_rf, layout, prof, args.steps),
-            # the launch durations above come from this untimed pass of the same steps
-            "roofline_pass": {"flags": "SPTR_FRAME_TIMING_TRACE | SPTR_FRAME_RECULL (direct launches)",
-                              "ms_per_step": round(rf_elapsed / args.steps * 1e3, 3)},
-            "output_check": output_check,
-            "overlap_probe": probe,
-            "stage_ms_per_step": stage_ms,  # (the roofline pass's)
-            # all stages of one untimed step, events around each (stage spans overlap on L2/HBM scenes)
-            "stage_ms_untimed_step": stage_full,
-            "cull_ms": stage_full["cull"],
             "cull_launches_per_step": sum(s.cull_launches for s in stats) / args.steps,
             "tail_rays_per_step": int(sum(s.rays_tail for s in stats) / args.steps),
             # paths the bounce traces handed to the straggler kernel (sptr_set_stragglers)
@@ -848,47 +943,15 @@ def main():
             # queries answered without a traversal: the camera rays of frustum-culled pixels (all ranks)
             "culled_primary_per_step": int((samples - traced_p) / args.steps) if args.integrator == "wavefront" else 0,
             "traversed_rays_per_step": int((rays - (samples - traced_p if args.integrator == "wavefront" else 0)) / args.steps),
-            # per step: max over ranks of render (+ tile copy) and of gather (+ rank-0 unpack), HIP events
-            # (an untimed pass of the same steps)
-            "render_ms": round(render_ms, 4),
-            "gather_ms": round(gather_ms, 4),
             "gather_bytes": int(shards * tiles_per_rank * 4096) if distributed else 0,
-            "render_ms_per_rank": [round(x, 4) for x in per_rank_render],
             "scene": {"prims": info["prims"], "lbvh_nodes": info["nodes"], "bvh_depth": info["depth"],
                       "lbvh_build_ms": round(info["build_ms"], 3), "leaf_size": layout["leaf_size"],
                       "bvh_width": layout["bvh_width"], "traversed_nodes": layout["num_nodes"],
                       "prim_refs": layout["num_prim_refs"]},
-            "cpu_baseline": None,
+            "full": bool(args.full),
         }
-        if args.integrator == "wavefront":
-            line["step_roofline"] = step_roofline(cnt, stats, args.steps, elapsed / args.steps * 1e3, line["roofline"],
-                                                  line["shadow_roofline"], samples / max(1, args.steps) / wl.spp / world,
-                                                  wl.spp, env_bytes=env_bytes)
-        if stats_serial:
-            rs = roofline(cnt, stats_serial, layout, wl.name, args.steps, env_bytes=env_bytes)
-            ss = shadow_roofline(cnt, stats_serial, layout, wl.name, args.steps)
-            line["roofline_serial"] = {
-                "note": "untimed pass with every launch on one stream (launch mode 2): launch durations with nothing "
-                        "beside them; the headline value is the overlapped run's",
-                "ms_per_step": round(serial_elapsed / args.steps * 1e3, 3),
-                "trace": {k: rs[k] for k in ("achieved", "frac", "avg_launch_us", "launches_per_step", "bytes_per_launch")},
-                "shadow": {k: ss[k] for k in ("achieved", "frac", "avg_launch_us", "launches_per_step", "bytes_per_launch")}
-                if ss else None}
-        line["pixel_lanes"] = {"requested": lanes_info["requested"], "active": lanes_info["active"],
-                               "note": "two lanes: the shard's even and odd tiles as two concurrent launch chains; "
-                                       "each launch's duration (avg_launch_us) includes the other chain's time, so "
-                                       "roofline.achieved divides the trace bytes by the trace launches' busy time "
-                                       "(the union of their intervals over both lanes, busy_us_per_launch)"
-                               if lanes_info["active"] else "one launch chain"}
-        if stats_one:
-            ro = roofline(cnt, stats_one, layout, wl.name + "_one_chain", args.steps, env_bytes=env_bytes)
-            line["roofline_one_chain"] = {
-                "note": "untimed pass of the same steps as one launch chain (sptr_set_pixel_lanes 1): the trace "
-                        "launches' own durations; the headline value is the two-lane run's",
-                "ms_per_step": round(one_elapsed / args.steps * 1e3, 3),
-                "trace": {k: ro[k] for k in ("achieved", "frac", "avg_launch_us", "launches_per_step", "bytes_per_launch")}}
-        if graph_replay:
-            line["graph_replay"] = graph_replay
+        if extra:
+            full_fields(line, extra, stats, per_rank_render, render_ms, gather_ms, elapsed, samples)
         if knobs:
             line["experiment_knobs"] = knobs
         if args.emulate_shards:
@@ -896,9 +959,10 @@ def main():
         if args.integrator == "pathtracer":
             line["note"] = ("PathTracer-mode throughput (the reference's default CPU integrator semantics, path per "
                             "thread); not the headline wavefront metric; roofline fields describe no k_trace launch")
-        if world == 1 and not args.no_interactive and not args.emulate_shards and args.integrator == "wavefront":
+        if args.full and world == 1 and not args.no_interactive and not args.emulate_shards and \
+                args.integrator == "wavefront":
             line["interactive"] = interactive(200)
-        if world == 1 and not args.no_cpu_baseline and args.integrator == "wavefront":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.integrator == "wavefront":
             line["cpu_baseline"] = cpu_baseline(wl, flat, cam)
         print(json.dumps(line), flush=True)
     r.close()

@@ -8,7 +8,7 @@ for i in $(seq 1 $reps); do for spec in tree "$@"; do
   lib=${spec%%:*}; extra=""; [[ "$spec" == *:* ]] && extra=$(echo "${spec#*:}" | tr '=' ' ')
   L=$GRAFT_REPO_ROOT/simple-path-tracer_amd/libsptr_hip.so; [ "$lib" = tree ] || L=$GRAFT_REPO_ROOT/$lib
   n=full_${wl}_${i}_$(echo "$spec" | tr '/: =' '____')
-  SPTR_LIB=$L timeout -k 10 240 python3 bench.py --workload $wl --steps 10 --warmup 2 --no-cpu-baseline --no-interactive $extra > $out/$n.json 2>$out/$n.err
+  SPTR_LIB=$L timeout -k 10 240 python3 bench.py --full --workload $wl --steps 10 --warmup 2 --no-cpu-baseline --no-interactive $extra > $out/$n.json 2>$out/$n.err
   python3 - "$out/$n.json" "$wl $spec" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().splitlines()[-1]); r = d["roofline"]; s = d.get("shadow_roofline") or {}

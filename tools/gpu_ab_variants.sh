@@ -13,7 +13,7 @@ for i in $(seq 1 "$reps"); do
     for spec in "$@"; do
       wl=${spec%%:*}; extra=""; [ "$spec" != "$wl" ] && extra=$(echo "${spec#*:}" | tr ':' ' ')
       f=$out/${wl}$(echo "$extra" | tr -d ' -')_${v}_$i.json
-      SPTR_LIB=$L timeout -k 10 200 python3 bench.py --workload "$wl" $extra --steps 20 --warmup 3 --no-cpu-baseline \
+      SPTR_LIB=$L timeout -k 10 200 python3 bench.py --full --workload "$wl" $extra --steps 20 --warmup 3 --no-cpu-baseline \
         --no-interactive --no-serial-pass > "$f" 2> "$f.err"
       python3 -c "import json,sys;d=json.loads(open('$f').read().splitlines()[-1]);s=d['stage_ms_untimed_step'];print('$spec', '$v', d['ms_per_step'], 'rf', d['roofline_pass']['ms_per_step'], 'trace0', s['trace0'], 'shade0', s['shade0'], 'trace', s['trace'], 'ok', d['output_check']['identical'])"
     done

@@ -6,13 +6,13 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 o=gpurun_out/$1; wl=$2; shift 2; mkdir -p $o
 extra=("$@")
 timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $o/stats_$wl -o run -- \
-  python3 bench.py --workload $wl --steps 3 --warmup 1 --no-cpu-baseline --no-interactive --no-serial-pass "${extra[@]}" > $o/stats_$wl.log 2>&1 || exit 1
+  python3 bench.py --full --workload $wl --steps 3 --warmup 1 --no-cpu-baseline --no-interactive --no-serial-pass "${extra[@]}" > $o/stats_$wl.log 2>&1 || exit 1
 python3 tools/prof_summary.py $o/stats_$wl > $o/summary_$wl.txt; head -14 $o/summary_$wl.txt
 run() {  # name, counters...
   local n=$1; shift
   local cs=("$@")
   timeout -s KILL 120 rocprofv3 --pmc "${cs[@]}" --output-format csv -d $o/cnt_${wl}_$n -o run -- \
-    python3 bench.py --workload $wl --steps 1 --warmup 0 --no-cpu-baseline --no-interactive --no-serial-pass "${extra[@]}" > $o/cnt_${wl}_$n.log 2>&1 || return 1
+    python3 bench.py --full --workload $wl --steps 1 --warmup 0 --no-cpu-baseline --no-interactive --no-serial-pass "${extra[@]}" > $o/cnt_${wl}_$n.log 2>&1 || return 1
   python3 tools/prof_summary.py $o/cnt_${wl}_$n > $o/cnt_${wl}_$n.txt || true
   echo "== $n"; grep -E "k_trace|k_shade|k_bounce|k_shadow|k_sky|k_tail" $o/cnt_${wl}_$n.txt | grep -v '<true' | head -12
 }

@@ -9,7 +9,7 @@ timeout -k 10 600 python3 -u -m pytest tests -m gpu -x -q --timeout 240 --timeou
 tail -2 $o/pytest_gpu.log
 run() {  # workload variant rep
   lib=$GRAFT_REPO_ROOT/variants/$2/libsptr_hip.so; [ "$2" = tree ] && lib=$GRAFT_REPO_ROOT/simple-path-tracer_amd/libsptr_hip.so
-  SPTR_LIB=$lib timeout -k 10 300 python3 bench.py --workload $1 --steps 20 --warmup 3 --no-cpu-baseline --no-interactive \
+  SPTR_LIB=$lib timeout -k 10 300 python3 bench.py --full --workload $1 --steps 20 --warmup 3 --no-cpu-baseline --no-interactive \
     > $o/$1_$2_$3.json 2> $o/$1_$2_$3.err
   python3 -c "import json;d=json.loads(open('$o/$1_$2_$3.json').read().splitlines()[-1]);print('$1 $2 $3',d['ms_per_step'],d.get('stage_ms_untimed_step'))"
 }

@@ -12,7 +12,7 @@ for rep in 1 2; do
   for v in tree nohead; do
     for g in 8 1; do
       ex=""; [ $g = 8 ] && ex="--emulate-shards 8"
-      SPTR_LIB=$(lib $v) timeout -k 10 300 python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-interactive $ex \
+      SPTR_LIB=$(lib $v) timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-interactive $ex \
         > $o/c2_g${g}_${v}_$rep.json 2> $o/c2_g${g}_${v}_$rep.err
       python3 -c "import json;d=json.loads(open('$o/c2_g${g}_${v}_$rep.json').read().splitlines()[-1]);print('g$g $v $rep',d['ms_per_step'],d['output_check']['identical'] if 'output_check' in d else '')"
     done

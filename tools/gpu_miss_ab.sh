@@ -10,7 +10,7 @@ lib() { [ "$1" = tree ] && echo $GRAFT_REPO_ROOT/simple-path-tracer_amd/libsptr_
 for rep in 1 2; do
   for wl in c5 c3; do
     for v in tree nomiss; do
-      SPTR_LIB=$(lib $v) timeout -k 10 300 python3 bench.py --workload $wl --steps 20 --warmup 3 --no-cpu-baseline --no-interactive \
+      SPTR_LIB=$(lib $v) timeout -k 10 300 python3 bench.py --full --workload $wl --steps 20 --warmup 3 --no-cpu-baseline --no-interactive \
         > $o/${wl}_${v}_$rep.json 2> $o/${wl}_${v}_$rep.err
       python3 -c "import json;d=json.loads(open('$o/${wl}_${v}_$rep.json').read().splitlines()[-1]);print('$wl $v $rep',d['ms_per_step'],d['output_check']['identical'],d.get('stage_ms_untimed_step'))"
     done

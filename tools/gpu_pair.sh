@@ -13,7 +13,7 @@ for rep in 1 2; do
 for v in base "$@"; do
   lib=$GRAFT_REPO_ROOT/variants/$v/libsptr_hip.so; [ -f $lib ] || lib=$GRAFT_REPO_ROOT/simple-path-tracer_amd/libsptr_hip.so
   for wl in c5 c3; do
-    SPTR_LIB=$lib timeout -k 10 300 python3 bench.py --workload $wl --steps 10 --warmup 2 --no-cpu-baseline --no-interactive --no-serial-pass \
+    SPTR_LIB=$lib timeout -k 10 300 python3 bench.py --full --workload $wl --steps 10 --warmup 2 --no-cpu-baseline --no-interactive --no-serial-pass \
       > $o/${wl}_$v.json 2> $o/${wl}_$v.err || { tail -5 $o/${wl}_$v.err; exit 4; }
     python3 -c "import json;d=json.loads(open('$o/${wl}_$v.json').read().splitlines()[-1]);print('$wl $v rep$rep',d['ms_per_step'],d['stage_ms_per_step'],'handed',d.get('paths_handed_off_per_step'))"
   done

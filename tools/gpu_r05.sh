@@ -21,7 +21,7 @@ if [ "${1:-}" = "--tests" ]; then
 fi
 for wl in "$@"; do
   echo "[$(date +%T)] bench $wl"
-  timeout -k 10 300 python3 bench.py --workload "$wl" --steps 10 --warmup 2 --no-cpu-baseline --no-interactive \
+  timeout -k 10 300 python3 bench.py --full --workload "$wl" --steps 10 --warmup 2 --no-cpu-baseline --no-interactive \
     > "$out/bench_$wl.json" 2> "$out/bench_$wl.err"
   python3 - "$out/bench_$wl.json" <<'PY'
 import json, sys

@@ -13,7 +13,7 @@ for v in "$@"; do
 done
 for rep in 1 2; do
   for v in "$@"; do
-    SPTR_LIB=$(lib $v) timeout -k 10 300 python3 bench.py --workload ${WL:-c5} --steps 20 --warmup 3 --no-cpu-baseline --no-interactive \
+    SPTR_LIB=$(lib $v) timeout -k 10 300 python3 bench.py --full --workload ${WL:-c5} --steps 20 --warmup 3 --no-cpu-baseline --no-interactive \
       > $o/${WL:-c5}_${v}_$rep.json 2> $o/${WL:-c5}_${v}_$rep.err
     python3 -c "import json;d=json.loads(open('$o/${WL:-c5}_${v}_$rep.json').read().splitlines()[-1]);print('$v $rep',d['ms_per_step'],d.get('stage_ms_untimed_step'))"
   done
