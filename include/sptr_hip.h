@@ -319,7 +319,8 @@ int sptr_render(sptr_ctx* ctx, const sptr_frame* frame, void* stream, sptr_stats
 int sptr_collect_stats(sptr_ctx* ctx, sptr_stats* stats);
 /* Full image RGB8 (width*height*3; only this shard's tiles are written) and the accumulation sums
  * (width*height*3 floats; divide by the frame count for the mean): linear radiance in wavefront
- * mode, tonemapped per-frame colours in PathTracer mode (what GLRenderer accumulates). */
+ * mode, tonemapped per-frame colours in PathTracer mode (what GLRenderer accumulates).  While the
+ * denoiser is on (sptr_set_denoise), sptr_read_rgb8 and sptr_read_rgb8_lagged return the filtered image. */
 int sptr_read_rgb8(sptr_ctx* ctx, uint8_t* rgb);
 /* ABI 9, the interactive loop's readback with one frame of latency (GLRenderer::renderLoop calls render()
  * once per frame, src/GLRenderer.cpp:161-176): call it after an asynchronous render (SPTR_FRAME_ASYNC).  The
@@ -340,6 +341,51 @@ int sptr_tiles_device(sptr_ctx* ctx, void** dptr, size_t* bytes);
  * stream and waits; on a caller's stream it only enqueues. */
 int sptr_unpack_tiles(sptr_ctx* ctx, const void* gathered, int32_t shard_count, uint32_t tiles_per_rank,
                       int32_t width, int32_t height, void* rgb8_out, void* stream);
+
+/* ---- first-hit AOVs and the edge-avoiding denoiser (symbols added within ABI 9: no existing struct or
+ *      entry point changed, so SPTR_ABI_VERSION stays 9) ------------------------------------------------
+ * The interactive loop renders 1 spp per call; these entry points give such a frame a filtered image and
+ * give an external denoiser its feature buffers.  The filter is an a-trous wavelet filter steered by the
+ * first hit's normal, depth and albedo and by the colour itself (DESIGN.md "Denoiser"): iteration i
+ * (i = 0 .. iterations-1) takes a 5x5 B3-spline footprint with a step of 2^i pixels; the colour weight's
+ * sigma fades as 1 / n with the accumulation's frame count n, so a converging image is left alone; pixels
+ * whose camera ray leaves the scene (the environment) and pixels whose mean is not finite pass through.
+ * Only + - x, correctly rounded division, max and compares: a float32 restatement in the same order is
+ * bit-exact (tests/denoise_ref.py). */
+typedef struct sptr_denoise_params {
+  uint32_t iterations;        /* 0 = off (default); 1..5 */
+  float sigma_color;          /* 0 -> 0.5  */
+  float sigma_depth;          /* 0 -> 0.05 */
+  float sigma_albedo;         /* 0 -> 0.2  */
+  uint32_t normal_log2_power; /* 0 -> 6 (cos^64); at most 16 */
+  uint32_t reserved[3];       /* 0 */
+} sptr_denoise_params;
+/* params == NULL or iterations == 0: off.  With the denoiser on, a denoise pass follows every wavefront
+ * render call that resolves (not SPTR_FRAME_NO_RESOLVE), on the call's stream and outside any captured
+ * launch graph, so it also follows SPTR_FRAME_ASYNC calls; it writes a second RGB8 device image, which
+ * sptr_read_rgb8 and sptr_read_rgb8_lagged then return.  The accumulation, sptr_read_accum,
+ * sptr_tiles_device and the stats are untouched, and with the denoiser off a render call issues exactly
+ * the launches it issued before these entry points existed.  With the denoiser on, sptr_render returns
+ * SPTR_ERR_INVALID for a call that is not SPTR_INTEGRATOR_WAVEFRONT or has shard_count > 1 (a shard's
+ * interleaved tiles have no neighbours).  Changing the parameters does not restart the accumulation. */
+int sptr_set_denoise(sptr_ctx* ctx, const sptr_denoise_params* params);
+/* First-hit feature buffers of the last render call's camera and size (any integrator, denoiser on or
+ * off), from one closest-hit query per pixel along the pixel-centre ray (no jitter, tnear 0):
+ *   SPTR_AOV_ALBEDO: W*H*3 floats, materials[geom_material[geomID]].albedo;
+ *   SPTR_AOV_NORMAL: W*H*3 floats, the normalised geometric normal, facing the camera (N.d <= 0);
+ *   SPTR_AOV_DEPTH : W*H floats, the hit distance t;
+ *   SPTR_AOV_ID    : W*H*2 uint32, (geomID, primID) as sptr_intersect reports them.
+ * A miss gives albedo 0, normal 0, depth -1 and ids 0xFFFFFFFF.  The buffers are cached per camera, size
+ * and scene state, as the cull mask is: a static camera pays for them once (sptr_denoise_info). */
+enum { SPTR_AOV_ALBEDO = 0, SPTR_AOV_NORMAL = 1, SPTR_AOV_DEPTH = 2, SPTR_AOV_ID = 3 };
+int sptr_read_aov(sptr_ctx* ctx, int kind, void* out);
+/* The filter's output before the resolve: W*H*3 linear radiance.  An error unless the last render call
+ * ran the denoise pass. */
+int sptr_read_denoised(sptr_ctx* ctx, float* rgb);
+/* Waits for the last denoise pass: device time of its AOV launch (0 when the cached buffers were used)
+ * and of its filter launches (mean, iterations, resolve), and the AOV passes computed so far.  Any
+ * pointer may be NULL. */
+int sptr_denoise_info(const sptr_ctx* ctx, double* ms_aov, double* ms_filter, uint32_t* aov_passes);
 
 /* ---- query entry points (tests / tooling) -------------------------------------------------------- */
 /* Closest-hit / any-hit queries on the device BVH: rays = n*8 floats (o3, d3, tnear, tfar).

@@ -4181,4 +4181,7 @@ void launch_primary(const FrameView& f, float* dirs, uint32_t* rng, hipStream_t 
   hipLaunchKernelGGL(k_primary, dim3(grid_for((uint64_t)f.W * f.H)), dim3(kBlock), 0, s, f, dirs, rng);
 }
 
+// first-hit AOVs and the denoiser (they share this file's traversal and resolve helpers)
+#include "kernels_denoise.h"
+
 }  // namespace sptr

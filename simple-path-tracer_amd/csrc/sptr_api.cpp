@@ -49,6 +49,24 @@ struct sptr_ctx {
   hipEvent_t copy_done = nullptr;
   void* reg_ptr = nullptr;
   size_t reg_bytes = 0;
+  // sptr_set_denoise / sptr_read_aov (the caller's context; a pixel lane holds none).  Everything is in
+  // image space: the AOV planes with the key they were computed for (as the cull mask's), the filter's two
+  // ping-pong colour images and the second RGB8 image the readbacks return while the denoiser is on.
+  struct Denoise {
+    sptr_denoise_params p{};  // iterations 0: off
+    sptr::DevBuf nz, albedo, ids, geom_first, flag, col[2], image;
+    bool geom_first_valid = false;  // (sptr_upload_scene)
+    uint64_t aov_epoch = 0;
+    sptr_camera aov_cam{};
+    int aov_W = 0, aov_H = 0;
+    uint32_t aov_passes = 0;
+    sptr_camera last_cam{};  // the last render call's camera and size (sptr_read_aov)
+    int last_W = 0, last_H = 0;
+    bool ran = false;        // the last render call ran the pass: `image` and col[final] hold its result
+    uint32_t final_col = 0;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // AOV begin / end, filter begin / end
+    bool aov_timed = false, filter_timed = false;             // ... recorded by the last pass
+  } dn;
 };
 
 namespace sptr {
@@ -1408,6 +1426,11 @@ int sptr_destroy(sptr_ctx* x) {
   for (hipEvent_t e : {x->lane_fork, x->lane_join})
     if (e) (void)hipEventDestroy(e);
   free_buf(x->tiles_full);
+  for (DevBuf* b : {&x->dn.nz, &x->dn.albedo, &x->dn.ids, &x->dn.geom_first, &x->dn.flag, &x->dn.col[0], &x->dn.col[1],
+                    &x->dn.image})
+    free_buf(*b);
+  for (hipEvent_t e : x->dn.ev)
+    if (e) (void)hipEventDestroy(e);
   Context& c = x->c;
   (void)hipSetDevice(c.device);
   if (c.pending) (void)hipStreamSynchronize(c.pending_stream);
@@ -1845,7 +1868,8 @@ int sptr_read_rgb8(sptr_ctx* x, uint8_t* rgb) {
   if (x->split && sync_pending(x->lane->c) != SPTR_OK) return SPTR_ERR_HIP;  // (it resolves into this image)
   if (!c.image.p) return fail(c, SPTR_ERR_NO_SCENE, "read_rgb8: nothing rendered");
   API_HIP(hipSetDevice(c.device));
-  API_HIP(hipMemcpy(rgb, c.image.p, (size_t)c.W * c.H * 3, hipMemcpyDeviceToHost));
+  // (the denoised image when the last call ran the denoise pass, sptr_set_denoise)
+  API_HIP(hipMemcpy(rgb, x->dn.ran ? x->dn.image.p : c.image.p, (size_t)c.W * c.H * 3, hipMemcpyDeviceToHost));
   return SPTR_OK;
 }
 
@@ -1869,7 +1893,7 @@ int sptr_read_rgb8_lagged(sptr_ctx* x, uint8_t* rgb, uint32_t* got) {
   // image is joined into that stream before the call's last launch).  The slot's last reader was the copy
   // two calls back, which that call waited for.
   API_HIP(ensure_buf(cur.buf, bytes));
-  API_HIP(hipMemcpyAsync(cur.buf.p, c.image.p, bytes, hipMemcpyDeviceToDevice, c.pending_stream));
+  API_HIP(hipMemcpyAsync(cur.buf.p, x->dn.ran ? x->dn.image.p : c.image.p, bytes, hipMemcpyDeviceToDevice, c.pending_stream));
   API_HIP(hipEventRecord(cur.ready, c.pending_stream));
   if (prev.valid && prev.W == c.W && prev.H == c.H) {
     if (x->reg_ptr != rgb || x->reg_bytes != bytes) {  // page-lock the destination: the copy becomes a DMA
@@ -2134,6 +2158,7 @@ static int lane_forward(sptr_ctx* x, int rc_lane) {
 int sptr_upload_scene(sptr_ctx* x, const sptr_scene* s) {
   const int rc = upload_scene_one(x, s);
   if (rc != SPTR_OK) return rc;
+  x->dn.geom_first_valid = false;
   if (x->split) x->c.W = 0;  // the pixel buffers describe the even lane: re-laid out for the next call
   x->split = false;
   x->lane_scene = false;
@@ -2239,8 +2264,8 @@ static void add_stats(sptr_stats& a, const sptr_stats& b) {
   a.ms_trace_busy = std::max(a.ms_trace_busy, b.ms_trace_busy);  // (the callers set the union)
 }
 
-int sptr_render(sptr_ctx* x, const sptr_frame* f, void* stream, sptr_stats* stats) {
-  if (!x || !f) return SPTR_ERR_INVALID;
+// One render call without the denoise pass (sptr_render, below, appends it).
+static int render_call(sptr_ctx* x, const sptr_frame* f, void* stream, sptr_stats* stats) {
   Context& c = x->c;
   if (!lanes_for(x, f)) {
     if (x->split) {  // leaving a two-lane accumulation: this call must start a new one
@@ -2318,6 +2343,236 @@ int sptr_render(sptr_ctx* x, const sptr_frame* f, void* stream, sptr_stats* stat
   add_stats(a, b);
   a.ms_trace_busy = busy;
   if (stats) *stats = a;
+  return SPTR_OK;
+}
+
+// ---- first-hit AOVs and the denoiser --------------------------------------------------------------
+int sptr_set_denoise(sptr_ctx* x, const sptr_denoise_params* p) {
+  if (!x) return SPTR_ERR_INVALID;
+  Context& c = x->c;
+  if (x->is_lane) return fail(c, SPTR_ERR_INVALID, "denoise: not on a lane context");
+  sptr_denoise_params q{};
+  if (p) q = *p;
+  if (q.iterations > 5u) return fail(c, SPTR_ERR_INVALID, "denoise: at most 5 iterations");
+  if (q.normal_log2_power > 16u) return fail(c, SPTR_ERR_INVALID, "denoise: normal_log2_power above 16");
+  for (float v : {q.sigma_color, q.sigma_depth, q.sigma_albedo})
+    if (!(v >= 0.0f) || !std::isfinite(v)) return fail(c, SPTR_ERR_INVALID, "denoise: a sigma is negative or not finite");
+  if (q.sigma_color == 0.0f) q.sigma_color = 0.5f;
+  if (q.sigma_depth == 0.0f) q.sigma_depth = 0.05f;
+  if (q.sigma_albedo == 0.0f) q.sigma_albedo = 0.2f;
+  if (q.normal_log2_power == 0u) q.normal_log2_power = 6u;
+  x->dn.p = q;  // (by value in the pass's launch arguments: a pending pass keeps the values it was enqueued with)
+  return SPTR_OK;
+}
+
+// The AOV planes of (cam, W, H) on stream s, unless the cached ones were computed for them and for this
+// scene state.  *ran: whether k_aov was launched.
+static int ensure_aov(sptr_ctx* x, const sptr_camera& cam, int W, int H, hipStream_t s, bool timed, bool* ran) {
+  Context& c = x->c;
+  auto& d = x->dn;
+  *ran = false;
+  if (d.aov_epoch == c.epoch && d.aov_W == W && d.aov_H == H && std::memcmp(&d.aov_cam, &cam, sizeof(cam)) == 0)
+    return SPTR_OK;
+  const size_t n = (size_t)W * H;
+  if (d.nz.bytes < n * 16 || d.albedo.bytes < n * 16 || d.ids.bytes < n * 8) {
+    if (sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;  // a pending pass may still read the old planes
+    API_HIP(ensure_buf(d.nz, n * 16));
+    API_HIP(ensure_buf(d.albedo, n * 16));
+    API_HIP(ensure_buf(d.ids, n * 8));
+  }
+  if (!d.flag.p) {
+    API_HIP(ensure_buf(d.flag, 16));
+    API_HIP(hipMemset(d.flag.p, 0, 16));
+  }
+  if (!d.geom_first_valid) {
+    if (sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;
+    API_HIP(ensure_buf(d.geom_first, (c.geom_first.size() + 1) * 4));
+    if (!c.geom_first.empty())
+      API_HIP(hipMemcpy(d.geom_first.p, c.geom_first.data(), c.geom_first.size() * 4, hipMemcpyHostToDevice));
+    d.geom_first_valid = true;
+  }
+  sptr_frame fr{};
+  fr.width = W;
+  fr.height = H;
+  fr.camera = cam;
+  fr.frame_begin = 1;
+  fr.max_depth = 1;
+  const FrameView fv = frame_view(c, fr);
+  AovView a{};
+  a.nz = static_cast<float4*>(d.nz.p);
+  a.albedo = static_cast<float4*>(d.albedo.p);
+  a.ids = static_cast<uint2*>(d.ids.p);
+  a.tri_orig = static_cast<const uint32_t*>(c.tri_orig.p);
+  a.geom_first = static_cast<const uint32_t*>(d.geom_first.p);
+  a.mats = static_cast<const DevMaterial*>(c.mats.p);
+  a.geom_mat = static_cast<const uint32_t*>(c.geom_mat.p);
+  a.stack_overflow = static_cast<uint32_t*>(d.flag.p);
+  if (timed) API_HIP(hipEventRecord(d.ev[0], s));
+  launch_aov(scene_view(c), fv, a, s);
+  API_HIP(hipGetLastError());
+  if (timed) API_HIP(hipEventRecord(d.ev[1], s));
+  d.aov_epoch = c.epoch;
+  d.aov_cam = cam;
+  d.aov_W = W;
+  d.aov_H = H;
+  ++d.aov_passes;
+  *ran = true;
+  return SPTR_OK;
+}
+
+// The denoise pass of the render call just enqueued on s: AOVs (if not cached), c_0, the a-trous
+// iterations, the resolve into the second RGB8 image.  Direct launches, outside any captured graph.
+static int enqueue_denoise(sptr_ctx* x, const sptr_frame* f, hipStream_t s) {
+  Context& c = x->c;
+  auto& d = x->dn;
+  for (hipEvent_t& e : d.ev)
+    if (!e) API_HIP(hipEventCreate(&e));
+  const int W = f->width, H = f->height;
+  const size_t n = (size_t)W * H;
+  if (d.col[0].bytes < n * 16 || d.col[1].bytes < n * 16 || d.image.bytes < n * 3) {
+    if (sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;
+    API_HIP(ensure_buf(d.col[0], n * 16));
+    API_HIP(ensure_buf(d.col[1], n * 16));
+    API_HIP(ensure_buf(d.image, n * 3));
+  }
+  bool aov_ran = false;
+  const int rc = ensure_aov(x, f->camera, W, H, s, true, &aov_ran);
+  if (rc != SPTR_OK) return rc;
+  d.aov_timed = aov_ran;
+  DenoiseView v{};
+  v.W = W;
+  v.H = H;
+  v.n = f->frame_begin + f->spp - 1;
+  v.nz = static_cast<const float4*>(d.nz.p);
+  v.albedo = static_cast<const float4*>(d.albedo.p);
+  v.sigma_z = d.p.sigma_depth;
+  v.sigma_a2 = d.p.sigma_albedo * d.p.sigma_albedo;
+  v.normal_log2 = d.p.normal_log2_power;
+  float4* col[2] = {static_cast<float4*>(d.col[0].p), static_cast<float4*>(d.col[1].p)};
+  API_HIP(hipEventRecord(d.ev[2], s));
+  // two pixel lanes: this context holds the even tiles (shard 0 of 2), the lane the odd ones
+  launch_dn_mean(v, static_cast<const float4*>(c.accum.p), x->split ? static_cast<const float4*>(x->lane->c.accum.p) : nullptr,
+                 x->split ? 2 : 1, col[0], s);
+  uint32_t cur = 0;
+  for (uint32_t i = 0; i < d.p.iterations; ++i) {
+    const float S = d.p.sigma_color * (1.0f / float(1u << i)) / float(v.n);  // sigma_c 2^-i / n
+    launch_atrous(v, col[cur], col[cur ^ 1u], 1 << i, S * S, s);
+    cur ^= 1u;
+  }
+  launch_dn_resolve(v, col[cur], static_cast<uint8_t*>(d.image.p), s);
+  API_HIP(hipGetLastError());
+  API_HIP(hipEventRecord(d.ev[3], s));
+  d.filter_timed = true;
+  d.final_col = cur;
+  d.ran = true;
+  return SPTR_OK;
+}
+
+int sptr_render(sptr_ctx* x, const sptr_frame* f, void* stream, sptr_stats* stats) {
+  if (!x || !f) return SPTR_ERR_INVALID;
+  Context& c = x->c;
+  const bool dn = x->dn.p.iterations != 0u && !x->is_lane;
+  if (!dn) {
+    const int rc = render_call(x, f, stream, stats);
+    if (rc == SPTR_OK) {
+      x->dn.ran = false;
+      x->dn.last_cam = f->camera;
+      x->dn.last_W = f->width;
+      x->dn.last_H = f->height;
+    }
+    return rc;
+  }
+  if (f->integrator != SPTR_INTEGRATOR_WAVEFRONT)
+    return fail(c, SPTR_ERR_INVALID, "render: the denoiser runs with SPTR_INTEGRATOR_WAVEFRONT only (sptr_set_denoise)");
+  if (f->shard_count > 1)
+    return fail(c, SPTR_ERR_INVALID, "render: the denoiser needs the whole image (shard_count 1): a shard's tiles have no neighbours");
+  // the call is enqueued without waiting, the pass after it on the same stream; a synchronous call is
+  // then collected as sptr_collect_stats collects asynchronous ones
+  sptr_frame fa = *f;
+  fa.flags |= SPTR_FRAME_ASYNC;
+  int rc = render_call(x, &fa, stream, nullptr);
+  if (rc != SPTR_OK) return rc;
+  x->dn.last_cam = f->camera;
+  x->dn.last_W = f->width;
+  x->dn.last_H = f->height;
+  x->dn.ran = false;
+  if (!(f->flags & SPTR_FRAME_NO_RESOLVE)) {
+    rc = enqueue_denoise(x, f, c.pending_stream);
+    if (rc != SPTR_OK) return rc;
+  }
+  if (f->flags & SPTR_FRAME_ASYNC) {
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    return SPTR_OK;
+  }
+  return sptr_collect_stats(x, stats);
+}
+
+int sptr_read_aov(sptr_ctx* x, int kind, void* out) {
+  if (!x || !out) return SPTR_ERR_INVALID;
+  Context& c = x->c;
+  if (kind < SPTR_AOV_ALBEDO || kind > SPTR_AOV_ID) return fail(c, SPTR_ERR_INVALID, "read_aov: unknown kind");
+  if (!c.have_scene || x->dn.last_W <= 0) return fail(c, SPTR_ERR_NO_SCENE, "read_aov: nothing rendered");
+  if (shading(c).mats_host.empty()) return fail(c, SPTR_ERR_NO_SCENE, "read_aov: no materials set");
+  API_HIP(hipSetDevice(c.device));
+  if (sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;
+  auto& d = x->dn;
+  bool ran = false;
+  const int rc = ensure_aov(x, d.last_cam, d.last_W, d.last_H, c.stream, false, &ran);
+  if (rc != SPTR_OK) return rc;
+  API_HIP(hipStreamSynchronize(c.stream));
+  uint32_t flag = 0;
+  API_HIP(hipMemcpy(&flag, d.flag.p, 4, hipMemcpyDeviceToHost));
+  if (flag) return fail(c, SPTR_ERR_HIP, "read_aov: BVH traversal stack overflow (internal error)");
+  const size_t n = (size_t)d.last_W * d.last_H;
+  if (kind == SPTR_AOV_ID) {
+    API_HIP(hipMemcpy(out, d.ids.p, n * 8, hipMemcpyDeviceToHost));
+    return SPTR_OK;
+  }
+  std::vector<float> tmp(n * 4);
+  API_HIP(hipMemcpy(tmp.data(), kind == SPTR_AOV_ALBEDO ? d.albedo.p : d.nz.p, n * 16, hipMemcpyDeviceToHost));
+  float* o = static_cast<float*>(out);
+  for (size_t i = 0; i < n; ++i) {
+    if (kind == SPTR_AOV_DEPTH) {
+      o[i] = tmp[i * 4 + 3];
+    } else {
+      o[i * 3 + 0] = tmp[i * 4 + 0];
+      o[i * 3 + 1] = tmp[i * 4 + 1];
+      o[i * 3 + 2] = tmp[i * 4 + 2];
+    }
+  }
+  return SPTR_OK;
+}
+
+int sptr_read_denoised(sptr_ctx* x, float* rgb) {
+  if (!x || !rgb) return SPTR_ERR_INVALID;
+  Context& c = x->c;
+  auto& d = x->dn;
+  if (!d.ran) return fail(c, SPTR_ERR_INVALID, "read_denoised: the last render call ran no denoise pass (sptr_set_denoise)");
+  API_HIP(hipSetDevice(c.device));
+  if (sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;
+  const size_t n = (size_t)d.last_W * d.last_H;
+  std::vector<float> tmp(n * 4);
+  API_HIP(hipMemcpy(tmp.data(), d.col[d.final_col].p, n * 16, hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < n; ++i) {
+    rgb[i * 3 + 0] = tmp[i * 4 + 0];
+    rgb[i * 3 + 1] = tmp[i * 4 + 1];
+    rgb[i * 3 + 2] = tmp[i * 4 + 2];
+  }
+  return SPTR_OK;
+}
+
+int sptr_denoise_info(const sptr_ctx* x, double* ms_aov, double* ms_filter, uint32_t* aov_passes) {
+  if (!x) return SPTR_ERR_INVALID;
+  const auto& d = x->dn;
+  float a = 0.0f, fl = 0.0f;
+  if (d.ran && d.filter_timed) {
+    if (hipEventSynchronize(d.ev[3]) != hipSuccess) return SPTR_ERR_HIP;
+    if (d.aov_timed) (void)hipEventElapsedTime(&a, d.ev[0], d.ev[1]);
+    (void)hipEventElapsedTime(&fl, d.ev[2], d.ev[3]);
+  }
+  if (ms_aov) *ms_aov = a;
+  if (ms_filter) *ms_filter = fl;
+  if (aov_passes) *aov_passes = d.aov_passes;
   return SPTR_OK;
 }
 

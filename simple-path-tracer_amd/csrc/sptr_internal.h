@@ -295,6 +295,27 @@ struct WaveView {
   unsigned long long* tslot = nullptr;
 };
 
+// First-hit AOVs (k_aov), image space (pixel y * W + x): two float4 planes and the ids.
+struct AovView {
+  float4* nz;      // normal.xyz (facing the camera), depth t; a miss: 0 0 0 -1
+  float4* albedo;  // albedo.xyz, 0; a miss: 0
+  uint2* ids;      // geomID, primID; a miss: kNoHit twice
+  const uint32_t* tri_orig;    // triangle slot -> index in the uploaded triangle list
+  const uint32_t* geom_first;  // geomID -> its first triangle in that list
+  const DevMaterial* mats;
+  const uint32_t* geom_mat;
+  uint32_t* stack_overflow;    // sticky flag (cannot happen within the build's stack bound)
+};
+// The denoiser's per-pass constants (k_dn_mean, k_atrous, k_dn_resolve), image space.
+struct DenoiseView {
+  int32_t W, H;
+  uint32_t n;  // frames in the accumulation after the call
+  const float4* nz;
+  const float4* albedo;
+  float sigma_z, sigma_a2;  // sigma_depth; sigma_albedo squared
+  uint32_t normal_log2;     // the normal weight is max(0, Np.Nq) squared this many times
+};
+
 struct DevBuf {
   void* p = nullptr;
   size_t bytes = 0;
@@ -521,6 +542,13 @@ void launch_query(const SceneView& sv, const uint32_t* tri_orig, const uint32_t*
                   bool anyhit, uint32_t* ref, float* t, float* ng, uint8_t* occ, uint32_t* stack_overflow, hipStream_t s);
 void launch_primary(const FrameView& f, float* dirs, uint32_t* rng, hipStream_t s);
 void launch_eval_math(int fn, const float* x, uint32_t n, float* out, hipStream_t s);
+// kernels_denoise.h: the first-hit AOVs of f's camera and size, and the denoiser's launches (c_0 from the
+// one or two lanes' accumulations; one a-trous iteration with pixel step `step` and squared colour sigma
+// S2; the resolve of the filtered mean into an RGB8 image)
+void launch_aov(const SceneView& sv, const FrameView& f, const AovView& a, hipStream_t s);
+void launch_dn_mean(const DenoiseView& v, const float4* accum0, const float4* accum1, int G, float4* out, hipStream_t s);
+void launch_atrous(const DenoiseView& v, const float4* cin, float4* cout, int step, float S2, hipStream_t s);
+void launch_dn_resolve(const DenoiseView& v, const float4* c, uint8_t* image, hipStream_t s);
 // one wave spinning for `ticks` of the device wall clock (sptr_overlap_probe)
 void launch_spin(uint64_t ticks, hipStream_t s);
 

@@ -3,6 +3,7 @@
 
 #include <cmath>
 #include <cstdio>
+#include <cstring>
 
 namespace backends {
 
@@ -75,6 +76,10 @@ bool HipBackend::syncState() {
     if (sptr_set_environment(ctx_, &e) != SPTR_OK) return false;
     env_dirty_ = false;
     frame_index_ = 0;
+  }
+  if (std::memcmp(&settings_.denoise, &denoise_applied_, sizeof(sptr_denoise_params)) != 0) {
+    if (sptr_set_denoise(ctx_, &settings_.denoise) != SPTR_OK) return false;
+    denoise_applied_ = settings_.denoise;  // (the accumulation goes on: the filter only reads it)
   }
   return true;
 }

@@ -36,6 +36,10 @@ class HipBackend {
     // resize is read synchronously.  The pixel buffer stays page-locked while render() writes into it.
     // Counters (stats()) are collected every kLaggedCollect calls and by flushStats().
     bool lagged_readback = false;
+    // sptr_set_denoise: iterations 0 = off (default); 1..5 = every render() returns the frame filtered by
+    // the edge-avoiding a-trous denoiser (wavefront integrator only; with lagged_readback, the denoised
+    // previous frame).  Zero sigmas / power take the defaults.  A change does not restart the accumulation.
+    sptr_denoise_params denoise{};
   };
   static constexpr uint32_t kLaggedCollect = 32;
 
@@ -59,6 +63,11 @@ class HipBackend {
   const sptr_stats& stats() const { return stats_; }
   // the counters of every render() since the last flush, summed (waits for the pending frames)
   sptr_stats flushStats();
+  // sptr_denoise_info of the last render(): device ms of its AOV launch (0: cached) and filter launches
+  // (waits for that pass), and the AOV passes computed so far
+  bool denoiseInfo(double* ms_aov, double* ms_filter, uint32_t* aov_passes) const {
+    return ctx_ && sptr_denoise_info(ctx_, ms_aov, ms_filter, aov_passes) == SPTR_OK;
+  }
   uint32_t frameIndex() const { return frame_index_; }
   const std::string& lastError() const { return err_; }
   const std::vector<uint32_t>& getGeomMaterialMapping() const { return geom_material_; }
@@ -85,6 +94,7 @@ class HipBackend {
   std::string err_;
   int debug_mode_ = 0;
   uint32_t lanes_applied_ = 0;  // the pixel-lane setting the context holds
+  sptr_denoise_params denoise_applied_{};  // the denoiser parameters the context holds
   sptr_stats flushed_{};        // counters since the last flushStats()
   uint32_t async_calls_ = 0;    // lagged mode: render calls not yet collected
 };

@@ -106,6 +106,13 @@ class SceneLayout(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class DenoiseParams(C.Structure):
+    _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_depth", C.c_float),
+                ("sigma_albedo", C.c_float), ("normal_log2_power", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+SPTR_AOV_ALBEDO, SPTR_AOV_NORMAL, SPTR_AOV_DEPTH, SPTR_AOV_ID = 0, 1, 2, 3
+
 _lib = None
 
 # every symbol include/sptr_hip.h declares
@@ -117,6 +124,7 @@ EXPORTS = [
     "sptr_read_accum",
     "sptr_tiles_device", "sptr_unpack_tiles", "sptr_intersect", "sptr_occluded", "sptr_primary_rays",
     "sptr_sort_pairs_u64", "sptr_scan_u32", "sptr_eval_math",
+    "sptr_set_denoise", "sptr_read_aov", "sptr_read_denoised", "sptr_denoise_info",
     "sptr_host_builtin_scene", "sptr_host_scene_view", "sptr_host_scene_free", "sptr_host_camera_lookat",
     "sptr_host_preset_materials", "sptr_host_default_lights", "sptr_host_equirect_to_faces",
     "sptr_host_pack_tiles", "sptr_host_unpack_tiles", "sptr_host_load_hdr", "sptr_host_free",
@@ -170,6 +178,10 @@ def lib() -> C.CDLL:
         "sptr_sort_pairs_u64": (C.c_int, [vp, C.POINTER(C.c_uint64), up, u32, C.POINTER(C.c_uint64), up]),
         "sptr_scan_u32": (C.c_int, [vp, up, u32, up]),
         "sptr_eval_math": (C.c_int, [vp, C.c_int, fp, u32, fp]),
+        "sptr_set_denoise": (C.c_int, [vp, C.POINTER(DenoiseParams)]),
+        "sptr_read_aov": (C.c_int, [vp, C.c_int, vp]),
+        "sptr_read_denoised": (C.c_int, [vp, fp]),
+        "sptr_denoise_info": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), up]),
         "sptr_host_builtin_scene": (C.c_int, [C.c_char_p, u32, u32, C.POINTER(vp)]),
         "sptr_host_scene_view": (C.c_int, [vp, C.POINTER(Scene)]),
         "sptr_host_scene_free": (None, [vp]),
@@ -503,6 +515,36 @@ class Renderer:
         out = np.zeros((self.height, self.width, 3), np.float32)
         self._check(self._L.sptr_read_accum(self._h, _f(out)), "read_accum")
         return out
+
+    def set_denoise(self, iterations: int = 0, sigma_color: float = 0.0, sigma_depth: float = 0.0,
+                    sigma_albedo: float = 0.0, normal_log2_power: int = 0):
+        """sptr_set_denoise: iterations 0 = off, 1..5 = an edge-avoiding a-trous pass after every wavefront
+        render call (read_rgb8 / read_rgb8_lagged then return the filtered image); a zero parameter takes
+        its default (0.5, 0.05, 0.2, 6)."""
+        p = DenoiseParams(iterations, sigma_color, sigma_depth, sigma_albedo, normal_log2_power)
+        self._check(self._L.sptr_set_denoise(self._h, C.byref(p) if iterations else None), "set_denoise")
+
+    def read_aov(self, kind: int) -> np.ndarray:
+        """First-hit feature buffer of the last render call's camera and size: SPTR_AOV_ALBEDO / _NORMAL
+        (H, W, 3) float32, SPTR_AOV_DEPTH (H, W) float32 (-1 on a miss), SPTR_AOV_ID (H, W, 2) uint32
+        (geomID, primID; 0xFFFFFFFF on a miss)."""
+        shape, dt = {SPTR_AOV_ALBEDO: ((3,), np.float32), SPTR_AOV_NORMAL: ((3,), np.float32),
+                     SPTR_AOV_DEPTH: ((), np.float32), SPTR_AOV_ID: ((2,), np.uint32)}[kind]
+        out = np.zeros((self.height, self.width) + shape, dt)
+        self._check(self._L.sptr_read_aov(self._h, kind, out.ctypes.data_as(C.c_void_p)), "read_aov")
+        return out
+
+    def read_denoised(self) -> np.ndarray:
+        """The filter's output of the last render call, before the resolve: (H, W, 3) linear radiance."""
+        out = np.zeros((self.height, self.width, 3), np.float32)
+        self._check(self._L.sptr_read_denoised(self._h, _f(out)), "read_denoised")
+        return out
+
+    def denoise_info(self) -> dict:
+        """Device ms of the last denoise pass's AOV launch (0: cached) and filter launches; AOV passes so far."""
+        a, f, n = C.c_double(), C.c_double(), C.c_uint32()
+        self._check(self._L.sptr_denoise_info(self._h, C.byref(a), C.byref(f), C.byref(n)), "denoise_info")
+        return {"ms_aov": a.value, "ms_filter": f.value, "aov_passes": n.value}
 
     def tiles_device(self) -> tuple[int, int]:
         p = C.c_void_p()

@@ -5,12 +5,15 @@
 //   sptr_cli [--scene default|default_emitter|test_triangle|sphere_mesh:STACKS:SLICES|gltf:PATH]
 //            [--w 800] [--h 600] [--spp 4] [--depth 6] [--env sky|FILE.hdr] [--out image.ppm]
 //            [--warmup N] [--json] [--integrator wavefront|pathtracer|optix] [--spf 4] [--launch-mode 0-3]
-//            [--lagged]
+//            [--lagged] [--denoise N]
 // --spp N renders N progressive frames of 1 spp each (GLRenderer's m_accumulated_samples loop);
 // --warmup N renders N untimed frames first (then restarts the accumulation by a camera change);
 // --json prints one line with per-frame wall-clock statistics (render + RGB8 read back, as the
 // window loop pays them) for bench.py's interactive leg.  --lagged: HipBackend::Settings::lagged_readback
 // (each render() returns the previous frame's image, read back beside the next frame's kernels).
+// --denoise N: HipBackend::Settings::denoise with N a-trous iterations (1..5, default parameters): every
+// frame comes back filtered, and the --json line's ms_aov / ms_filter are the per-frame means of the
+// pass's device times (sptr_denoise_info; with --lagged, the last frame's alone).
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -45,7 +48,7 @@ int main(int argc, char** argv) {
   int w = 800, h = 600, spp = 4, depth = 6, warmup = 0;
   bool json = false, lagged = false;
   std::string integrator = "wavefront";
-  int spf = 4, launch_mode = 0;
+  int spf = 4, launch_mode = 0, denoise = 0;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
     auto next = [&](void) -> const char* { return i + 1 < argc ? argv[++i] : ""; };
@@ -62,8 +65,9 @@ int main(int argc, char** argv) {
     else if (a == "--spf") spf = std::atoi(next());
     else if (a == "--launch-mode") launch_mode = std::atoi(next());
     else if (a == "--lagged") lagged = true;
+    else if (a == "--denoise") denoise = std::atoi(next());
     else {
-      std::fprintf(stderr, "usage: %s [--scene S] [--w W] [--h H] [--spp N] [--depth D] [--env sky|F.hdr] [--out F] [--warmup N] [--json]\n",
+      std::fprintf(stderr, "usage: %s [--scene S] [--w W] [--h H] [--spp N] [--depth D] [--env sky|F.hdr] [--out F] [--warmup N] [--json] [--lagged] [--denoise N]\n",
                    argv[0]);
       return 2;
     }
@@ -97,6 +101,7 @@ int main(int argc, char** argv) {
   st.samples_per_frame = uint32_t(spf);
   st.launch_mode = uint32_t(launch_mode);
   st.lagged_readback = lagged;
+  st.denoise.iterations = uint32_t(std::max(0, denoise));
   be.setSettings(st);
   if (!be.build(sd)) {
     std::fprintf(stderr, "%s\n", be.lastError().c_str());
@@ -109,11 +114,22 @@ int main(int argc, char** argv) {
   }
   std::vector<double> frame_ms;
   frame_ms.reserve(size_t(spp));
+  double ms_aov = 0.0, ms_filter = 0.0;
+  uint32_t aov_passes = 0;
+  int dn_frames = 0;
   (void)be.flushStats();  // (the warmup's counters)
   const auto t0 = std::chrono::steady_clock::now();
   for (int f = 0; f < spp; ++f) {
     const auto f0 = std::chrono::steady_clock::now();
     be.render(img.data(), w, h, cam);
+    if (denoise > 0 && (!lagged || f == spp - 1)) {  // (waits for the pass: a lagged loop asks once, at its end)
+      double a = 0.0, fl = 0.0;
+      if (be.denoiseInfo(&a, &fl, &aov_passes)) {
+        ms_aov += a;
+        ms_filter += fl;
+        ++dn_frames;
+      }
+    }
     frame_ms.push_back(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - f0).count());
   }
   const sptr_stats tot = be.flushStats();  // (lagged: waits for the last frames, inside the clock)
@@ -127,9 +143,10 @@ int main(int argc, char** argv) {
     std::printf("{\"scene\": \"%s\", \"launch_mode\": %d, \"width\": %d, \"height\": %d, \"frames\": %d, \"spp_per_frame\": 1, "
                 "\"depth\": %d, \"ms_per_frame_wall\": %.4f, \"ms_per_frame_p50\": %.4f, \"ms_per_frame_p99\": %.4f, "
                 "\"ms_per_frame_device\": %.4f, \"fps\": %.1f, \"mrays_per_s_wall\": %.1f, "
-                "\"lagged_readback\": %s, \"path\": \"backends::HipBackend::render (sptr_render + %s per frame)\"}\n",
+                "\"lagged_readback\": %s, \"denoise\": %d, \"ms_aov\": %.4f, \"ms_filter\": %.4f, \"aov_passes\": %u, \"path\": \"backends::HipBackend::render (sptr_render + %s per frame)\"}\n",
                 scene_name.c_str(), launch_mode, w, h, spp, depth, wall / spp, pct(0.5), pct(0.99), ms / spp,
-                wall > 0 ? 1e3 * spp / wall : 0.0, wall > 0 ? rays / (wall * 1e3) : 0.0, lagged ? "true" : "false",
+                wall > 0 ? 1e3 * spp / wall : 0.0, wall > 0 ? rays / (wall * 1e3) : 0.0, lagged ? "true" : "false", denoise, dn_frames ? ms_aov / dn_frames : 0.0,
+                dn_frames ? ms_filter / dn_frames : 0.0, aov_passes,
                 lagged ? "sptr_read_rgb8_lagged" : "sptr_read_rgb8");
   } else {
     std::printf("scene=%s %dx%d spp=%d depth=%d: %.2f ms device, %.2f ms wall, %.1f Mrays/s (device)\n",
