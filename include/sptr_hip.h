@@ -387,6 +387,41 @@ int sptr_read_denoised(sptr_ctx* ctx, float* rgb);
  * pointer may be NULL. */
 int sptr_denoise_info(const sptr_ctx* ctx, double* ms_aov, double* ms_filter, uint32_t* aov_passes);
 
+/* ---- dynamic scenes: refit the BVH in place when geometry moves (symbols added within ABI 9: no
+ *      existing struct or entry point changed) --------------------------------------------------------
+ * A scene whose coordinates change but whose topology does not (an animated or edited mesh, moving
+ * spheres) need not be uploaded again: sptr_update_geometry recomputes the triangle records, the spheres
+ * and every box of the BVH2 and of the wide BVH in place, with the tree topology and the slot order of
+ * the upload (DESIGN.md "Dynamic scenes").  No sort, tree construction, treelet or collapse pass runs.
+ * The records and the quantised nodes come from the device functions the build itself calls, so a hit's t
+ * and Ng equal those of a fresh upload of the moved scene bit for bit, and the original coordinates give
+ * the original nodes back.  The tree's quality degrades as the geometry deforms away from the uploaded
+ * one (the boxes stay tight, their overlap grows): upload again when traversal gets slow. */
+/* 1: the next sptr_upload_scene keeps what a refit needs (the index triples in slot order, a box per
+ * slot, the BVH2 nodes grouped by subtree height, per wide node the BVH2 boxes its children came from:
+ * about 44 B per triangle + 4 B per BVH2 node + 16 B per wide node); the tree and every result are those
+ * of an ordinary upload.  0 (default): uploads allocate, launch and keep exactly what they always did. */
+int sptr_set_dynamic(sptr_ctx* ctx, uint32_t on);
+
+enum { SPTR_UPDATE_DEVICE_PTRS = 1u };  /* positions / spheres are device pointers on ctx's device */
+/* New coordinates for the uploaded topology: positions = num_verts*3 floats or NULL (unchanged),
+ * spheres = num_spheres*4 floats or NULL (unchanged).  Counts must equal the upload's.  The indices, the
+ * geometry order and the material map stay as uploaded.  Waits for pending renders, as the upload does,
+ * and returns when the refit is complete (a pixel lane's copy of the scene included).  The state epoch is
+ * bumped: the cull mask, the AOV cache and captured launch graphs are invalidated as after an upload.
+ * Restarting the accumulation (frame_begin = 1) is the caller's job, as after an upload.
+ * Triangles that were exactly degenerate (zero Ng) at upload were left out of the tree and stay out: their
+ * records follow the new coordinates, but no ray can hit them until the scene is uploaded again.
+ * SPTR_ERR_NO_SCENE before an upload; SPTR_ERR_INVALID when the scene was not uploaded with
+ * sptr_set_dynamic(1), a count differs from the upload's, both pointers are NULL, or the scene was built
+ * with split references (sptr_set_split_refs took effect: num_prim_refs > num_tris + num_spheres). */
+int sptr_update_geometry(sptr_ctx* ctx, const float* positions, uint32_t num_verts,
+                         const float* spheres, uint32_t num_spheres, uint32_t flags);
+/* refits since the upload; wall ms of the last one (as build_ms is measured); device ms of its kernels;
+ * triangles left out of the tree because they were exactly degenerate at upload. Any pointer may be NULL. */
+int sptr_refit_info(const sptr_ctx* ctx, uint32_t* refits, double* ms_wall, double* ms_device,
+                    uint32_t* excluded_prims);
+
 /* ---- query entry points (tests / tooling) -------------------------------------------------------- */
 /* Closest-hit / any-hit queries on the device BVH: rays = n*8 floats (o3, d3, tnear, tfar).
  * Outputs as rtcIntersect1 reports them: geomID (0xFFFFFFFF on miss), primID, t, unnormalised Ng. */

@@ -27,6 +27,9 @@
 //                   fixed collapse of every second LBVH level it replaced left nodes half empty:
 //                   C5 15.58 -> 15.38 ms/step; opening by area x primitives and a host-built SAH BVH2
 //                   were A/B-only experiments, removed r05.)
+// Dynamic scenes (sptr_set_dynamic): the build also keeps what the in-place refit of kernels_refit.hip
+// needs — the final tree's nodes grouped by subtree height (k_heights and the counting sort once more),
+// the wide nodes' source table, the slot-order index triples and the first position boxes.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -35,6 +38,7 @@
 #include <cstring>
 #include <vector>
 
+#include "lbvh_shared.h"
 #include "sptr_internal.h"
 
 // treelet size (leaves) of the SAH restructuring of L2/HBM scenes' LBVH (r03u/v A/B); a restructured
@@ -86,12 +90,9 @@ __device__ __forceinline__ void prim_box(const BuildIn& in, uint32_t i, vec3& lo
     const vec3 p0 = v3(in.pos[3 * a], in.pos[3 * a + 1], in.pos[3 * a + 2]);
     const vec3 p1 = v3(in.pos[3 * b], in.pos[3 * b + 1], in.pos[3 * b + 2]);
     const vec3 p2 = v3(in.pos[3 * c], in.pos[3 * c + 1], in.pos[3 * c + 2]);
-    lo = v3(fminf(p0.x, fminf(p1.x, p2.x)), fminf(p0.y, fminf(p1.y, p2.y)), fminf(p0.z, fminf(p1.z, p2.z)));
-    hi = v3(fmaxf(p0.x, fmaxf(p1.x, p2.x)), fmaxf(p0.y, fmaxf(p1.y, p2.y)), fmaxf(p0.z, fmaxf(p1.z, p2.z)));
+    tri_box(p0, p1, p2, lo, hi);
   } else {
-    const float4 s = in.sph[i - in.ntri];
-    lo = v3(s.x - s.w, s.y - s.w, s.z - s.w);
-    hi = v3(s.x + s.w, s.y + s.w, s.z + s.w);
+    sphere_box(in.sph[i - in.ntri], lo, hi);
   }
 }
 
@@ -263,9 +264,7 @@ __device__ __forceinline__ vec3 tri_ng(const BuildIn& in, uint32_t prim) {
   const vec3 v0 = v3(in.pos[3 * a], in.pos[3 * a + 1], in.pos[3 * a + 2]);
   const vec3 v1 = v3(in.pos[3 * b], in.pos[3 * b + 1], in.pos[3 * b + 2]);
   const vec3 v2 = v3(in.pos[3 * c], in.pos[3 * c + 1], in.pos[3 * c + 2]);
-  const vec3 e1 = v0 - v1, e2 = v2 - v0;
-  return v3(__builtin_fmaf(e2.y, e1.z, -(e2.z * e1.y)), __builtin_fmaf(e2.z, e1.x, -(e2.x * e1.z)),
-            __builtin_fmaf(e2.x, e1.y, -(e2.y * e1.x)));
+  return tri_ng3(v0, v1, v2);
 }
 // Morton code of the centroid; a triangle whose stored Ng is exactly zero (two equal vertices: e.g.
 // the 1250x4000 sphere mesh's north-pole ring, whose vertices are all (+-0, r, +-0)) gets bit 63, so
@@ -319,11 +318,11 @@ __global__ void k_leaves(BuildIn in, uint32_t N, const uint32_t* vals, const uin
       const vec3 v0 = v3(in.pos[3 * a], in.pos[3 * a + 1], in.pos[3 * a + 2]);
       const vec3 v1 = v3(in.pos[3 * b], in.pos[3 * b + 1], in.pos[3 * b + 2]);
       const vec3 v2 = v3(in.pos[3 * c], in.pos[3 * c + 1], in.pos[3 * c + 2]);
-      const vec3 e1 = v0 - v1, e2 = v2 - v0;
-      const vec3 ng = tri_ng(in, prim);  // Ng = cross(e2, e1) with Embree's msub (fma) evaluation
-      tris[3 * slot + 0] = make_float4(v0.x, v0.y, v0.z, e1.x);
-      tris[3 * slot + 1] = make_float4(e1.y, e1.z, e2.x, e2.y);
-      tris[3 * slot + 2] = make_float4(e2.z, ng.x, ng.y, ng.z);
+      float4 rec[3];  // Ng = cross(e2, e1) with Embree's msub (fma) evaluation (tri_record, lbvh_shared.h)
+      tri_record(v0, v1, v2, rec);
+      tris[3 * slot + 0] = rec[0];
+      tris[3 * slot + 1] = rec[1];
+      tris[3 * slot + 2] = rec[2];
       tri_geom[slot] = in.tri_geom[prim];
       tri_orig[slot] = prim;
       prim_ref[i] = slot;
@@ -771,114 +770,8 @@ __global__ void __launch_bounds__(kTreeletBlock) k_treelet(const uint32_t* order
   }
 }
 
-struct WideBoxes {
-  float lo[3][kWide], hi[3][kWide];
-  uint32_t link[kWide];
-};
-
-// Quantise the n child boxes of one wide node (WideNode): per axis, org = the smallest lower
-// plane, step 2^e the smallest power of two (e in [-100, 60]) with extent <= 255 * 2^e, qlo =
-// floor((lo - org) / 2^e) and qhi = ceil((hi - org) / 2^e) evaluated in double (exact for the
-// scene's float coordinates), so the decoded box always contains the child box.
-__device__ __forceinline__ WideNode quantize_wide(const WideBoxes& b, int n, uint32_t parent) {
-  WideNode o;
-  float org[3];
-  uint32_t ex = (uint32_t)n << 24;
-  for (int w = 0; w < 6; ++w)
-    for (int j = 0; j < kQWords; ++j) o.q[w][j] = 0u;
-  for (int a = 0; a < 3; ++a) {
-    float mn = b.lo[a][0], mx = b.hi[a][0];
-    for (int k = 1; k < n; ++k) {
-      mn = fminf(mn, b.lo[a][k]);
-      mx = fmaxf(mx, b.hi[a][k]);
-    }
-    org[a] = mn;
-    const double ext = (double)mx - (double)mn;
-    int e = -100;
-    if (ext > 0.0) {
-      int x;
-      (void)frexp(ext / 255.0, &x);  // ext / 255 in (2^(x-1), 2^x]
-      e = x;
-      if (ext <= 255.0 * ldexp(1.0, e - 1)) --e;
-      e = e < -100 ? -100 : (e > 60 ? 60 : e);
-    }
-    ex |= (uint32_t)(e + 127) << (8 * a);
-    const double inv_step = ldexp(1.0, -e);
-    for (int k = 0; k < n; ++k) {
-      double l = floor(((double)b.lo[a][k] - (double)mn) * inv_step), h = ceil(((double)b.hi[a][k] - (double)mn) * inv_step);
-      l = l < 0.0 ? 0.0 : (l > 255.0 ? 255.0 : l);
-      h = h < 0.0 ? 0.0 : (h > 255.0 ? 255.0 : h);
-      o.q[2 * a][k / 4] |= (uint32_t)l << (8 * (k % 4));
-      o.q[2 * a + 1][k / 4] |= (uint32_t)h << (8 * (k % 4));
-    }
-  }
-  o.ox = org[0];
-  o.oy = org[1];
-  o.oz = org[2];
-  o.ex = ex;
-  for (int k = 0; k < kWide; ++k) o.link[k] = b.link[k];
-  o.parent = parent;
-  for (uint32_t& x : o.pad) x = 0u;
-  return o;
-}
-
-// Greedy surface-area collapse, top-down one wide level per launch pair: a wide
-// node's child list starts as its BVH2 node's two children and grows, up to kWide entries, by
-// opening the internal entry whose box has the largest surface area (lowest slot on ties) — it is
-// replaced in place by its left and right children, so the list stays in left-to-right order.
-// Unlike a fixed two-level collapse this fills nodes whose grandchildren include leaves and spends
-// the wide levels where the big boxes are, so deep LBVH chains give shallower wide trees.
-// Its internal entries become the next level's wide nodes.
-__device__ __forceinline__ float box_area(const WideBoxes& b, int e) {
-  const float dx = b.hi[0][e] - b.lo[0][e], dy = b.hi[1][e] - b.lo[1][e], dz = b.hi[2][e] - b.lo[2][e];
-  return dx * dy + dy * dz + dz * dx;
-}
-__device__ __forceinline__ void put_child(WideBoxes& b, int e, const BvhNode& nd, bool right) {
-  if (!right) {
-    b.link[e] = nd.link.x;
-    b.lo[0][e] = nd.lxy.x; b.hi[0][e] = nd.lxy.y; b.lo[1][e] = nd.lxy.z; b.hi[1][e] = nd.lxy.w;
-    b.lo[2][e] = nd.z.x;   b.hi[2][e] = nd.z.y;
-  } else {
-    b.link[e] = nd.link.y;
-    b.lo[0][e] = nd.rxy.x; b.hi[0][e] = nd.rxy.y; b.lo[1][e] = nd.rxy.z; b.hi[1][e] = nd.rxy.w;
-    b.lo[2][e] = nd.z.z;   b.hi[2][e] = nd.z.w;
-  }
-}
-__device__ int expand_greedy(const BvhNode* nodes, uint32_t node, WideBoxes& b) {
-  for (int k = 0; k < kWide; ++k) {
-    b.link[k] = kNoHit;
-    for (int a = 0; a < 3; ++a) b.lo[a][k] = b.hi[a][k] = 0.0f;
-  }
-  const BvhNode nd = nodes[node];
-  put_child(b, 0, nd, false);
-  put_child(b, 1, nd, true);
-  int n = 2;
-  while (n < kWide) {
-    int best = -1;
-    float ba = -1.0f;
-    for (int e = 0; e < n; ++e)
-      if (!(b.link[e] & kLeafBit)) {
-        const float a = box_area(b, e);
-        if (a > ba) {
-          ba = a;
-          best = e;
-        }
-      }
-    if (best < 0) break;
-    const BvhNode cn = nodes[b.link[best]];
-    for (int e = n; e > best + 1; --e) {
-      b.link[e] = b.link[e - 1];
-      for (int a = 0; a < 3; ++a) {
-        b.lo[a][e] = b.lo[a][e - 1];
-        b.hi[a][e] = b.hi[a][e - 1];
-      }
-    }
-    put_child(b, best, cn, false);
-    put_child(b, best + 1, cn, true);
-    ++n;
-  }
-  return n;
-}
+// The wide node's child list (WideBoxes, expand_greedy: the greedy surface-area collapse) and its
+// quantisation (quantize_wide) are in lbvh_shared.h: a refit re-emits the nodes with the same code.
 // pass 1: internal children per wide node of this level (cur[j] = {BVH2 node, parent wide index})
 __global__ void k_wide_count(uint32_t ncur, const uint2* cur, const BvhNode* nodes, uint32_t* cnt) {
   for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < ncur; j += gridDim.x * blockDim.x) {
@@ -955,6 +848,12 @@ int build_lbvh(Context& c, const float* h_pos, uint32_t nverts, const uint32_t* 
   c.num_tris = ntris;
   c.num_sph = nsph;
   c.bvh_depth = 0;
+  // dynamic scenes (sptr_set_dynamic): what a refit needs is kept below; otherwise nothing of it is
+  c.rf.valid = c.rf.split = false;
+  c.rf.refits = 0;
+  c.rf.num_verts = nverts;
+  c.rf.max_h = 0;
+  if (!c.dynamic) refit_release(c, false);
   if (NP == 0) {
     c.num_nodes = 0;
     c.num_tri_refs = 0;
@@ -1010,6 +909,8 @@ int build_lbvh(Context& c, const float* h_pos, uint32_t nverts, const uint32_t* 
     return (c.err = "lbvh: too many primitive references (" + std::to_string(NR64) + ")", SPTR_ERR_INVALID);
   const uint32_t NR = (uint32_t)NR64;
   const uint32_t ntri_refs = NR - nsph;  // spheres keep one reference each
+  c.rf.split = NR != NP;
+  const bool retain = c.dynamic && !c.rf.split;  // split references are not refitted
   c.num_tri_refs = ntri_refs;
   c.num_nodes = NR > 1 ? NR - 1 : 0;
   // + 64 B: the unified wide walk (wide_walk_u) reads a node's 56 B from a direct leaf's primitive address
@@ -1145,6 +1046,42 @@ int build_lbvh(Context& c, const float* h_pos, uint32_t nverts, const uint32_t* 
         }
       }
     }
+    if (retain) {
+      // the final tree's nodes grouped by subtree height: the launch order of a refit's BVH2 pass
+      uint32_t *hlab = nullptr, *hhist = nullptr;
+      LB_CHECK(tmp.alloc(&hlab, N));
+      LB_CHECK(tmp.alloc(&hhist, (size_t)kMaxHeight * kHeightBlocks));
+      LB_CHECK(hipMemsetAsync(rflags, 0, (size_t)N * 4, s));
+      hipLaunchKernelGGL(k_heights, dim3(blocks_for(N)), dim3(256), 0, s, (int)N, leaf_parent, nodes, rflags, hlab);
+      const uint32_t nn = N - 1u, per = (nn + kHeightBlocks - 1u) / kHeightBlocks;
+      std::vector<uint32_t> bh((size_t)kMaxHeight * kHeightBlocks);
+      hipLaunchKernelGGL(k_height_count, dim3(kHeightBlocks), dim3(256), 0, s, nn, per, hlab, hhist);
+      LB_CHECK(hipGetLastError());
+      LB_CHECK(hipMemcpyAsync(bh.data(), hhist, bh.size() * 4, hipMemcpyDeviceToHost, s));
+      LB_CHECK(hipStreamSynchronize(s));
+      std::vector<uint32_t>& ho = c.rf.hoff_h;
+      ho.assign(kMaxHeight + 1u, 0u);
+      uint32_t run = 0u, max_h = 0u;
+      for (uint32_t h = 0; h < kMaxHeight; ++h) {
+        ho[h] = run;
+        for (uint32_t b = 0; b < kHeightBlocks; ++b) {
+          const uint32_t n = bh[(size_t)h * kHeightBlocks + b];
+          bh[(size_t)h * kHeightBlocks + b] = run;
+          run += n;
+        }
+        if (run > ho[h]) max_h = h;
+      }
+      ho[kMaxHeight] = run;
+      c.rf.max_h = max_h;
+      LB_CHECK(realloc_buf(c.rf.order, (size_t)nn * 4));
+      LB_CHECK(realloc_buf(c.rf.hoff, ho.size() * 4));
+      LB_CHECK(hipMemcpyAsync(hhist, bh.data(), bh.size() * 4, hipMemcpyHostToDevice, s));
+      LB_CHECK(hipMemcpyAsync(c.rf.hoff.p, ho.data(), ho.size() * 4, hipMemcpyHostToDevice, s));
+      hipLaunchKernelGGL(k_height_scatter, dim3(kHeightBlocks), dim3(256), 0, s, nn, per, hlab, hhist,
+                         static_cast<uint32_t*>(c.rf.order.p));
+      LB_CHECK(hipGetLastError());
+      LB_CHECK(hipStreamSynchronize(s));  // bh is read by the copy above
+    }
     c.root = N <= leaf_max ? (kLeafBit | (N - 1u)) : 0u;  // whole scene in one leaf range, or node 0
     c.bvh_depth = dep;
     // a BVH2 node at depth d holds at most d pushed entries and pushes one more; a wide node (BVH2
@@ -1173,6 +1110,7 @@ int build_lbvh(Context& c, const float* h_pos, uint32_t nverts, const uint32_t* 
       void* stw = nullptr;
       LB_CHECK(tmp.alloc(reinterpret_cast<char**>(&stw), sw));
       LB_CHECK(realloc_buf(c.nodes4, (size_t)(N - 1) * sizeof(WideNode)));  // <= one wide node per BVH2 node
+      if (retain) LB_CHECK(realloc_buf(c.rf.wsrc, (size_t)(N - 1) * kWide * 4));
       const uint2 root2 = make_uint2(0u, kNoHit);
       LB_CHECK(hipMemcpyAsync(cur, &root2, sizeof(root2), hipMemcpyHostToDevice, s));
       uint32_t ncur = 1u, base = 0u, levels = 0u;
@@ -1183,6 +1121,7 @@ int build_lbvh(Context& c, const float* h_pos, uint32_t nverts, const uint32_t* 
         LB_CHECK(scan_u32(stw, sw, flag, off, ncur, s));
         hipLaunchKernelGGL(k_wide_emit, dim3(blocks_for(ncur)), dim3(256), 0, s, ncur, cur, base, nodes, off, nxt,
                            static_cast<WideNode*>(c.nodes4.p), static_cast<const uint32_t*>(c.prim_ref.p));
+        if (retain) launch_wide_sources(ncur, cur, base, nodes, static_cast<uint32_t*>(c.rf.wsrc.p), s);
         LB_CHECK(hipGetLastError());
         uint32_t last[2] = {0u, 0u};  // cnt, off of the level's last node
         LB_CHECK(hipMemcpyAsync(&last[0], flag + (ncur - 1u), 4, hipMemcpyDeviceToHost, s));
@@ -1200,6 +1139,11 @@ int build_lbvh(Context& c, const float* h_pos, uint32_t nverts, const uint32_t* 
       c.stack_need4 = (uint32_t)(kWide - 1) * levels;
       c.root4 = 0u;  // node 0 (depth 0) is kept and scans to index 0
     }
+  }
+  if (retain) {
+    const int rr = refit_retain_slots(c, d_pos, d_idx, d_sph);
+    if (rr != SPTR_OK) return rr;
+    c.rf.valid = true;
   }
   LB_CHECK(hipStreamSynchronize(s));
   c.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();

@@ -1,0 +1,283 @@
+// kernels_refit.hip — in-place refit of an uploaded scene whose coordinates moved
+// (sptr_update_geometry, DESIGN.md "Dynamic scenes").  The tree topology, the slot order and every link
+// stay the upload's; three passes recompute what depends on coordinates:
+//   k_refit_slots : one thread per sorted position: the triangle record (tri_record, the function
+//                   k_leaves calls) through the slot-order index triples, or the sphere, written in
+//                   place, and the position's box
+//   k_refit_nodes : BVH2 child boxes, one launch per subtree height (ascending): a child box is the
+//                   union of a leaf range's position boxes, or of the child node's two boxes, which an
+//                   earlier launch finished.  k_refit_nodes_block: the same for trees of at most
+//                   kRefitBlockNodes nodes (the scenes staged in LDS), one block walking the heights
+//                   with __syncthreads() between them
+//   k_refit_wide  : every wide node re-quantised (quantize_wide, the function k_wide_emit calls) from
+//                   the BVH2 boxes its children were collapsed from (the source table k_wide_sources
+//                   wrote at upload)
+// No kernel here waits for, or hands data to, another workgroup of its launch: kernel boundaries and
+// __syncthreads() are the only synchronisation.  fminf / fmaxf are exact, so a box does not depend on
+// the order its parts are merged in (the build's k_refit merges in tree order), up to the sign of a zero.
+#include <hip/hip_runtime.h>
+
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+
+#include "lbvh_shared.h"
+#include "sptr_internal.h"
+
+namespace sptr {
+
+namespace {
+
+#define RF_CHECK(x)                                                    \
+  do {                                                                 \
+    hipError_t e_ = (x);                                               \
+    if (e_ != hipSuccess) {                                            \
+      c.err = std::string("refit: ") + #x + ": " + hipGetErrorString(e_); \
+      return SPTR_ERR_HIP;                                             \
+    }                                                                  \
+  } while (0)
+
+constexpr uint32_t kRefitBlockNodes = 1024;  // trees up to this many nodes: one block walks the heights
+
+struct SlotIn {
+  const float* pos;          // vertex positions, or null: triangles keep their records and boxes
+  const float4* sph_in;      // spheres in upload order, or null: spheres keep theirs
+  const uint32_t* idx;       // 3 vertex indices per triangle slot
+  const uint32_t* sph_orig;  // sphere slot -> index in the upload
+  const uint32_t* prim_ref;  // sorted position -> [kSphereBit] | slot
+  uint32_t n;                // sorted positions
+};
+
+__global__ void __launch_bounds__(256) k_refit_slots(SlotIn in, float4* tris, float4* sph, float4* box_lo, float4* box_hi) {
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < in.n; i += gridDim.x * blockDim.x) {
+    const uint32_t ref = in.prim_ref[i], slot = ref & kIndexMask;
+    vec3 lo, hi;
+    if (ref & kSphereBit) {
+      if (!in.sph_in) continue;
+      const float4 s = in.sph_in[in.sph_orig[slot]];
+      sph[slot] = s;
+      sphere_box(s, lo, hi);
+    } else {
+      if (!in.pos) continue;
+      const uint32_t a = in.idx[3 * slot], b = in.idx[3 * slot + 1], c = in.idx[3 * slot + 2];
+      const vec3 v0 = v3(in.pos[3 * a], in.pos[3 * a + 1], in.pos[3 * a + 2]);
+      const vec3 v1 = v3(in.pos[3 * b], in.pos[3 * b + 1], in.pos[3 * b + 2]);
+      const vec3 v2 = v3(in.pos[3 * c], in.pos[3 * c + 1], in.pos[3 * c + 2]);
+      float4 rec[3];
+      tri_record(v0, v1, v2, rec);
+      tris[3 * slot + 0] = rec[0];
+      tris[3 * slot + 1] = rec[1];
+      tris[3 * slot + 2] = rec[2];
+      tri_box(v0, v1, v2, lo, hi);
+    }
+    box_lo[i] = make_float4(lo.x, lo.y, lo.z, 0.0f);
+    box_hi[i] = make_float4(hi.x, hi.y, hi.z, 0.0f);
+  }
+}
+
+// idx_out[3 * slot ..] = the uploaded triple of the slot's triangle
+__global__ void k_slot_indices(uint32_t nslots, const uint32_t* tri_orig, const uint32_t* idx, uint32_t* idx_out) {
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < nslots; i += gridDim.x * blockDim.x) {
+    const uint32_t p = tri_orig[i];
+    idx_out[3 * i] = idx[3 * p];
+    idx_out[3 * i + 1] = idx[3 * p + 1];
+    idx_out[3 * i + 2] = idx[3 * p + 2];
+  }
+}
+
+struct Box6 {
+  float lo[3], hi[3];
+};
+// the box of a BVH2 child link: a leaf range of sorted positions, or a node of a smaller height
+__device__ __forceinline__ Box6 child_box(uint32_t link, const BvhNode* nodes, const float4* box_lo, const float4* box_hi) {
+  Box6 b;
+  if (link & kLeafBit) {
+    const uint32_t start = (link & ~kLeafBit) >> kLeafCountBits, cnt = (link & kLeafRangeMask) + 1u;
+    const float4 l0 = box_lo[start], h0 = box_hi[start];
+    b.lo[0] = l0.x; b.lo[1] = l0.y; b.lo[2] = l0.z;
+    b.hi[0] = h0.x; b.hi[1] = h0.y; b.hi[2] = h0.z;
+    for (uint32_t k = 1; k < cnt; ++k) {
+      const float4 l = box_lo[start + k], h = box_hi[start + k];
+      b.lo[0] = fminf(b.lo[0], l.x); b.lo[1] = fminf(b.lo[1], l.y); b.lo[2] = fminf(b.lo[2], l.z);
+      b.hi[0] = fmaxf(b.hi[0], h.x); b.hi[1] = fmaxf(b.hi[1], h.y); b.hi[2] = fmaxf(b.hi[2], h.z);
+    }
+  } else {
+    const BvhNode* cn = nodes + link;
+    const float4 l = cn->lxy, r = cn->rxy, z = cn->z;
+    b.lo[0] = fminf(l.x, r.x); b.hi[0] = fmaxf(l.y, r.y);
+    b.lo[1] = fminf(l.z, r.z); b.hi[1] = fmaxf(l.w, r.w);
+    b.lo[2] = fminf(z.x, z.z); b.hi[2] = fmaxf(z.y, z.w);
+  }
+  return b;
+}
+__device__ __forceinline__ void refit_node(uint32_t x, BvhNode* nodes, const float4* box_lo, const float4* box_hi) {
+  const uint4 link = nodes[x].link;
+  const Box6 l = child_box(link.x, nodes, box_lo, box_hi), r = child_box(link.y, nodes, box_lo, box_hi);
+  nodes[x].lxy = make_float4(l.lo[0], l.hi[0], l.lo[1], l.hi[1]);
+  nodes[x].rxy = make_float4(r.lo[0], r.hi[0], r.lo[1], r.hi[1]);
+  nodes[x].z = make_float4(l.lo[2], l.hi[2], r.lo[2], r.hi[2]);
+}
+
+// the nodes of one height: order[0 .. count)
+__global__ void __launch_bounds__(256) k_refit_nodes(const uint32_t* order, uint32_t count, BvhNode* nodes, const float4* box_lo,
+                                                     const float4* box_hi) {
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x)
+    refit_node(order[i], nodes, box_lo, box_hi);
+}
+// one block, every height: nodes of height h are order[hoff[h] .. hoff[h + 1]); the barrier (with its
+// workgroup-scope fence) makes height h's boxes visible to the threads that read them for height h + 1
+__global__ void __launch_bounds__(256) k_refit_nodes_block(const uint32_t* order, const uint32_t* hoff, uint32_t max_h,
+                                                           BvhNode* nodes, const float4* box_lo, const float4* box_hi) {
+  for (uint32_t h = 1; h <= max_h; ++h) {
+    const uint32_t lo = hoff[h], hi = hoff[h + 1];
+    for (uint32_t i = lo + threadIdx.x; i < hi; i += blockDim.x) refit_node(order[i], nodes, box_lo, box_hi);
+    __syncthreads();
+  }
+}
+
+// wide node base + j of one level: where each of its child boxes is read from
+__global__ void k_wide_sources(uint32_t ncur, const uint2* cur, uint32_t base, const BvhNode* nodes, uint32_t* wsrc) {
+  for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < ncur; j += gridDim.x * blockDim.x) {
+    WideBoxes b;
+    uint32_t src[kWide];
+    (void)expand_greedy_t<true>(nodes, cur[j].x, b, src);
+    for (int e = 0; e < kWide; ++e) wsrc[(size_t)(base + j) * kWide + e] = src[e];
+  }
+}
+
+__global__ void __launch_bounds__(256) k_refit_wide(uint32_t nw, WideNode* nodes4, const uint32_t* wsrc, const BvhNode* nodes) {
+  for (uint32_t w = blockIdx.x * blockDim.x + threadIdx.x; w < nw; w += gridDim.x * blockDim.x) {
+    const WideNode old = nodes4[w];
+    const int n = (int)(old.ex >> 24);
+    WideBoxes b;
+    for (int e = 0; e < kWide; ++e) {
+      b.link[e] = old.link[e];
+      for (int a = 0; a < 3; ++a) b.lo[a][e] = b.hi[a][e] = 0.0f;
+      const uint32_t s = wsrc[(size_t)w * kWide + e];
+      if (e >= n || s == kNoHit) continue;
+      const BvhNode* nd = nodes + (s >> 1);
+      const float4 xy = (s & 1u) ? nd->rxy : nd->lxy, z = nd->z;
+      b.lo[0][e] = xy.x; b.hi[0][e] = xy.y; b.lo[1][e] = xy.z; b.hi[1][e] = xy.w;
+      b.lo[2][e] = (s & 1u) ? z.z : z.x;
+      b.hi[2][e] = (s & 1u) ? z.w : z.y;
+    }
+    // the child count as a constant: quantize_wide's loops unroll and the child arrays stay in registers
+    // (with a variable count they live in scratch); the same function either way, so the same bits
+    WideNode o;
+    if (n == 2) o = quantize_wide(b, 2, old.parent);
+    else if (n == 3) o = quantize_wide(b, 3, old.parent);
+    else o = quantize_wide(b, kWide, old.parent);
+    nodes4[w] = o;
+  }
+}
+
+hipError_t rf_buf(DevBuf& b, size_t bytes) {
+  if (b.p && b.bytes >= bytes) return hipSuccess;
+  if (b.p) (void)hipFree(b.p);
+  b.p = nullptr;
+  b.bytes = 0;
+  hipError_t e = hipMalloc(&b.p, bytes ? bytes : 16);
+  if (e == hipSuccess) b.bytes = bytes ? bytes : 16;
+  return e;
+}
+
+unsigned blocks_for(size_t n) {
+  size_t b = (n + 255) / 256;
+  if (b < 1) b = 1;
+  if (b > 4096) b = 4096;
+  return (unsigned)b;
+}
+
+void launch_slots(Context& c, const float* d_pos, const float4* d_sph) {
+  const uint32_t n = c.num_tri_refs + c.num_sph;
+  SlotIn in{d_pos, d_sph, static_cast<const uint32_t*>(c.rf.idx.p), static_cast<const uint32_t*>(c.sph_orig.p),
+            static_cast<const uint32_t*>(c.prim_ref.p), n};
+  hipLaunchKernelGGL(k_refit_slots, dim3(blocks_for(n)), dim3(256), 0, c.stream, in, static_cast<float4*>(c.tris.p),
+                     static_cast<float4*>(c.sph.p), static_cast<float4*>(c.rf.box_lo.p), static_cast<float4*>(c.rf.box_hi.p));
+}
+
+}  // namespace
+
+void refit_release(Context& c, bool events) {
+  RefitState& r = c.rf;
+  for (DevBuf* b : {&r.idx, &r.box_lo, &r.box_hi, &r.order, &r.hoff, &r.wsrc, &r.in_pos, &r.in_sph}) {
+    if (b->p) (void)hipFree(b->p);
+    b->p = nullptr;
+    b->bytes = 0;
+  }
+  r.hoff_h.clear();
+  r.valid = false;
+  if (events)
+    for (hipEvent_t& e : r.ev) {
+      if (e) (void)hipEventDestroy(e);
+      e = nullptr;
+    }
+}
+
+int refit_retain_slots(Context& c, const float* d_pos, const uint32_t* d_idx, const float4* d_sph) {
+  const uint32_t n = c.num_tri_refs + c.num_sph;
+  RF_CHECK(rf_buf(c.rf.idx, (size_t)c.num_tri_refs * 12));
+  RF_CHECK(rf_buf(c.rf.box_lo, (size_t)n * 16));
+  RF_CHECK(rf_buf(c.rf.box_hi, (size_t)n * 16));
+  if (c.num_tri_refs)
+    hipLaunchKernelGGL(k_slot_indices, dim3(blocks_for(c.num_tri_refs)), dim3(256), 0, c.stream, c.num_tri_refs,
+                       static_cast<const uint32_t*>(c.tri_orig.p), d_idx, static_cast<uint32_t*>(c.rf.idx.p));
+  // the first boxes (and, bit for bit, the records k_leaves just wrote): a later update of the positions
+  // or of the spheres alone finds the other kind's boxes here
+  launch_slots(c, c.num_tri_refs ? d_pos : nullptr, c.num_sph ? d_sph : nullptr);
+  RF_CHECK(hipGetLastError());
+  return SPTR_OK;
+}
+
+void launch_wide_sources(uint32_t ncur, const uint2* cur, uint32_t base, const BvhNode* nodes, uint32_t* wsrc, hipStream_t s) {
+  hipLaunchKernelGGL(k_wide_sources, dim3(blocks_for(ncur)), dim3(256), 0, s, ncur, cur, base, nodes, wsrc);
+}
+
+int refit_lbvh(Context& c, const float* d_pos, const float4* d_sph) {
+  const auto t0 = std::chrono::steady_clock::now();
+  RefitState& r = c.rf;
+  hipStream_t s = c.stream;
+  for (hipEvent_t& e : r.ev)
+    if (!e) RF_CHECK(hipEventCreate(&e));
+  BvhNode* nodes = static_cast<BvhNode*>(c.nodes.p);
+  const float4 *blo = static_cast<const float4*>(r.box_lo.p), *bhi = static_cast<const float4*>(r.box_hi.p);
+  RF_CHECK(hipEventRecord(r.ev[0], s));
+  if (c.num_tri_refs + c.num_sph) launch_slots(c, c.num_tri_refs ? d_pos : nullptr, c.num_sph ? d_sph : nullptr);
+  RF_CHECK(hipEventRecord(r.ev[1], s));
+  if (c.num_nodes) {
+    const uint32_t* order = static_cast<const uint32_t*>(r.order.p);
+    if (c.num_nodes <= kRefitBlockNodes) {
+      hipLaunchKernelGGL(k_refit_nodes_block, dim3(1), dim3(256), 0, s, order, static_cast<const uint32_t*>(r.hoff.p), r.max_h,
+                         nodes, blo, bhi);
+    } else {
+      for (uint32_t h = 1; h <= r.max_h; ++h) {
+        const uint32_t lo = r.hoff_h[h], cnt = r.hoff_h[h + 1] - lo;
+        if (cnt) hipLaunchKernelGGL(k_refit_nodes, dim3(blocks_for(cnt)), dim3(256), 0, s, order + lo, cnt, nodes, blo, bhi);
+      }
+    }
+  }
+  RF_CHECK(hipEventRecord(r.ev[2], s));
+  if (c.num_nodes4)
+    hipLaunchKernelGGL(k_refit_wide, dim3(blocks_for(c.num_nodes4)), dim3(256), 0, s, c.num_nodes4,
+                       static_cast<WideNode*>(c.nodes4.p), static_cast<const uint32_t*>(r.wsrc.p), nodes);
+  RF_CHECK(hipGetLastError());
+  RF_CHECK(hipEventRecord(r.ev[3], s));
+  RF_CHECK(hipStreamSynchronize(s));
+  float ms = 0.0f;
+  for (int k = 0; k < 3; ++k) {
+    RF_CHECK(hipEventElapsedTime(&ms, r.ev[k], r.ev[k + 1]));
+    r.ms_stage[k] = ms;
+  }
+  RF_CHECK(hipEventElapsedTime(&ms, r.ev[0], r.ev[3]));
+  r.ms_device = ms;
+  ++r.refits;
+  r.ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  // SPTR_REFIT_STAGES=1: the device ms of the three passes, for the measurements of DESIGN.md
+  static const bool print = std::getenv("SPTR_REFIT_STAGES") != nullptr;
+  if (print)
+    std::fprintf(stderr, "refit %u: slots %.4f ms, bvh2 %.4f ms (%u heights), wide %.4f ms, wall %.4f ms\n", r.refits,
+                 r.ms_stage[0], r.ms_stage[1], r.max_h, r.ms_stage[2], r.ms_wall);
+  return SPTR_OK;
+}
+
+}  // namespace sptr

@@ -1446,6 +1446,7 @@ int sptr_destroy(sptr_ctx* x) {
     if (st) (void)hipStreamDestroy(st);
   drop_graph(c);
   free_buf(c.dyn);
+  refit_release(c, true);
   for (hipEvent_t e : c.events) (void)hipEventDestroy(e);
   if (c.stream) (void)hipStreamDestroy(c.stream);
   if (c.cap_stream) (void)hipStreamDestroy(c.cap_stream);
@@ -2178,6 +2179,73 @@ int sptr_upload_scene(sptr_ctx* x, const sptr_scene* s) {
     if (r1 != SPTR_OK) return lane_forward(x, r1);
     x->lane_scene = true;
   }
+  return SPTR_OK;
+}
+
+// ---- dynamic scenes ----------------------------------------------------------------------------
+int sptr_set_dynamic(sptr_ctx* x, uint32_t on) {
+  if (!x) return SPTR_ERR_INVALID;
+  x->c.dynamic = on != 0u;  // read by the next upload (build_lbvh)
+  if (x->lane) x->lane->c.dynamic = x->c.dynamic;
+  return SPTR_OK;
+}
+
+// c's scene refitted from device coordinates (either may be null)
+static int refit_one(Context& c, const float* d_pos, const float* d_sph) {
+  if (sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;  // a pending render may still read the old boxes
+  const int rc = refit_lbvh(c, d_pos, reinterpret_cast<const float4*>(d_sph));
+  ++c.epoch;  // cull mask, AOV planes and captured graphs were computed for the old coordinates
+  return rc;
+}
+
+int sptr_update_geometry(sptr_ctx* x, const float* positions, uint32_t num_verts, const float* spheres,
+                         uint32_t num_spheres, uint32_t flags) {
+  if (!x) return SPTR_ERR_INVALID;
+  Context& c = x->c;
+  if (x->is_lane) return fail(c, SPTR_ERR_INVALID, "update_geometry: not on a lane context");
+  if (!c.have_scene) return fail(c, SPTR_ERR_NO_SCENE, "update_geometry: no scene uploaded");
+  if (c.rf.split)
+    return fail(c, SPTR_ERR_INVALID, "update_geometry: the scene was built with split references (sptr_set_split_refs)");
+  if (!c.rf.valid) return fail(c, SPTR_ERR_INVALID, "update_geometry: the scene was not uploaded with sptr_set_dynamic(1)");
+  if (!positions && !spheres) return fail(c, SPTR_ERR_INVALID, "update_geometry: no coordinates given");
+  if ((positions && num_verts != c.rf.num_verts) || (spheres && num_spheres != c.num_sph))
+    return fail(c, SPTR_ERR_INVALID, "update_geometry: counts differ from the uploaded scene's");
+  if (flags & ~(uint32_t)SPTR_UPDATE_DEVICE_PTRS) return fail(c, SPTR_ERR_INVALID, "update_geometry: unknown flags");
+  const auto t0 = std::chrono::steady_clock::now();
+  API_HIP(hipSetDevice(c.device));
+  if (sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;
+  const float *d_pos = positions, *d_sph = spheres;
+  if (!(flags & SPTR_UPDATE_DEVICE_PTRS)) {
+    if (positions) {
+      API_HIP(ensure_buf(c.rf.in_pos, (size_t)num_verts * 12));
+      API_HIP(hipMemcpyAsync(c.rf.in_pos.p, positions, (size_t)num_verts * 12, hipMemcpyHostToDevice, c.stream));
+      d_pos = static_cast<const float*>(c.rf.in_pos.p);
+    }
+    if (spheres) {
+      API_HIP(ensure_buf(c.rf.in_sph, (size_t)num_spheres * 16));
+      API_HIP(hipMemcpyAsync(c.rf.in_sph.p, spheres, (size_t)num_spheres * 16, hipMemcpyHostToDevice, c.stream));
+      d_sph = static_cast<const float*>(c.rf.in_sph.p);
+    }
+  }
+  const int rc = refit_one(c, d_pos, d_sph);  // (returns after c.stream drained: the staging is stable)
+  if (rc != SPTR_OK) return rc;
+  if (x->lane && x->lane_scene) {  // the lane's copy of the scene, on the lane's stream
+    Context& cy = x->lane->c;
+    if (!cy.rf.valid) return fail(c, SPTR_ERR_INVALID, "update_geometry: the pixel lane's scene is not dynamic");
+    const int r1 = refit_one(cy, d_pos, d_sph);
+    if (r1 != SPTR_OK) return lane_forward(x, r1);
+  }
+  c.rf.ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return SPTR_OK;
+}
+
+int sptr_refit_info(const sptr_ctx* x, uint32_t* refits, double* ms_wall, double* ms_device, uint32_t* excluded_prims) {
+  if (!x) return SPTR_ERR_INVALID;
+  const Context& c = x->c;
+  if (refits) *refits = c.rf.refits;
+  if (ms_wall) *ms_wall = c.rf.ms_wall;
+  if (ms_device) *ms_device = c.rf.ms_device;
+  if (excluded_prims) *excluded_prims = c.excluded_prims;
   return SPTR_OK;
 }
 

@@ -373,6 +373,26 @@ struct GraphCache {
   uint32_t nodes = 0, edges = 0, depth = 0;
 };
 
+// What a dynamic upload (sptr_set_dynamic) keeps beside the scene for sptr_update_geometry's refit
+// (kernels_refit.hip, DESIGN.md "Dynamic scenes").  Sorted position i is the i-th primitive reference
+// in tree order (prim_ref[i] names its slot); the tree covers positions 0..num_nodes.
+struct RefitState {
+  bool valid = false;      // the current scene can be refitted
+  bool split = false;      // ... it cannot: it was built with split references
+  uint32_t num_verts = 0;  // of the upload
+  DevBuf idx;              // 3 vertex indices per triangle slot (the uploaded triples in slot order)
+  DevBuf box_lo, box_hi;   // float4 per sorted position: its primitive's box (a leaf range's boxes are merged from these)
+  DevBuf order;            // BVH2 nodes grouped by subtree height, heights ascending
+  DevBuf hoff;             // device copy of hoff_h
+  std::vector<uint32_t> hoff_h;  // [max_h + 2]: nodes of height h are order[hoff_h[h] .. hoff_h[h + 1]); height 0: none
+  uint32_t max_h = 0;      // the root's height
+  DevBuf wsrc;             // kWide words per wide node: (BVH2 node << 1 | side) each child box is read from, or kNoHit
+  DevBuf in_pos, in_sph;   // device staging of host-pointer updates
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // begin, after the slot pass, after the BVH2 pass, end
+  uint32_t refits = 0;     // since the upload
+  double ms_wall = 0.0, ms_device = 0.0, ms_stage[3] = {0.0, 0.0, 0.0};  // of the last refit
+};
+
 struct Context {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -438,6 +458,8 @@ struct Context {
   std::vector<uint32_t> geom_material;  // host copy
   bool have_scene = false;
   double build_ms = 0.0;
+  bool dynamic = false;  // sptr_set_dynamic: the next upload keeps RefitState
+  RefitState rf;
   // shading state
   std::vector<DevMaterial> mats_host;
   DevBuf mats;
@@ -473,6 +495,15 @@ struct Context {
 // kernels_lbvh.hip
 int build_lbvh(Context& c, const float* h_pos, uint32_t nverts, const uint32_t* h_idx, uint32_t ntris,
                const float* h_sph, uint32_t nsph, const uint32_t* h_tri_geom, uint32_t sph_geom_base);
+
+// kernels_refit.hip.  The upload's part (dynamic scenes only): the slot-order index triples and the
+// first slot boxes; the source table of one wide level (cur[j].x = BVH2 node of wide node base + j).
+// refit_lbvh: new device coordinates (either may be null: unchanged) -> triangle records, spheres and
+// every BVH2 and wide box in place, on c.stream; returns when done.
+int refit_retain_slots(Context& c, const float* d_pos, const uint32_t* d_idx, const float4* d_sph);
+void launch_wide_sources(uint32_t ncur, const uint2* cur, uint32_t base, const BvhNode* nodes, uint32_t* wsrc, hipStream_t s);
+int refit_lbvh(Context& c, const float* d_pos, const float4* d_sph);
+void refit_release(Context& c, bool events);
 
 // kernels_sort.hip: the build's device primitives (temp == nullptr: set temp_bytes only)
 hipError_t scan_u32(void* temp, size_t& temp_bytes, const uint32_t* in, uint32_t* out, uint32_t n, hipStream_t s);

@@ -39,17 +39,46 @@ void HipBackend::setDebugMode(int mode) {
 
 bool HipBackend::build(const scene::SceneDesc& sd) {
   if (!ensureContext()) return false;
-  const scene::FlatScene flat = scene::Flatten(sd);
+  return buildFlat(scene::Flatten(sd));
+}
+
+bool HipBackend::buildFlat(const scene::FlatScene& flat) {
   const sptr_scene v = flat.view();
+  built_ = false;
+  if (sptr_set_dynamic(ctx_, settings_.dynamic ? 1u : 0u) != SPTR_OK) return false;
   const int rc = sptr_upload_scene(ctx_, &v);
   if (rc != SPTR_OK) {
     err_ = std::string("HipBackend::build: ") + sptr_last_error(ctx_);
     return false;
   }
   geom_material_ = flat.geom_material;
+  built_indices_ = flat.indices;
+  built_geom_first_ = flat.tri_geom_first;
+  built_verts_ = flat.positions.size() / 3;
+  built_spheres_ = flat.spheres.size() / 4;
+  built_dynamic_ = settings_.dynamic;
   built_ = true;
   frame_index_ = 0;
   return true;
+}
+
+bool HipBackend::update(const scene::SceneDesc& sd) {
+  if (!ensureContext()) return false;
+  const scene::FlatScene flat = scene::Flatten(sd);
+  const bool same = built_ && built_dynamic_ && flat.positions.size() / 3 == built_verts_ &&
+                    flat.spheres.size() / 4 == built_spheres_ && flat.indices == built_indices_ &&
+                    flat.tri_geom_first == built_geom_first_ && flat.geom_material == geom_material_ &&
+                    (built_verts_ || built_spheres_);
+  if (same) {
+    const int rc = sptr_update_geometry(ctx_, built_verts_ ? flat.positions.data() : nullptr, uint32_t(built_verts_),
+                                        built_spheres_ ? flat.spheres.data() : nullptr, uint32_t(built_spheres_), 0u);
+    if (rc == SPTR_OK) {
+      frame_index_ = 0;
+      return true;
+    }
+    // (a scene built with split references cannot be refitted: built again below)
+  }
+  return buildFlat(flat);
 }
 
 bool HipBackend::syncState() {

@@ -40,6 +40,9 @@ class HipBackend {
     // the edge-avoiding a-trous denoiser (wavefront integrator only; with lagged_readback, the denoised
     // previous frame).  Zero sigmas / power take the defaults.  A change does not restart the accumulation.
     sptr_denoise_params denoise{};
+    // sptr_set_dynamic, applied before build(): the build keeps what update() needs to refit the BVH in
+    // place when only coordinates change
+    bool dynamic = false;
   };
   static constexpr uint32_t kLaggedCollect = 32;
 
@@ -49,6 +52,20 @@ class HipBackend {
   HipBackend& operator=(const HipBackend&) = delete;
 
   bool build(const scene::SceneDesc& sceneDesc);
+  // The scene after a change: flattens as build() does; when the counts, the indices, the geometry order
+  // and the material map equal the built scene's (and Settings::dynamic was set for that build), the new
+  // coordinates are refitted in place (sptr_update_geometry), otherwise the scene is built again.  Either
+  // way the accumulation restarts.
+  bool update(const scene::SceneDesc& sceneDesc);
+  // sptr_refit_info: refits since the last build, wall / device ms of the last one, excluded primitives
+  bool refitInfo(uint32_t* refits, double* ms_wall, double* ms_device, uint32_t* excluded_prims) const {
+    return ctx_ && sptr_refit_info(ctx_, refits, ms_wall, ms_device, excluded_prims) == SPTR_OK;
+  }
+  // sptr_scene_info's build_ms of the last build
+  double buildMs() const {
+    double ms = 0.0;
+    return ctx_ && sptr_scene_info(ctx_, nullptr, nullptr, nullptr, &ms) == SPTR_OK ? ms : 0.0;
+  }
   void render(unsigned char* pixels, int width, int height, const Camera& camera);
   void setEnvironment(const EnvironmentManager* env) { env_ = env; env_dirty_ = true; }
   void setMaterialManager(const MaterialManager* mm) { mm_ = mm; mats_dirty_ = true; }
@@ -74,6 +91,7 @@ class HipBackend {
 
  private:
   bool ensureContext();
+  bool buildFlat(const scene::FlatScene& flat);
   bool syncState();
   bool renderInternal(int width, int height, const Camera& camera, bool async = false);
   void addStats(const sptr_stats& s);
@@ -91,6 +109,10 @@ class HipBackend {
   bool has_last_camera_ = false;
   std::array<float, 9> last_cam_{};
   std::vector<uint32_t> geom_material_;
+  // the built scene's topology (update() compares against it) and whether it was built dynamic
+  std::vector<uint32_t> built_indices_, built_geom_first_;
+  size_t built_verts_ = 0, built_spheres_ = 0;
+  bool built_dynamic_ = false;
   std::string err_;
   int debug_mode_ = 0;
   uint32_t lanes_applied_ = 0;  // the pixel-lane setting the context holds

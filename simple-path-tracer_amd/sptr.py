@@ -26,6 +26,7 @@ SPTR_FRAME_ASYNC = 8
 SPTR_FRAME_TIMING_TRACE = 16
 SPTR_FRAME_NO_CULL = 32
 SPTR_FRAME_RECULL = 64
+SPTR_UPDATE_DEVICE_PTRS = 1
 
 SPTR_INTEGRATOR_WAVEFRONT = 0   # WavefrontPathTracerCPU semantics (default)
 SPTR_INTEGRATOR_PATHTRACER = 1  # PathTracer (the reference's default CPU integrator) semantics
@@ -125,6 +126,7 @@ EXPORTS = [
     "sptr_tiles_device", "sptr_unpack_tiles", "sptr_intersect", "sptr_occluded", "sptr_primary_rays",
     "sptr_sort_pairs_u64", "sptr_scan_u32", "sptr_eval_math",
     "sptr_set_denoise", "sptr_read_aov", "sptr_read_denoised", "sptr_denoise_info",
+    "sptr_set_dynamic", "sptr_update_geometry", "sptr_refit_info",
     "sptr_host_builtin_scene", "sptr_host_scene_view", "sptr_host_scene_free", "sptr_host_camera_lookat",
     "sptr_host_preset_materials", "sptr_host_default_lights", "sptr_host_equirect_to_faces",
     "sptr_host_pack_tiles", "sptr_host_unpack_tiles", "sptr_host_load_hdr", "sptr_host_free",
@@ -182,6 +184,9 @@ def lib() -> C.CDLL:
         "sptr_read_aov": (C.c_int, [vp, C.c_int, vp]),
         "sptr_read_denoised": (C.c_int, [vp, fp]),
         "sptr_denoise_info": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), up]),
+        "sptr_set_dynamic": (C.c_int, [vp, u32]),
+        "sptr_update_geometry": (C.c_int, [vp, vp, u32, vp, u32, u32]),
+        "sptr_refit_info": (C.c_int, [vp, up, C.POINTER(C.c_double), C.POINTER(C.c_double), up]),
         "sptr_host_builtin_scene": (C.c_int, [C.c_char_p, u32, u32, C.POINTER(vp)]),
         "sptr_host_scene_view": (C.c_int, [vp, C.POINTER(Scene)]),
         "sptr_host_scene_free": (None, [vp]),
@@ -393,6 +398,38 @@ class Renderer:
     def upload_scene(self, s: FlatScene):
         cs = s.to_c()
         self._check(self._L.sptr_upload_scene(self._h, C.byref(cs)), "upload_scene")
+
+    def set_dynamic(self, on: bool = True):
+        """sptr_set_dynamic: the next upload_scene keeps what update_geometry's refit needs."""
+        self._check(self._L.sptr_set_dynamic(self._h, 1 if on else 0), "set_dynamic")
+
+    def update_geometry(self, positions=None, spheres=None, device: bool = False):
+        """sptr_update_geometry: new coordinates for the uploaded topology, refitted in place.  positions
+        (V, 3) and spheres (S, 4) float32, or None for unchanged; with device=True they are contiguous
+        float32 tensors on this context's GPU (anything with data_ptr() and numel()).  Restart the
+        accumulation (frame_begin=1) afterwards."""
+        ptr, cnt, keep = [None, None], [0, 0], []
+        for k, (a, cols) in enumerate(((positions, 3), (spheres, 4))):
+            if a is None:
+                continue
+            if device:
+                if a.numel() % cols or not a.is_contiguous() or a.element_size() != 4:
+                    raise SptrError("update_geometry: device arrays must be contiguous float32")
+                ptr[k], cnt[k] = C.c_void_p(a.data_ptr()), a.numel() // cols
+            else:
+                h = np.ascontiguousarray(a, np.float32).reshape(-1, cols)
+                keep.append(h)
+                ptr[k], cnt[k] = C.c_void_p(h.ctypes.data), len(h)
+        self._check(self._L.sptr_update_geometry(self._h, ptr[0], cnt[0], ptr[1], cnt[1],
+                                                 SPTR_UPDATE_DEVICE_PTRS if device else 0), "update_geometry")
+
+    def refit_info(self) -> dict:
+        """Refits since the upload, wall / device ms of the last one, and the triangles left out of the tree
+        because they were exactly degenerate at upload."""
+        n, ex = C.c_uint32(), C.c_uint32()
+        w, d = C.c_double(), C.c_double()
+        self._check(self._L.sptr_refit_info(self._h, C.byref(n), C.byref(w), C.byref(d), C.byref(ex)), "refit_info")
+        return {"refits": n.value, "ms_wall": w.value, "ms_device": d.value, "excluded_prims": ex.value}
 
     def scene_info(self) -> dict:
         n, nn, dep = C.c_uint32(), C.c_uint32(), C.c_uint32()

@@ -5,7 +5,7 @@
 //   sptr_cli [--scene default|default_emitter|test_triangle|sphere_mesh:STACKS:SLICES|gltf:PATH]
 //            [--w 800] [--h 600] [--spp 4] [--depth 6] [--env sky|FILE.hdr] [--out image.ppm]
 //            [--warmup N] [--json] [--integrator wavefront|pathtracer|optix] [--spf 4] [--launch-mode 0-3]
-//            [--lagged] [--denoise N]
+//            [--lagged] [--denoise N] [--animate K [--rebuild]]
 // --spp N renders N progressive frames of 1 spp each (GLRenderer's m_accumulated_samples loop);
 // --warmup N renders N untimed frames first (then restarts the accumulation by a camera change);
 // --json prints one line with per-frame wall-clock statistics (render + RGB8 read back, as the
@@ -14,7 +14,13 @@
 // --denoise N: HipBackend::Settings::denoise with N a-trous iterations (1..5, default parameters): every
 // frame comes back filtered, and the --json line's ms_aov / ms_filter are the per-frame means of the
 // pass's device times (sptr_denoise_info; with --lagged, the last frame's alone).
+// --animate K: K frames of --spp samples each; before frame k > 0 analytic sphere i moves by a fixed step
+// (0.06 sin 1.7i, 0.04 (i mod 3), 0.05 cos 2.3i), the scene goes through HipBackend::update (a refit in
+// place: Settings::dynamic) and the accumulation restarts; the last frame is written.  --rebuild: the same
+// loop through HipBackend::build instead.  The --json line adds refits, the mean ms_refit_wall /
+// ms_refit_device of the updates and the mean ms_build of the rebuild loop's builds.
 #include <algorithm>
+#include <cmath>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -46,7 +52,8 @@ static bool build_scene(const std::string& s, scene::SceneDesc& sd, MaterialMana
 int main(int argc, char** argv) {
   std::string scene_name = "default", env = "sky", out = "image.ppm";
   int w = 800, h = 600, spp = 4, depth = 6, warmup = 0;
-  bool json = false, lagged = false;
+  bool json = false, lagged = false, rebuild = false;
+  int animate = 0;
   std::string integrator = "wavefront";
   int spf = 4, launch_mode = 0, denoise = 0;
   for (int i = 1; i < argc; ++i) {
@@ -66,8 +73,10 @@ int main(int argc, char** argv) {
     else if (a == "--launch-mode") launch_mode = std::atoi(next());
     else if (a == "--lagged") lagged = true;
     else if (a == "--denoise") denoise = std::atoi(next());
+    else if (a == "--animate") animate = std::atoi(next());
+    else if (a == "--rebuild") rebuild = true;
     else {
-      std::fprintf(stderr, "usage: %s [--scene S] [--w W] [--h H] [--spp N] [--depth D] [--env sky|F.hdr] [--out F] [--warmup N] [--json] [--lagged] [--denoise N]\n",
+      std::fprintf(stderr, "usage: %s [--scene S] [--w W] [--h H] [--spp N] [--depth D] [--env sky|F.hdr] [--out F] [--warmup N] [--json] [--lagged] [--denoise N] [--animate K [--rebuild]]\n",
                    argv[0]);
       return 2;
     }
@@ -102,6 +111,7 @@ int main(int argc, char** argv) {
   st.launch_mode = uint32_t(launch_mode);
   st.lagged_readback = lagged;
   st.denoise.iterations = uint32_t(std::max(0, denoise));
+  st.dynamic = animate > 0 && !rebuild;
   be.setSettings(st);
   if (!be.build(sd)) {
     std::fprintf(stderr, "%s\n", be.lastError().c_str());
@@ -113,16 +123,40 @@ int main(int argc, char** argv) {
     for (int f = 0; f < warmup; ++f) be.render(img.data(), w, h, wcam);  // the camera change below resets
   }
   std::vector<double> frame_ms;
-  frame_ms.reserve(size_t(spp));
+  frame_ms.reserve(size_t(spp) * size_t(std::max(1, animate)));
   double ms_aov = 0.0, ms_filter = 0.0;
   uint32_t aov_passes = 0;
   int dn_frames = 0;
   (void)be.flushStats();  // (the warmup's counters)
+  double ms_refit_wall = 0.0, ms_refit_device = 0.0, ms_build = 0.0;
+  uint32_t refits = 0;
+  int moves = 0;
   const auto t0 = std::chrono::steady_clock::now();
-  for (int f = 0; f < spp; ++f) {
+  const int shots = std::max(1, animate), total_frames = shots * spp;
+  for (int f = 0; f < total_frames; ++f) {
+    if (f > 0 && f % spp == 0) {  // the next animation frame: move the spheres, refit or rebuild
+      for (size_t i = 0; i < sd.spheres.size(); ++i) {
+        const float fi = float(i);
+        sd.spheres[i].center = sd.spheres[i].center +
+                               vec3{0.06f * std::sin(1.7f * fi), 0.04f * float(i % 3), 0.05f * std::cos(2.3f * fi)};
+      }
+      if (!(rebuild ? be.build(sd) : be.update(sd))) {
+        std::fprintf(stderr, "%s\n", be.lastError().c_str());
+        return 1;
+      }
+      ++moves;
+      if (rebuild) {
+        ms_build += be.buildMs();
+      } else {
+        double mw = 0.0, md = 0.0;
+        (void)be.refitInfo(&refits, &mw, &md, nullptr);
+        ms_refit_wall += mw;
+        ms_refit_device += md;
+      }
+    }
     const auto f0 = std::chrono::steady_clock::now();
     be.render(img.data(), w, h, cam);
-    if (denoise > 0 && (!lagged || f == spp - 1)) {  // (waits for the pass: a lagged loop asks once, at its end)
+    if (denoise > 0 && (!lagged || f == total_frames - 1)) {  // (waits for the pass: a lagged loop asks once, at its end)
       double a = 0.0, fl = 0.0;
       if (be.denoiseInfo(&a, &fl, &aov_passes)) {
         ms_aov += a;
@@ -143,10 +177,12 @@ int main(int argc, char** argv) {
     std::printf("{\"scene\": \"%s\", \"launch_mode\": %d, \"width\": %d, \"height\": %d, \"frames\": %d, \"spp_per_frame\": 1, "
                 "\"depth\": %d, \"ms_per_frame_wall\": %.4f, \"ms_per_frame_p50\": %.4f, \"ms_per_frame_p99\": %.4f, "
                 "\"ms_per_frame_device\": %.4f, \"fps\": %.1f, \"mrays_per_s_wall\": %.1f, "
-                "\"lagged_readback\": %s, \"denoise\": %d, \"ms_aov\": %.4f, \"ms_filter\": %.4f, \"aov_passes\": %u, \"path\": \"backends::HipBackend::render (sptr_render + %s per frame)\"}\n",
-                scene_name.c_str(), launch_mode, w, h, spp, depth, wall / spp, pct(0.5), pct(0.99), ms / spp,
-                wall > 0 ? 1e3 * spp / wall : 0.0, wall > 0 ? rays / (wall * 1e3) : 0.0, lagged ? "true" : "false", denoise, dn_frames ? ms_aov / dn_frames : 0.0,
-                dn_frames ? ms_filter / dn_frames : 0.0, aov_passes,
+                "\"lagged_readback\": %s, \"denoise\": %d, \"ms_aov\": %.4f, \"ms_filter\": %.4f, \"aov_passes\": %u, \"animate\": %d, \"refits\": %u, \"ms_refit_wall\": %.4f, \"ms_refit_device\": %.4f, \"ms_build\": %.4f, \"path\": \"backends::HipBackend::render (sptr_render + %s per frame)\"}\n",
+                scene_name.c_str(), launch_mode, w, h, total_frames, depth, wall / total_frames, pct(0.5), pct(0.99), ms / total_frames,
+                wall > 0 ? 1e3 * total_frames / wall : 0.0, wall > 0 ? rays / (wall * 1e3) : 0.0, lagged ? "true" : "false", denoise, dn_frames ? ms_aov / dn_frames : 0.0,
+                dn_frames ? ms_filter / dn_frames : 0.0, aov_passes, animate, refits,
+                moves && !rebuild ? ms_refit_wall / moves : 0.0, moves && !rebuild ? ms_refit_device / moves : 0.0,
+                moves && rebuild ? ms_build / moves : 0.0,
                 lagged ? "sptr_read_rgb8_lagged" : "sptr_read_rgb8");
   } else {
     std::printf("scene=%s %dx%d spp=%d depth=%d: %.2f ms device, %.2f ms wall, %.1f Mrays/s (device)\n",
