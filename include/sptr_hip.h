@@ -422,6 +422,61 @@ int sptr_update_geometry(sptr_ctx* ctx, const float* positions, uint32_t num_ver
 int sptr_refit_info(const sptr_ctx* ctx, uint32_t* refits, double* ms_wall, double* ms_device,
                     uint32_t* excluded_prims);
 
+/* ---- ray queries on caller buffers (symbols added within ABI 9: no existing struct or entry point
+ *      changed) ------------------------------------------------------------------------------------------
+ * Batched closest-hit / any-hit queries against the uploaded (and possibly refitted) scene, for callers that
+ * hold rays in device memory and want the answers there: AO or visibility baking, sensor simulation,
+ * picking, feeding an external denoiser or a learning pipeline.  The rays are walked by the traversal the
+ * render kernels use (scenes staged into LDS are staged, wide scenes take the BVH4 walk), so a ray's hit is
+ * the renderer's hit; (geomID, primID) are resolved on the device (DESIGN.md "Ray queries").
+ *
+ * rays: n x 8 floats (o3, d3, tnear, tfar), as sptr_intersect.  Closest-hit outputs, reported exactly as
+ * sptr_intersect reports them; each pointer may be NULL and is then not written:
+ *   geom, prim: n uint32 each; a miss gives 0xFFFFFFFF twice; a sphere gives prim 0;
+ *   t         : n floats; a miss gives +inf;
+ *   ng        : n x 3 floats, the unnormalised geometric normal; a miss gives 0;
+ *   uv        : n x 2 floats, the barycentrics of a triangle hit: u = U / |den|, v = V / |den| of the
+ *               Moeller-Trumbore terms of the triangle finally hit (IEEE division, as for t), so that the hit
+ *               point is (1 - u - v) v0 + u v1 + v v2 with v0, v1, v2 in the order of the uploaded index
+ *               triple; a sphere hit (the reference's sphere callbacks set no u or v) and a miss give 0.
+ * With SPTR_QUERY_ANY_HIT the only output is occluded (n bytes, 1 = something lies in (tnear, tfar)), as
+ * sptr_occluded; the other output pointers are ignored.
+ *
+ * Pointers: with SPTR_QUERY_DEVICE_PTRS every pointer is a device pointer on the context's device, and the
+ * ray buffer must be 16-byte aligned (SPTR_ERR_INVALID otherwise); without it every pointer is a host
+ * pointer, the library stages the arrays, and the call is synchronous (a non-NULL stream is
+ * SPTR_ERR_INVALID).
+ * Streams: stream == NULL runs on the context's stream, after any pending renders, and returns when the
+ * results are written.  A non-NULL stream (a hipStream_t, device pointers only) only enqueues, as
+ * sptr_unpack_tiles does: consecutive enqueued queries must use one stream (they share the context's
+ * scratch), and the caller synchronises that stream before any upload (sptr_upload_scene, sptr_set_*),
+ * sptr_update_geometry or sptr_destroy: an enqueued query reads the scene in place.
+ * Order: SPTR_QUERY_SORT traces the batch in the order of a per-ray key (a Morton code of the origin, then
+ * the direction's octant and octahedral cell), sorted on the device by the build's radix sort; the results
+ * are written at each ray's own index and do not depend on the order.  SPTR_QUERY_NO_SORT traces in
+ * the caller's order.  With neither flag the library decides (at present it never sorts).
+ * n == 0 returns SPTR_OK with no launch.  SPTR_ERR_INVALID: both sort flags, n > 2^28, NULL rays with n > 0,
+ * SPTR_QUERY_ANY_HIT without occluded, unknown flags, a lane context; SPTR_ERR_NO_SCENE before an upload. */
+enum { SPTR_QUERY_ANY_HIT = 1u, SPTR_QUERY_DEVICE_PTRS = 2u, SPTR_QUERY_SORT = 4u, SPTR_QUERY_NO_SORT = 8u };
+typedef struct sptr_ray_query {
+  const float* rays;   /* n x 8 floats: o3 d3 tnear tfar, as sptr_intersect */
+  uint32_t n;          /* <= 2^28 */
+  uint32_t flags;
+  uint32_t* geom;      /* outputs; each may be NULL and is then not written */
+  uint32_t* prim;
+  float* t;            /* n */
+  float* ng;           /* n x 3, unnormalised, as sptr_intersect */
+  float* uv;           /* n x 2 barycentrics */
+  uint8_t* occluded;   /* n; the only output of SPTR_QUERY_ANY_HIT */
+  uint64_t reserved[4];/* 0 */
+} sptr_ray_query;
+int sptr_query_rays(sptr_ctx* ctx, const sptr_ray_query* query, void* stream);
+/* Waits for the last query: the device times of its sort phase (keys and radix sort; 0 when it was traced
+ * unsorted) and of its trace launch, whether it was sorted (0 / 1), and the queries launched so far (one
+ * with n == 0 launches nothing and is not counted).  SPTR_ERR_HIP, with the text sptr_intersect gives, if the last query set the
+ * traversal-stack-overflow flag (a synchronous query checks the flag itself).  Any pointer may be NULL. */
+int sptr_query_info(sptr_ctx* ctx, double* ms_sort, double* ms_trace, uint32_t* sorted, uint32_t* queries);
+
 /* ---- query entry points (tests / tooling) -------------------------------------------------------- */
 /* Closest-hit / any-hit queries on the device BVH: rays = n*8 floats (o3, d3, tnear, tfar).
  * Outputs as rtcIntersect1 reports them: geomID (0xFFFFFFFF on miss), primID, t, unnormalised Ng. */

@@ -3731,7 +3731,7 @@ struct GridCache {
   unsigned blocks = 0;
 };
 static unsigned resident_grid(const void* fn, uint32_t lds_bytes) {
-  static GridCache cache[32];
+  static GridCache cache[64];
   static int cus = 0;
   int per = 0;
   for (GridCache& g : cache)
@@ -4183,5 +4183,7 @@ void launch_primary(const FrameView& f, float* dirs, uint32_t* rng, hipStream_t 
 
 // first-hit AOVs and the denoiser (they share this file's traversal and resolve helpers)
 #include "kernels_denoise.h"
+// batched ray queries on caller buffers (the same traversal, staged or wide as the render kernels')
+#include "kernels_query.h"
 
 }  // namespace sptr

@@ -67,6 +67,16 @@ struct sptr_ctx {
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // AOV begin / end, filter begin / end
     bool aov_timed = false, filter_timed = false;             // ... recorded by the last pass
   } dn;
+  // sptr_query_rays (the caller's context; a pixel lane holds none): scratch that grows on demand (sort keys
+  // and identity indices, their sorted copies, the radix sort's temporaries, the stack-overflow flag, the
+  // staging of host-pointer queries) and the events of the last query, which may still run on a caller's stream
+  struct RayQuery {
+    sptr::DevBuf keys, index, keys_sorted, order, temp, flag, stage_in, stage_out;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};  // begin, after the sort, end
+    bool issued = false;                             // ev[0] and ev[2] (sorted: ev[1] too) are recorded
+    bool sorted = false;
+    uint32_t count = 0;
+  } rq;
 };
 
 namespace sptr {
@@ -1431,6 +1441,13 @@ int sptr_destroy(sptr_ctx* x) {
     free_buf(*b);
   for (hipEvent_t e : x->dn.ev)
     if (e) (void)hipEventDestroy(e);
+  // a query enqueued on a caller's stream (the caller synchronises it first; this costs nothing then)
+  if (x->rq.issued) (void)hipEventSynchronize(x->rq.ev[2]);
+  for (DevBuf* b : {&x->rq.keys, &x->rq.index, &x->rq.keys_sorted, &x->rq.order, &x->rq.temp, &x->rq.flag,
+                    &x->rq.stage_in, &x->rq.stage_out})
+    free_buf(*b);
+  for (hipEvent_t e : x->rq.ev)
+    if (e) (void)hipEventDestroy(e);
   Context& c = x->c;
   (void)hipSetDevice(c.device);
   if (c.pending) (void)hipStreamSynchronize(c.pending_stream);
@@ -2041,6 +2058,192 @@ int sptr_occluded(sptr_ctx* x, const float* rays, uint32_t n, uint8_t* occ) {
   return run_query(x, rays, n, true, nullptr, nullptr, nullptr, nullptr, occ);
 }
 
+// ---- ray queries on caller buffers -----------------------------------------------------------------
+constexpr uint32_t kQueryMaxRays = 1u << 28;
+constexpr uint32_t kQueryFlags = SPTR_QUERY_ANY_HIT | SPTR_QUERY_DEVICE_PTRS | SPTR_QUERY_SORT | SPTR_QUERY_NO_SORT;
+// Order of a query that sets neither sort flag.  The rule: sort scenes that are not staged
+// into LDS from the smallest batch at which keys + sort + sorted trace beat the unsorted trace by more than
+// the measured spread.  No such batch size has been measured, so the default never sorts.
+static bool query_sorts_by_default(const SceneView&, uint32_t) { return false; }
+
+// the triangle list's geomID offsets on the device (k_aov and k_rayquery derive primIDs from them)
+static int ensure_geom_first(sptr_ctx* x) {
+  Context& c = x->c;
+  auto& d = x->dn;
+  if (d.geom_first_valid) return SPTR_OK;
+  if (sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;
+  API_HIP(ensure_buf(d.geom_first, (c.geom_first.size() + 1) * 4));
+  if (!c.geom_first.empty())
+    API_HIP(hipMemcpy(d.geom_first.p, c.geom_first.data(), c.geom_first.size() * 4, hipMemcpyHostToDevice));
+  d.geom_first_valid = true;
+  return SPTR_OK;
+}
+
+// the last query, on whichever stream it was enqueued
+static int query_wait(sptr_ctx* x) {
+  Context& c = x->c;
+  if (x->rq.issued) API_HIP(hipEventSynchronize(x->rq.ev[2]));
+  return SPTR_OK;
+}
+
+// after the last query completed: its traversal-stack-overflow flag (sticky on the device; cleared once reported)
+static int query_check_flag(sptr_ctx* x) {
+  Context& c = x->c;
+  if (!x->rq.flag.p) return SPTR_OK;
+  uint32_t sflag = 0;
+  API_HIP(hipMemcpy(&sflag, x->rq.flag.p, 4, hipMemcpyDeviceToHost));
+  if (!sflag) return SPTR_OK;
+  API_HIP(hipMemset(x->rq.flag.p, 0, 4));
+  return fail(c, SPTR_ERR_HIP, "query: BVH traversal stack overflow (internal error)");
+}
+
+// One validated batch with device pointers, enqueued on s: [keys, radix sort,] trace.
+static int enqueue_query(sptr_ctx* x, const sptr_ray_query& q, hipStream_t s) {
+  Context& c = x->c;
+  auto& rq = x->rq;
+  const SceneView sv = scene_view(c);
+  const bool any = (q.flags & SPTR_QUERY_ANY_HIT) != 0u;
+  const bool sort = (q.flags & SPTR_QUERY_SORT) != 0u ||
+                    ((q.flags & SPTR_QUERY_NO_SORT) == 0u && sv.lds_bytes == 0u && query_sorts_by_default(sv, q.n));
+  for (hipEvent_t& e : rq.ev)
+    if (!e) API_HIP(hipEventCreate(&e));
+  if (!rq.flag.p) {
+    API_HIP(ensure_buf(rq.flag, 16));
+    API_HIP(hipMemset(rq.flag.p, 0, 16));
+  }
+  const int rg = ensure_geom_first(x);
+  if (rg != SPTR_OK) return rg;
+  size_t temp_bytes = 0;
+  if (sort) {
+    API_HIP(radix_sort_pairs_u64(nullptr, temp_bytes, nullptr, nullptr, nullptr, nullptr, q.n, s));
+    const size_t kb = (size_t)q.n * 8, ib = (size_t)q.n * 4;
+    if (rq.keys.bytes < kb || rq.keys_sorted.bytes < kb || rq.index.bytes < ib || rq.order.bytes < ib ||
+        rq.temp.bytes < temp_bytes) {
+      const int rw = query_wait(x);  // an enqueued query may still use the old scratch
+      if (rw != SPTR_OK) return rw;
+      API_HIP(ensure_buf(rq.keys, kb));
+      API_HIP(ensure_buf(rq.keys_sorted, kb));
+      API_HIP(ensure_buf(rq.index, ib));
+      API_HIP(ensure_buf(rq.order, ib));
+      API_HIP(ensure_buf(rq.temp, temp_bytes));
+    }
+  }
+  RayQueryView v{};
+  v.rays = reinterpret_cast<const float4*>(q.rays);
+  v.n = q.n;
+  if (any) {
+    v.occ = q.occluded;
+  } else {
+    v.geom = q.geom;
+    v.prim = q.prim;
+    v.t = q.t;
+    v.ng = q.ng;
+    v.uv = q.uv;
+  }
+  v.tri_orig = static_cast<const uint32_t*>(c.tri_orig.p);
+  v.geom_first = static_cast<const uint32_t*>(x->dn.geom_first.p);
+  v.stack_overflow = static_cast<uint32_t*>(rq.flag.p);
+  API_HIP(hipEventRecord(rq.ev[0], s));
+  if (sort) {
+    launch_ray_keys(sv, v.rays, q.n, static_cast<uint64_t*>(rq.keys.p), static_cast<uint32_t*>(rq.index.p), s);
+    API_HIP(hipGetLastError());
+    size_t tb = rq.temp.bytes;
+    API_HIP(radix_sort_pairs_u64(rq.temp.p, tb, static_cast<const uint64_t*>(rq.keys.p),
+                                 static_cast<uint64_t*>(rq.keys_sorted.p), static_cast<const uint32_t*>(rq.index.p),
+                                 static_cast<uint32_t*>(rq.order.p), q.n, s));
+    API_HIP(hipEventRecord(rq.ev[1], s));
+    v.order = static_cast<const uint32_t*>(rq.order.p);
+  }
+  launch_rayquery(sv, v, any, s);
+  API_HIP(hipGetLastError());
+  API_HIP(hipEventRecord(rq.ev[2], s));
+  rq.issued = true;
+  rq.sorted = sort;
+  ++rq.count;
+  return SPTR_OK;
+}
+
+int sptr_query_rays(sptr_ctx* x, const sptr_ray_query* q, void* stream) {
+  if (!x || !q) return SPTR_ERR_INVALID;
+  Context& c = x->c;
+  if (x->is_lane) return fail(c, SPTR_ERR_INVALID, "query_rays: not on a lane context");
+  const bool any = (q->flags & SPTR_QUERY_ANY_HIT) != 0u, dev = (q->flags & SPTR_QUERY_DEVICE_PTRS) != 0u;
+  if (q->flags & ~kQueryFlags) return fail(c, SPTR_ERR_INVALID, "query_rays: unknown flags");
+  if ((q->flags & SPTR_QUERY_SORT) && (q->flags & SPTR_QUERY_NO_SORT))
+    return fail(c, SPTR_ERR_INVALID, "query_rays: SPTR_QUERY_SORT and SPTR_QUERY_NO_SORT exclude each other");
+  if (q->n > kQueryMaxRays) return fail(c, SPTR_ERR_INVALID, "query_rays: more than 2^28 rays");
+  if (q->n && !q->rays) return fail(c, SPTR_ERR_INVALID, "query_rays: no rays");
+  if (any && !q->occluded) return fail(c, SPTR_ERR_INVALID, "query_rays: SPTR_QUERY_ANY_HIT needs the occluded output");
+  if (!dev && stream) return fail(c, SPTR_ERR_INVALID, "query_rays: host pointers cannot be enqueued on a stream");
+  if (dev && (reinterpret_cast<uintptr_t>(q->rays) & 15u))
+    return fail(c, SPTR_ERR_INVALID, "query_rays: the device ray buffer must be 16-byte aligned");
+  if (!c.have_scene) return fail(c, SPTR_ERR_NO_SCENE, "query_rays: no scene");
+  if (q->n == 0u) return SPTR_OK;
+  API_HIP(hipSetDevice(c.device));
+  if (stream) return enqueue_query(x, *q, static_cast<hipStream_t>(stream));  // on a caller's stream the call only enqueues
+  if (sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;
+  const int rw = query_wait(x);
+  if (rw != SPTR_OK) return rw;
+  sptr_ray_query d = *q;
+  const size_t n = q->n;
+  // host pointers: rays in, then geom | prim | t | ng | uv | occluded out, staged in the context
+  const size_t off_prim = n * 4, off_t = n * 8, off_ng = n * 12, off_uv = n * 24, off_occ = n * 32;
+  if (!dev) {
+    auto& rq = x->rq;
+    API_HIP(ensure_buf(rq.stage_in, n * 32));
+    API_HIP(ensure_buf(rq.stage_out, n * 33));
+    API_HIP(hipMemcpy(rq.stage_in.p, q->rays, n * 32, hipMemcpyHostToDevice));
+    char* o = static_cast<char*>(rq.stage_out.p);
+    d.rays = static_cast<const float*>(rq.stage_in.p);
+    d.geom = q->geom ? reinterpret_cast<uint32_t*>(o) : nullptr;
+    d.prim = q->prim ? reinterpret_cast<uint32_t*>(o + off_prim) : nullptr;
+    d.t = q->t ? reinterpret_cast<float*>(o + off_t) : nullptr;
+    d.ng = q->ng ? reinterpret_cast<float*>(o + off_ng) : nullptr;
+    d.uv = q->uv ? reinterpret_cast<float*>(o + off_uv) : nullptr;
+    d.occluded = reinterpret_cast<uint8_t*>(o + off_occ);
+  }
+  const int rc = enqueue_query(x, d, c.stream);
+  if (rc != SPTR_OK) return rc;
+  API_HIP(hipStreamSynchronize(c.stream));
+  const int rf = query_check_flag(x);
+  if (rf != SPTR_OK) return rf;
+  if (!dev) {
+    if (any) {
+      API_HIP(hipMemcpy(q->occluded, d.occluded, n, hipMemcpyDeviceToHost));
+    } else {
+      if (q->geom) API_HIP(hipMemcpy(q->geom, d.geom, n * 4, hipMemcpyDeviceToHost));
+      if (q->prim) API_HIP(hipMemcpy(q->prim, d.prim, n * 4, hipMemcpyDeviceToHost));
+      if (q->t) API_HIP(hipMemcpy(q->t, d.t, n * 4, hipMemcpyDeviceToHost));
+      if (q->ng) API_HIP(hipMemcpy(q->ng, d.ng, n * 12, hipMemcpyDeviceToHost));
+      if (q->uv) API_HIP(hipMemcpy(q->uv, d.uv, n * 8, hipMemcpyDeviceToHost));
+    }
+  }
+  return SPTR_OK;
+}
+
+int sptr_query_info(sptr_ctx* x, double* ms_sort, double* ms_trace, uint32_t* sorted, uint32_t* queries) {
+  if (!x) return SPTR_ERR_INVALID;
+  Context& c = x->c;
+  auto& rq = x->rq;
+  double ms_s = 0.0, ms_t = 0.0;
+  if (rq.issued) {
+    API_HIP(hipSetDevice(c.device));
+    API_HIP(hipEventSynchronize(rq.ev[2]));
+    float ms = 0.0f;
+    if (rq.sorted) {
+      API_HIP(hipEventElapsedTime(&ms, rq.ev[0], rq.ev[1]));
+      ms_s = ms;
+    }
+    API_HIP(hipEventElapsedTime(&ms, rq.sorted ? rq.ev[1] : rq.ev[0], rq.ev[2]));
+    ms_t = ms;
+  }
+  if (ms_sort) *ms_sort = ms_s;
+  if (ms_trace) *ms_trace = ms_t;
+  if (sorted) *sorted = rq.issued && rq.sorted ? 1u : 0u;
+  if (queries) *queries = rq.count;
+  return rq.issued ? query_check_flag(x) : SPTR_OK;
+}
+
 int sptr_primary_rays(sptr_ctx* x, const sptr_camera* cam, int32_t W, int32_t H, uint32_t acc, float* dirs,
                       uint32_t* rng) {
   if (!x || !cam || W <= 0 || H <= 0 || !dirs || !rng) return SPTR_ERR_INVALID;
@@ -2452,13 +2655,8 @@ static int ensure_aov(sptr_ctx* x, const sptr_camera& cam, int W, int H, hipStre
     API_HIP(ensure_buf(d.flag, 16));
     API_HIP(hipMemset(d.flag.p, 0, 16));
   }
-  if (!d.geom_first_valid) {
-    if (sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;
-    API_HIP(ensure_buf(d.geom_first, (c.geom_first.size() + 1) * 4));
-    if (!c.geom_first.empty())
-      API_HIP(hipMemcpy(d.geom_first.p, c.geom_first.data(), c.geom_first.size() * 4, hipMemcpyHostToDevice));
-    d.geom_first_valid = true;
-  }
+  const int rg = ensure_geom_first(x);
+  if (rg != SPTR_OK) return rg;
   sptr_frame fr{};
   fr.width = W;
   fr.height = H;

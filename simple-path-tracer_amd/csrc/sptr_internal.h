@@ -306,6 +306,21 @@ struct AovView {
   const uint32_t* geom_mat;
   uint32_t* stack_overflow;    // sticky flag (cannot happen within the build's stack bound)
 };
+// One batch of ray queries on caller buffers (k_rayquery): device pointers, indexed by ray.
+struct RayQueryView {
+  const float4* rays;     // two per ray: o.xyz d.x | d.yz tnear tfar
+  uint32_t n;
+  const uint32_t* order;  // sorted batches: thread j traces ray order[j]; null: ray j
+  uint32_t* geom;         // closest-hit outputs, each may be null (not written)
+  uint32_t* prim;
+  float* t;
+  float* ng;              // n x 3
+  float* uv;              // n x 2
+  uint8_t* occ;           // the any-hit output
+  const uint32_t* tri_orig;    // as AovView's
+  const uint32_t* geom_first;
+  uint32_t* stack_overflow;    // sticky flag
+};
 // The denoiser's per-pass constants (k_dn_mean, k_atrous, k_dn_resolve), image space.
 struct DenoiseView {
   int32_t W, H;
@@ -580,6 +595,10 @@ void launch_aov(const SceneView& sv, const FrameView& f, const AovView& a, hipSt
 void launch_dn_mean(const DenoiseView& v, const float4* accum0, const float4* accum1, int G, float4* out, hipStream_t s);
 void launch_atrous(const DenoiseView& v, const float4* cin, float4* cout, int step, float S2, hipStream_t s);
 void launch_dn_resolve(const DenoiseView& v, const float4* c, uint8_t* image, hipStream_t s);
+// kernels_query.h: one batch of ray queries (sptr_query_rays), and the sort keys of a batch with the
+// identity indices 0..n-1 beside them (the radix sort's values)
+void launch_rayquery(const SceneView& sv, const RayQueryView& q, bool anyhit, hipStream_t s);
+void launch_ray_keys(const SceneView& sv, const float4* rays, uint32_t n, uint64_t* keys, uint32_t* index, hipStream_t s);
 // one wave spinning for `ticks` of the device wall clock (sptr_overlap_probe)
 void launch_spin(uint64_t ticks, hipStream_t s);
 

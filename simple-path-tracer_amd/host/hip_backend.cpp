@@ -234,4 +234,36 @@ bool HipBackend::renderLinear(float* rgb32, int width, int height, const Camera&
   return true;
 }
 
+bool HipBackend::queryRays(const float* rays, uint32_t n, bool anyHit, HitBuffers& out) {
+  if (!ctx_ || !built_) {
+    err_ = "HipBackend::queryRays: build() has not succeeded";
+    return false;
+  }
+  sptr_ray_query q{};
+  q.rays = rays;
+  q.n = n;
+  if (anyHit) {
+    out.occluded.assign(n, 0);
+    q.flags = SPTR_QUERY_ANY_HIT;
+    q.occluded = out.occluded.data();
+  } else {
+    out.geom.assign(n, 0u);
+    out.prim.assign(n, 0u);
+    out.t.assign(n, 0.0f);
+    out.ng.assign(size_t(n) * 3, 0.0f);
+    out.uv.assign(size_t(n) * 2, 0.0f);
+    q.geom = out.geom.data();
+    q.prim = out.prim.data();
+    q.t = out.t.data();
+    q.ng = out.ng.data();
+    q.uv = out.uv.data();
+  }
+  if (n == 0u) return true;
+  if (sptr_query_rays(ctx_, &q, nullptr) != SPTR_OK) {
+    err_ = std::string("HipBackend::queryRays: ") + sptr_last_error(ctx_);
+    return false;
+  }
+  return true;
+}
+
 }  // namespace backends

@@ -85,6 +85,15 @@ class HipBackend {
   bool denoiseInfo(double* ms_aov, double* ms_filter, uint32_t* aov_passes) const {
     return ctx_ && sptr_denoise_info(ctx_, ms_aov, ms_filter, aov_passes) == SPTR_OK;
   }
+  // sptr_query_rays with host pointers: n rays of 8 floats (o3, d3, tnear, tfar) against the built scene,
+  // traced by the renderer's traversal.  Closest hit fills geom, prim, t, ng (n x 3) and uv (n x 2) as
+  // include/sptr_hip.h describes them (a miss: geom = prim = 0xFFFFFFFF, t = +inf); anyHit fills occluded.
+  struct HitBuffers {
+    std::vector<uint32_t> geom, prim;
+    std::vector<float> t, ng, uv;
+    std::vector<uint8_t> occluded;
+  };
+  bool queryRays(const float* rays, uint32_t n, bool anyHit, HitBuffers& out);
   uint32_t frameIndex() const { return frame_index_; }
   const std::string& lastError() const { return err_; }
   const std::vector<uint32_t>& getGeomMaterialMapping() const { return geom_material_; }

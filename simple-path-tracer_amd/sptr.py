@@ -27,6 +27,10 @@ SPTR_FRAME_TIMING_TRACE = 16
 SPTR_FRAME_NO_CULL = 32
 SPTR_FRAME_RECULL = 64
 SPTR_UPDATE_DEVICE_PTRS = 1
+SPTR_QUERY_ANY_HIT = 1
+SPTR_QUERY_DEVICE_PTRS = 2
+SPTR_QUERY_SORT = 4
+SPTR_QUERY_NO_SORT = 8
 
 SPTR_INTEGRATOR_WAVEFRONT = 0   # WavefrontPathTracerCPU semantics (default)
 SPTR_INTEGRATOR_PATHTRACER = 1  # PathTracer (the reference's default CPU integrator) semantics
@@ -112,6 +116,13 @@ class DenoiseParams(C.Structure):
                 ("sigma_albedo", C.c_float), ("normal_log2_power", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
+class RayQuery(C.Structure):
+    """sptr_ray_query: pointers as addresses (host or device, by SPTR_QUERY_DEVICE_PTRS)."""
+    _fields_ = [("rays", C.c_void_p), ("n", C.c_uint32), ("flags", C.c_uint32), ("geom", C.c_void_p),
+                ("prim", C.c_void_p), ("t", C.c_void_p), ("ng", C.c_void_p), ("uv", C.c_void_p),
+                ("occluded", C.c_void_p), ("reserved", C.c_uint64 * 4)]
+
+
 SPTR_AOV_ALBEDO, SPTR_AOV_NORMAL, SPTR_AOV_DEPTH, SPTR_AOV_ID = 0, 1, 2, 3
 
 _lib = None
@@ -127,6 +138,7 @@ EXPORTS = [
     "sptr_sort_pairs_u64", "sptr_scan_u32", "sptr_eval_math",
     "sptr_set_denoise", "sptr_read_aov", "sptr_read_denoised", "sptr_denoise_info",
     "sptr_set_dynamic", "sptr_update_geometry", "sptr_refit_info",
+    "sptr_query_rays", "sptr_query_info",
     "sptr_host_builtin_scene", "sptr_host_scene_view", "sptr_host_scene_free", "sptr_host_camera_lookat",
     "sptr_host_preset_materials", "sptr_host_default_lights", "sptr_host_equirect_to_faces",
     "sptr_host_pack_tiles", "sptr_host_unpack_tiles", "sptr_host_load_hdr", "sptr_host_free",
@@ -187,6 +199,8 @@ def lib() -> C.CDLL:
         "sptr_set_dynamic": (C.c_int, [vp, u32]),
         "sptr_update_geometry": (C.c_int, [vp, vp, u32, vp, u32, u32]),
         "sptr_refit_info": (C.c_int, [vp, up, C.POINTER(C.c_double), C.POINTER(C.c_double), up]),
+        "sptr_query_rays": (C.c_int, [vp, C.POINTER(RayQuery), vp]),
+        "sptr_query_info": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), up, up]),
         "sptr_host_builtin_scene": (C.c_int, [C.c_char_p, u32, u32, C.POINTER(vp)]),
         "sptr_host_scene_view": (C.c_int, [vp, C.POINTER(Scene)]),
         "sptr_host_scene_free": (None, [vp]),
@@ -610,6 +624,94 @@ class Renderer:
         out = np.zeros(len(rays), np.uint8)
         self._check(self._L.sptr_occluded(self._h, _f(rays), len(rays), _b(out)), "occluded")
         return out
+
+    _QUERY_FIELDS = (("geom", 1, np.uint32), ("prim", 1, np.uint32), ("t", 1, np.float32), ("ng", 3, np.float32),
+                     ("uv", 2, np.float32))
+    _QUERY_EMPTY = C.c_uint64(0)
+
+    def query_rays(self, rays, any_hit: bool = False, sort: bool | None = None, uv: bool = True,
+                   stream: int | None = None, fields=None, out: dict | None = None) -> dict:
+        """sptr_query_rays: closest-hit (or, with any_hit, occlusion) queries for n rays of 8 floats (o3, d3,
+        tnear, tfar), walked by the render kernels' traversal.
+
+        A numpy (n, 8) array takes the host path and returns numpy arrays.  A contiguous float32 tensor on
+        this context's GPU (anything with data_ptr() and numel(); 16-byte aligned) takes the device path and
+        returns torch tensors allocated on that device; nothing crosses the host.  The result is a dict with
+        geom, prim (n, uint32; 0xFFFFFFFF on a miss), t (n; +inf on a miss), ng (n, 3) and uv (n, 2; the
+        barycentrics of a triangle hit, include/sptr_hip.h), or with occluded (n, uint8).
+        sort: None lets the library decide, True / False force SPTR_QUERY_SORT / SPTR_QUERY_NO_SORT (the
+        results do not depend on it).  uv=False leaves the barycentrics out; fields names the outputs wanted
+        (a subset of geom, prim, t, ng, uv), the others are not computed.  out: preallocated contiguous arrays
+        (host path) or tensors (device path) to write into, by name.
+        stream: a hipStream_t handle (device path only): the query is only enqueued there and the returned
+        tensors are valid once that stream is synchronised; the caller orders the stream after the rays'
+        producer.  Without it a device-path call waits for torch's current stream first, runs on the
+        context's stream and returns when the results are written."""
+        device = hasattr(rays, "data_ptr")
+        if device:
+            import torch
+
+            if rays.element_size() != 4 or not rays.is_floating_point() or not rays.is_contiguous() or rays.numel() % 8:
+                raise SptrError("query_rays: device rays must be a contiguous float32 tensor of n x 8")
+            n = rays.numel() // 8
+            tdt = {np.uint32: torch.uint32, np.float32: torch.float32, np.uint8: torch.uint8}
+
+            def alloc(cols, dt):
+                return torch.empty((n, cols) if cols > 1 else (n,), dtype=tdt[dt], device=rays.device)
+
+            def addr(a):
+                return a.data_ptr()
+
+            def ok(a, cols, dt):
+                return a.is_contiguous() and a.numel() == n * cols and a.dtype == tdt[dt] and a.device == rays.device
+        else:
+            if stream is not None:
+                raise SptrError("query_rays: a stream needs device tensors")
+            rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+            n = len(rays)
+
+            def alloc(cols, dt):
+                return np.zeros((n, cols) if cols > 1 else (n,), dt)
+
+            def addr(a):
+                return a.ctypes.data
+
+            def ok(a, cols, dt):
+                return isinstance(a, np.ndarray) and a.flags.c_contiguous and a.size == n * cols and a.dtype == dt
+        if any_hit:
+            want = (("occluded", 1, np.uint8),)
+        else:
+            names = [f for f, _, _ in self._QUERY_FIELDS if uv or f != "uv"] if fields is None else list(fields)
+            if not names or any(f not in [g for g, _, _ in self._QUERY_FIELDS] for f in names):
+                raise SptrError(f"query_rays: fields must name some of geom, prim, t, ng, uv (got {names})")
+            want = tuple(x for x in self._QUERY_FIELDS if x[0] in names)
+        res = {}
+        for name, cols, dt in want:
+            a = (out or {}).get(name)
+            if a is None:
+                a = alloc(cols, dt)
+            elif not ok(a, cols, dt):
+                raise SptrError(f"query_rays: out[{name!r}] must be contiguous, of {n} x {cols} {np.dtype(dt).name}")
+            res[name] = a
+        q = RayQuery()
+        q.rays = addr(rays) if n else None
+        q.n = n
+        q.flags = ((SPTR_QUERY_ANY_HIT if any_hit else 0) | (SPTR_QUERY_DEVICE_PTRS if device else 0)
+                   | (0 if sort is None else SPTR_QUERY_SORT if sort else SPTR_QUERY_NO_SORT))
+        for name, a in res.items():  # (an empty tensor has no address: n == 0 writes nothing, any non-NULL will do)
+            setattr(q, name, addr(a) or (C.addressof(self._QUERY_EMPTY) if n == 0 else None))
+        if device and stream is None and n:
+            torch.cuda.current_stream(rays.device).synchronize()  # the rays' (and the outputs') producers
+        self._check(self._L.sptr_query_rays(self._h, C.byref(q), C.c_void_p(stream) if stream else None), "query_rays")
+        return res
+
+    def query_info(self) -> dict:
+        """sptr_query_info: waits for the last query; device ms of its sort phase (0 when unsorted) and of its
+        trace launch, whether it was sorted (0 / 1), and the queries launched so far."""
+        s, t = C.c_double(), C.c_double()
+        so, n = C.c_uint32(), C.c_uint32()
+        self._check(self._L.sptr_query_info(self._h, C.byref(s), C.byref(t), C.byref(so), C.byref(n)), "query_info")
+        return {"ms_sort": s.value, "ms_trace": t.value, "sorted": so.value, "queries": n.value}
 
     def primary_rays(self, cam: Camera, width: int, height: int, acc: int):
         dirs = np.zeros((height, width, 3), np.float32)

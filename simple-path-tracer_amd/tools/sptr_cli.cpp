@@ -5,7 +5,7 @@
 //   sptr_cli [--scene default|default_emitter|test_triangle|sphere_mesh:STACKS:SLICES|gltf:PATH]
 //            [--w 800] [--h 600] [--spp 4] [--depth 6] [--env sky|FILE.hdr] [--out image.ppm]
 //            [--warmup N] [--json] [--integrator wavefront|pathtracer|optix] [--spf 4] [--launch-mode 0-3]
-//            [--lagged] [--denoise N] [--animate K [--rebuild]]
+//            [--lagged] [--denoise N] [--animate K [--rebuild]] [--query-centre-rays]
 // --spp N renders N progressive frames of 1 spp each (GLRenderer's m_accumulated_samples loop);
 // --warmup N renders N untimed frames first (then restarts the accumulation by a camera change);
 // --json prints one line with per-frame wall-clock statistics (render + RGB8 read back, as the
@@ -19,12 +19,16 @@
 // place: Settings::dynamic) and the accumulation restarts; the last frame is written.  --rebuild: the same
 // loop through HipBackend::build instead.  The --json line adds refits, the mean ms_refit_wall /
 // ms_refit_device of the updates and the mean ms_build of the rebuild loop's builds.
+// --query-centre-rays: after the render, the W x H pixel-centre rays of the camera (the rays of the first-hit
+// AOVs: direction getRayDirection((x + 0.5) / W, (y + 0.5) / H), tnear 0, tfar inf) go through
+// HipBackend::queryRays; the --json line adds "query": {"rays": n, "hits": h, "tri_hits": k}.
 #include <algorithm>
 #include <cmath>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -52,7 +56,7 @@ static bool build_scene(const std::string& s, scene::SceneDesc& sd, MaterialMana
 int main(int argc, char** argv) {
   std::string scene_name = "default", env = "sky", out = "image.ppm";
   int w = 800, h = 600, spp = 4, depth = 6, warmup = 0;
-  bool json = false, lagged = false, rebuild = false;
+  bool json = false, lagged = false, rebuild = false, query_centre = false;
   int animate = 0;
   std::string integrator = "wavefront";
   int spf = 4, launch_mode = 0, denoise = 0;
@@ -75,8 +79,9 @@ int main(int argc, char** argv) {
     else if (a == "--denoise") denoise = std::atoi(next());
     else if (a == "--animate") animate = std::atoi(next());
     else if (a == "--rebuild") rebuild = true;
+    else if (a == "--query-centre-rays") query_centre = true;
     else {
-      std::fprintf(stderr, "usage: %s [--scene S] [--w W] [--h H] [--spp N] [--depth D] [--env sky|F.hdr] [--out F] [--warmup N] [--json] [--lagged] [--denoise N] [--animate K [--rebuild]]\n",
+      std::fprintf(stderr, "usage: %s [--scene S] [--w W] [--h H] [--spp N] [--depth D] [--env sky|F.hdr] [--out F] [--warmup N] [--json] [--lagged] [--denoise N] [--animate K [--rebuild]] [--query-centre-rays]\n",
                    argv[0]);
       return 2;
     }
@@ -169,6 +174,32 @@ int main(int argc, char** argv) {
   const sptr_stats tot = be.flushStats();  // (lagged: waits for the last frames, inside the clock)
   const double wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   const uint64_t rays = tot.rays_closest + tot.rays_shadow;
+  size_t q_rays = 0, q_hits = 0, q_tri_hits = 0;
+  if (query_centre) {
+    std::vector<float> qr(size_t(w) * h * 8);
+    const sptr_camera dc = cam.toDevice();
+    for (int y = 0; y < h; ++y)
+      for (int x = 0; x < w; ++x) {
+        const vec3 d = cam.getRayDirection((float(x) + 0.5f) / float(w), (float(y) + 0.5f) / float(h));
+        float* r = &qr[(size_t(y) * w + x) * 8];
+        r[0] = dc.pos[0], r[1] = dc.pos[1], r[2] = dc.pos[2];
+        r[3] = d.x, r[4] = d.y, r[5] = d.z;
+        r[6] = 0.0f, r[7] = std::numeric_limits<float>::infinity();
+      }
+    backends::HipBackend::HitBuffers hb;
+    if (!be.queryRays(qr.data(), uint32_t(size_t(w) * h), false, hb)) {
+      std::fprintf(stderr, "%s\n", be.lastError().c_str());
+      return 1;
+    }
+    // geomIDs: the triangle geometries first, then one per analytic sphere
+    const size_t tri_geoms = be.getGeomMaterialMapping().size() - sd.spheres.size();
+    q_rays = hb.geom.size();
+    for (uint32_t g : hb.geom) {
+      if (g == 0xFFFFFFFFu) continue;
+      ++q_hits;
+      if (g < tri_geoms) ++q_tri_hits;
+    }
+  }
   const double ms = tot.ms_total;
   if (json) {
     std::vector<double> s = frame_ms;
@@ -177,13 +208,15 @@ int main(int argc, char** argv) {
     std::printf("{\"scene\": \"%s\", \"launch_mode\": %d, \"width\": %d, \"height\": %d, \"frames\": %d, \"spp_per_frame\": 1, "
                 "\"depth\": %d, \"ms_per_frame_wall\": %.4f, \"ms_per_frame_p50\": %.4f, \"ms_per_frame_p99\": %.4f, "
                 "\"ms_per_frame_device\": %.4f, \"fps\": %.1f, \"mrays_per_s_wall\": %.1f, "
-                "\"lagged_readback\": %s, \"denoise\": %d, \"ms_aov\": %.4f, \"ms_filter\": %.4f, \"aov_passes\": %u, \"animate\": %d, \"refits\": %u, \"ms_refit_wall\": %.4f, \"ms_refit_device\": %.4f, \"ms_build\": %.4f, \"path\": \"backends::HipBackend::render (sptr_render + %s per frame)\"}\n",
+                "\"lagged_readback\": %s, \"denoise\": %d, \"ms_aov\": %.4f, \"ms_filter\": %.4f, \"aov_passes\": %u, \"animate\": %d, \"refits\": %u, \"ms_refit_wall\": %.4f, \"ms_refit_device\": %.4f, \"ms_build\": %.4f, \"path\": \"backends::HipBackend::render (sptr_render + %s per frame)\"",
                 scene_name.c_str(), launch_mode, w, h, total_frames, depth, wall / total_frames, pct(0.5), pct(0.99), ms / total_frames,
                 wall > 0 ? 1e3 * total_frames / wall : 0.0, wall > 0 ? rays / (wall * 1e3) : 0.0, lagged ? "true" : "false", denoise, dn_frames ? ms_aov / dn_frames : 0.0,
                 dn_frames ? ms_filter / dn_frames : 0.0, aov_passes, animate, refits,
                 moves && !rebuild ? ms_refit_wall / moves : 0.0, moves && !rebuild ? ms_refit_device / moves : 0.0,
                 moves && rebuild ? ms_build / moves : 0.0,
                 lagged ? "sptr_read_rgb8_lagged" : "sptr_read_rgb8");
+    if (query_centre) std::printf(", \"query\": {\"rays\": %zu, \"hits\": %zu, \"tri_hits\": %zu}", q_rays, q_hits, q_tri_hits);
+    std::printf("}\n");
   } else {
     std::printf("scene=%s %dx%d spp=%d depth=%d: %.2f ms device, %.2f ms wall, %.1f Mrays/s (device)\n",
                 scene_name.c_str(), w, h, spp, depth, ms, wall, ms > 0 ? rays / (ms * 1e3) : 0.0);
