@@ -806,31 +806,6 @@ __global__ void k_wide_emit(uint32_t ncur, const uint2* cur, uint32_t base, cons
   }
 }
 
-struct Tmp {
-  std::vector<void*> ptrs;
-  ~Tmp() {
-    for (void* p : ptrs) (void)hipFree(p);
-  }
-  template <class T>
-  hipError_t alloc(T** p, size_t n) {
-    void* q = nullptr;
-    hipError_t e = hipMalloc(&q, n ? n * sizeof(T) : 16);
-    if (e == hipSuccess) ptrs.push_back(q);
-    *p = static_cast<T*>(q);
-    return e;
-  }
-};
-
-hipError_t realloc_buf(DevBuf& b, size_t bytes) {
-  if (b.p && b.bytes >= bytes) return hipSuccess;
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.bytes = 0;
-  hipError_t e = hipMalloc(&b.p, bytes ? bytes : 16);
-  if (e == hipSuccess) b.bytes = bytes ? bytes : 16;
-  return e;
-}
-
 unsigned blocks_for(size_t n) {
   size_t b = (n + 255) / 256;
   if (b < 1) b = 1;
@@ -853,7 +828,7 @@ int build_lbvh(Context& c, const float* h_pos, uint32_t nverts, const uint32_t* 
   c.rf.refits = 0;
   c.rf.num_verts = nverts;
   c.rf.max_h = 0;
-  if (!c.dynamic) refit_release(c, false);
+  if (!c.dynamic) refit_release(c);
   if (NP == 0) {
     c.num_nodes = 0;
     c.num_tri_refs = 0;
@@ -864,7 +839,7 @@ int build_lbvh(Context& c, const float* h_pos, uint32_t nverts, const uint32_t* 
     c.stack_need2 = c.stack_need4 = 0;
     return SPTR_OK;
   }
-  Tmp tmp;
+  DevTemps tmp;
   float* d_pos = nullptr;
   uint32_t *d_idx = nullptr, *d_tg = nullptr;
   float4* d_sph = nullptr;
@@ -914,14 +889,14 @@ int build_lbvh(Context& c, const float* h_pos, uint32_t nverts, const uint32_t* 
   c.num_tri_refs = ntri_refs;
   c.num_nodes = NR > 1 ? NR - 1 : 0;
   // + 64 B: the unified wide walk (wide_walk_u) reads a node's 56 B from a direct leaf's primitive address
-  LB_CHECK(realloc_buf(c.tris, (size_t)ntri_refs * 48 + 64));
-  LB_CHECK(realloc_buf(c.tri_geom, (size_t)ntri_refs * 4));
-  LB_CHECK(realloc_buf(c.tri_orig, (size_t)ntri_refs * 4));
-  LB_CHECK(realloc_buf(c.sph, (size_t)nsph * 16 + 64));
-  LB_CHECK(realloc_buf(c.sph_geom, (size_t)nsph * 4));
-  LB_CHECK(realloc_buf(c.sph_orig, (size_t)nsph * 4));
-  LB_CHECK(realloc_buf(c.nodes, (size_t)c.num_nodes * sizeof(BvhNode)));
-  LB_CHECK(realloc_buf(c.prim_ref, ((size_t)NR + 3) / 4 * 16));
+  LB_CHECK(c.tris.ensure((size_t)ntri_refs * 48 + 64));
+  LB_CHECK(c.tri_geom.ensure((size_t)ntri_refs * 4));
+  LB_CHECK(c.tri_orig.ensure((size_t)ntri_refs * 4));
+  LB_CHECK(c.sph.ensure((size_t)nsph * 16 + 64));
+  LB_CHECK(c.sph_geom.ensure((size_t)nsph * 4));
+  LB_CHECK(c.sph_orig.ensure((size_t)nsph * 4));
+  LB_CHECK(c.nodes.ensure((size_t)c.num_nodes * sizeof(BvhNode)));
+  LB_CHECK(c.prim_ref.ensure(((size_t)NR + 3) / 4 * 16));
 
   float4 *blo = nullptr, *bhi = nullptr;
   uint32_t* cb = nullptr;
@@ -1073,8 +1048,8 @@ int build_lbvh(Context& c, const float* h_pos, uint32_t nverts, const uint32_t* 
       }
       ho[kMaxHeight] = run;
       c.rf.max_h = max_h;
-      LB_CHECK(realloc_buf(c.rf.order, (size_t)nn * 4));
-      LB_CHECK(realloc_buf(c.rf.hoff, ho.size() * 4));
+      LB_CHECK(c.rf.order.ensure((size_t)nn * 4));
+      LB_CHECK(c.rf.hoff.ensure(ho.size() * 4));
       LB_CHECK(hipMemcpyAsync(hhist, bh.data(), bh.size() * 4, hipMemcpyHostToDevice, s));
       LB_CHECK(hipMemcpyAsync(c.rf.hoff.p, ho.data(), ho.size() * 4, hipMemcpyHostToDevice, s));
       hipLaunchKernelGGL(k_height_scatter, dim3(kHeightBlocks), dim3(256), 0, s, nn, per, hlab, hhist,
@@ -1109,8 +1084,8 @@ int build_lbvh(Context& c, const float* h_pos, uint32_t nverts, const uint32_t* 
       LB_CHECK(scan_u32(nullptr, sw, flag, off, N, s));
       void* stw = nullptr;
       LB_CHECK(tmp.alloc(reinterpret_cast<char**>(&stw), sw));
-      LB_CHECK(realloc_buf(c.nodes4, (size_t)(N - 1) * sizeof(WideNode)));  // <= one wide node per BVH2 node
-      if (retain) LB_CHECK(realloc_buf(c.rf.wsrc, (size_t)(N - 1) * kWide * 4));
+      LB_CHECK(c.nodes4.ensure((size_t)(N - 1) * sizeof(WideNode)));  // <= one wide node per BVH2 node
+      if (retain) LB_CHECK(c.rf.wsrc.ensure((size_t)(N - 1) * kWide * 4));
       const uint2 root2 = make_uint2(0u, kNoHit);
       LB_CHECK(hipMemcpyAsync(cur, &root2, sizeof(root2), hipMemcpyHostToDevice, s));
       uint32_t ncur = 1u, base = 0u, levels = 0u;

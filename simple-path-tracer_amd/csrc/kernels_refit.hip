@@ -171,16 +171,6 @@ __global__ void __launch_bounds__(256) k_refit_wide(uint32_t nw, WideNode* nodes
   }
 }
 
-hipError_t rf_buf(DevBuf& b, size_t bytes) {
-  if (b.p && b.bytes >= bytes) return hipSuccess;
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.bytes = 0;
-  hipError_t e = hipMalloc(&b.p, bytes ? bytes : 16);
-  if (e == hipSuccess) b.bytes = bytes ? bytes : 16;
-  return e;
-}
-
 unsigned blocks_for(size_t n) {
   size_t b = (n + 255) / 256;
   if (b < 1) b = 1;
@@ -198,27 +188,18 @@ void launch_slots(Context& c, const float* d_pos, const float4* d_sph) {
 
 }  // namespace
 
-void refit_release(Context& c, bool events) {
+void refit_release(Context& c) {
   RefitState& r = c.rf;
-  for (DevBuf* b : {&r.idx, &r.box_lo, &r.box_hi, &r.order, &r.hoff, &r.wsrc, &r.in_pos, &r.in_sph}) {
-    if (b->p) (void)hipFree(b->p);
-    b->p = nullptr;
-    b->bytes = 0;
-  }
+  for (DevBuf* b : {&r.idx, &r.box_lo, &r.box_hi, &r.order, &r.hoff, &r.wsrc, &r.in_pos, &r.in_sph}) b->release();
   r.hoff_h.clear();
   r.valid = false;
-  if (events)
-    for (hipEvent_t& e : r.ev) {
-      if (e) (void)hipEventDestroy(e);
-      e = nullptr;
-    }
 }
 
 int refit_retain_slots(Context& c, const float* d_pos, const uint32_t* d_idx, const float4* d_sph) {
   const uint32_t n = c.num_tri_refs + c.num_sph;
-  RF_CHECK(rf_buf(c.rf.idx, (size_t)c.num_tri_refs * 12));
-  RF_CHECK(rf_buf(c.rf.box_lo, (size_t)n * 16));
-  RF_CHECK(rf_buf(c.rf.box_hi, (size_t)n * 16));
+  RF_CHECK(c.rf.idx.ensure((size_t)c.num_tri_refs * 12));
+  RF_CHECK(c.rf.box_lo.ensure((size_t)n * 16));
+  RF_CHECK(c.rf.box_hi.ensure((size_t)n * 16));
   if (c.num_tri_refs)
     hipLaunchKernelGGL(k_slot_indices, dim3(blocks_for(c.num_tri_refs)), dim3(256), 0, c.stream, c.num_tri_refs,
                        static_cast<const uint32_t*>(c.tri_orig.p), d_idx, static_cast<uint32_t*>(c.rf.idx.p));
@@ -237,8 +218,8 @@ int refit_lbvh(Context& c, const float* d_pos, const float4* d_sph) {
   const auto t0 = std::chrono::steady_clock::now();
   RefitState& r = c.rf;
   hipStream_t s = c.stream;
-  for (hipEvent_t& e : r.ev)
-    if (!e) RF_CHECK(hipEventCreate(&e));
+  for (DevEvent& e : r.ev)
+    if (!e) RF_CHECK(hipEventCreate(e.put()));
   BvhNode* nodes = static_cast<BvhNode*>(c.nodes.p);
   const float4 *blo = static_cast<const float4*>(r.box_lo.p), *bhi = static_cast<const float4*>(r.box_hi.p);
   RF_CHECK(hipEventRecord(r.ev[0], s));

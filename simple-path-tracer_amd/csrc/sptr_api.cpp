@@ -32,21 +32,25 @@ struct sptr_ctx {
   uint32_t lanes_req = 0;   // 0: automatic, 1: one chain, 2: two lanes
   bool lane_scene = false;  // the lane context holds this context's scene
   bool split = false;       // the current accumulation runs in two lanes
-  hipEvent_t lane_fork = nullptr, lane_join = nullptr;
+  sptr::DevEvent lane_fork, lane_join;
   sptr::DevBuf tiles_full;  // with split: this context's tiles, interleaved from the two lanes'
   uint32_t full_tiles = 0;
   int full_G = 1, full_R = 0;
+  // the triangle list's geomID offsets on the device, beside the scene they mirror (c.geom_first): k_aov
+  // and k_rayquery derive primIDs from them (ensure_geom_first; invalidated by sptr_upload_scene)
+  sptr::DevBuf geom_first;
+  bool geom_first_valid = false;
   // sptr_read_rgb8_lagged: two device snapshots of the RGB8 image, alternately written; a copy stream and
   // the registered host destination (created / registered on first use)
   struct Snap {
     sptr::DevBuf buf;
-    hipEvent_t ready = nullptr;
+    sptr::DevEvent ready;
     int W = 0, H = 0;
     bool valid = false;
   } snap[2];
   uint32_t snap_cur = 0;
-  hipStream_t copy_stream = nullptr;
-  hipEvent_t copy_done = nullptr;
+  sptr::DevStream copy_stream;
+  sptr::DevEvent copy_done;
   void* reg_ptr = nullptr;
   size_t reg_bytes = 0;
   // sptr_set_denoise / sptr_read_aov (the caller's context; a pixel lane holds none).  Everything is in
@@ -54,8 +58,7 @@ struct sptr_ctx {
   // ping-pong colour images and the second RGB8 image the readbacks return while the denoiser is on.
   struct Denoise {
     sptr_denoise_params p{};  // iterations 0: off
-    sptr::DevBuf nz, albedo, ids, geom_first, flag, col[2], image;
-    bool geom_first_valid = false;  // (sptr_upload_scene)
+    sptr::DevBuf nz, albedo, ids, flag, col[2], image;
     uint64_t aov_epoch = 0;
     sptr_camera aov_cam{};
     int aov_W = 0, aov_H = 0;
@@ -64,7 +67,7 @@ struct sptr_ctx {
     int last_W = 0, last_H = 0;
     bool ran = false;        // the last render call ran the pass: `image` and col[final] hold its result
     uint32_t final_col = 0;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // AOV begin / end, filter begin / end
+    sptr::DevEvent ev[4];                                     // AOV begin / end, filter begin / end
     bool aov_timed = false, filter_timed = false;             // ... recorded by the last pass
   } dn;
   // sptr_query_rays (the caller's context; a pixel lane holds none): scratch that grows on demand (sort keys
@@ -72,11 +75,25 @@ struct sptr_ctx {
   // staging of host-pointer queries) and the events of the last query, which may still run on a caller's stream
   struct RayQuery {
     sptr::DevBuf keys, index, keys_sorted, order, temp, flag, stage_in, stage_out;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};  // begin, after the sort, end
+    sptr::DevEvent ev[3];                            // begin, after the sort, end
     bool issued = false;                             // ev[0] and ev[2] (sorted: ev[1] too) are recorded
     bool sorted = false;
     uint32_t count = 0;
   } rq;
+  // Waits for everything that may still use this context's resources, then lets the lane go; the members
+  // free themselves after that (in reverse order of declaration: c, with its streams, last).
+  ~sptr_ctx() {
+    (void)hipSetDevice(c.device);
+    // this context's stream before the lane goes: after an asynchronous two-lane call it may still run
+    // k_interleave_tiles, which reads the lane's tiles
+    if (c.pending) (void)hipStreamSynchronize(c.pending_stream);
+    if (c.stream) (void)hipStreamSynchronize(c.stream);
+    if (copy_stream) (void)hipStreamSynchronize(copy_stream);  // the lagged readback's copy
+    // a query enqueued on a caller's stream (the caller synchronises it first; this costs nothing then)
+    if (rq.issued) (void)hipEventSynchronize(rq.ev[2]);
+    if (reg_ptr) (void)hipHostUnregister(reg_ptr);
+    delete lane;
+  }
 };
 
 namespace sptr {
@@ -93,22 +110,6 @@ int sync_pending(Context& c);
     hipError_t e_ = (x);                                                                    \
     if (e_ != hipSuccess) return fail(c, SPTR_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
   } while (0)
-
-hipError_t ensure_buf(DevBuf& b, size_t bytes) {
-  if (bytes == 0) bytes = 16;
-  if (b.p && b.bytes >= bytes) return hipSuccess;
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.bytes = 0;
-  hipError_t e = hipMalloc(&b.p, bytes);
-  if (e == hipSuccess) b.bytes = bytes;
-  return e;
-}
-void free_buf(DevBuf& b) {
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.bytes = 0;
-}
 
 // The context whose shading state (materials and their device table, the geomID -> material table,
 // lights, environment, debug mode) a render of c uses: a pixel lane reads its parent's (ADVICE r05:
@@ -156,16 +157,16 @@ int resolve_geom_materials(Context& c) {
     else m = (g < nm) ? g : g % nm;
     t[g] = m;
   }
-  API_HIP(ensure_buf(c.geom_mat, t.size() * 4));
+  API_HIP(c.geom_mat.ensure(t.size() * 4));
   API_HIP(hipMemcpy(c.geom_mat.p, t.data(), t.size() * 4, hipMemcpyHostToDevice));
   // scenes traversed from L2/HBM: the material of every triangle slot, so that shading a hit loads it
   // directly instead of the slot's geomID and then its material
 #ifndef SPTR_TRI_MAT
 #define SPTR_TRI_MAT 1
 #endif
-  free_buf(c.tri_mat);
+  c.tri_mat.release();
   if (SPTR_TRI_MAT && scene_view(c).lds_bytes == 0u && c.num_tri_refs) {
-    API_HIP(ensure_buf(c.tri_mat, (size_t)c.num_tri_refs * 4));
+    API_HIP(c.tri_mat.ensure((size_t)c.num_tri_refs * 4));
     launch_tri_materials(static_cast<const uint32_t*>(c.tri_geom.p), static_cast<const uint32_t*>(c.geom_mat.p),
                          c.num_tri_refs, static_cast<uint32_t*>(c.tri_mat.p), c.stream);
     API_HIP(hipGetLastError());
@@ -204,21 +205,21 @@ int ensure_wave(Context& c, uint64_t cap, uint32_t L, uint32_t ts, uint32_t k_sl
   if (grow && sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;  // pending renders may still use the old streams
   if (grow) ++c.epoch;
   if (!b.seg.p) {  // segment tables, per-block tallies and work counters, zeroed once
-    API_HIP(ensure_buf(b.seg, seg_table_bytes()));
+    API_HIP(b.seg.ensure(seg_table_bytes()));
     API_HIP(hipMemset(b.seg.p, 0, seg_table_bytes()));
   }
   // straggler records (k_trace_dyn -> k_strag, scenes beyond an XCD's L2): kStragCap per bounce
-  if (strag_applies(scene_view(c))) API_HIP(ensure_buf(b.strag, (size_t)kStragHandoffBounces * kStragCap * kStragRec * 16u));
-  API_HIP(ensure_buf(b.hrec, hrec_bytes));
+  if (strag_applies(scene_view(c))) API_HIP(b.strag.ensure((size_t)kStragHandoffBounces * kStragCap * kStragRec * 16u));
+  API_HIP(b.hrec.ensure(hrec_bytes));
   if (b.cap >= cap && b.L * b.ts >= L * ts && b.rad.p) return SPTR_OK;
   // Segmented streams: a stage with G blocks writes block b's outputs at [b*per, b*per + count)
   // with per = ceil(n / (G*kBlock)) * kBlock, so the segment space G*per can exceed n by up to
   // G*kBlock - 1 records: every segmented stream carries kMaxSegs*kBlock records of slack.
   const size_t n = (size_t)cap, ns = n + (size_t)kMaxSegs * kBlock;
   for (auto& r : b.rs)
-    for (DevBuf& x : r) API_HIP(ensure_buf(x, ns * 16));
-  API_HIP(ensure_buf(b.rad, n * 16));
-  API_HIP(ensure_buf(b.stask, ns * L * ts * 16));
+    for (DevBuf& x : r) API_HIP(x.ensure(ns * 16));
+  API_HIP(b.rad.ensure(n * 16));
+  API_HIP(b.stask.ensure(ns * L * ts * 16));
   b.cap = cap;
   b.L = L;
   b.ts = ts;
@@ -352,8 +353,8 @@ struct StageTimer {
   size_t call = SIZE_MAX;   // index in c.marks of this call's stage-0 span
   size_t alloc() {  // a pool event for this call (not recorded)
     if (c.events_used == c.events.size()) {
-      hipEvent_t e = nullptr;
-      const hipError_t r = hipEventCreate(&e);
+      DevEvent e;
+      const hipError_t r = hipEventCreate(e.put());
       if (r != hipSuccess) {
         if (err == hipSuccess) {
           err = r;
@@ -361,7 +362,7 @@ struct StageTimer {
         }
         return SIZE_MAX;
       }
-      c.events.push_back(e);
+      c.events.push_back(std::move(e));
     }
     return c.events_used++;
   }
@@ -641,11 +642,11 @@ int ensure_pixels(Context& c, int W, int H, int G, int R, hipStream_t s, bool& r
   c.R = R;
   c.local_tiles = local_tiles;
   c.P = local_tiles * (uint32_t)kTilePixels;
-  API_HIP(ensure_buf(c.accum, (size_t)c.P * 16));
-  API_HIP(ensure_buf(c.tiles, (size_t)c.P * 4));
-  API_HIP(ensure_buf(c.image, (size_t)W * H * 3));
-  API_HIP(ensure_buf(c.cull, (size_t)c.P / 32u * 4u + 4u));
-  API_HIP(ensure_buf(c.plist, ((size_t)c.P + 2u) * 4u));
+  API_HIP(c.accum.ensure((size_t)c.P * 16));
+  API_HIP(c.tiles.ensure((size_t)c.P * 4));
+  API_HIP(c.image.ensure((size_t)W * H * 3));
+  API_HIP(c.cull.ensure((size_t)c.P / 32u * 4u + 4u));
+  API_HIP(c.plist.ensure(((size_t)c.P + 2u) * 4u));
   ++c.epoch;
   API_HIP(hipMemsetAsync(c.accum.p, 0, (size_t)c.P * 16, s));
   API_HIP(hipMemsetAsync(c.tiles.p, 0, (size_t)c.P * 4, s));
@@ -1070,12 +1071,6 @@ bool check_graph(hipGraph_t g, GraphShape& out, std::string& why) {
   return true;
 }
 
-void drop_graph(Context& c) {
-  if (c.graph.exec) (void)hipGraphExecDestroy(c.graph.exec);
-  if (c.graph.graph) (void)hipGraphDestroy(c.graph.graph);
-  c.graph = GraphCache{};
-}
-
 // Enqueue one render call's launch sequence on s.  A call shape seen twice in a row is captured
 // once into a hipGraph (on the context's capture stream) and replayed from then on: one graph
 // launch instead of ~20 kernel launches, with the per-call values (frame_begin, reset, total) passed
@@ -1124,14 +1119,14 @@ int run_call(Context& c, const GraphKey& key, uint32_t frame_begin, uint32_t res
   };
   if (!graphable || timing || bad || !(repeat || (c.graph.valid && same_key(key, c.graph.key)))) return direct();
   if (!(c.graph.valid && same_key(key, c.graph.key))) {  // capture this shape
-    drop_graph(c);
+    c.graph.exec.reset();  // (before its graph)
+    c.graph = GraphCache{};
     // a pixel lane's capture stream is its own, created on its first capture (only launch mode 3 captures
     // a lane's calls).  r06: with one capture stream shared by the two contexts, a parent's capture after
     // the lane's (a mode-3 two-lane shape, then direct two-lane calls, then a one-chain shape captured in
     // mode 0) was instantiated, and its first hipGraphLaunch faulted inside torch's HIP runtime (a null
     // member read at libamdhip64+0xaee41, gpurun_out/r06e); with a stream per context it does not.
-    if (!c.cap_stream && hipStreamCreateWithFlags(&c.cap_stream, hipStreamNonBlocking) != hipSuccess) {
-      c.cap_stream = nullptr;
+    if (!c.cap_stream && hipStreamCreateWithFlags(c.cap_stream.put(), hipStreamNonBlocking) != hipSuccess) {
       (void)hipGetLastError();
       return direct();
     }
@@ -1153,40 +1148,31 @@ int run_call(Context& c, const GraphKey& key, uint32_t frame_begin, uint32_t res
     StageTimer tm{c, false, false, c.cap_stream};
     tm.capturing = true;
     const uint32_t nw = enqueue(c.cap_stream, tm);
-    hipGraph_t g = nullptr;
-    const hipError_t ec = hipStreamEndCapture(c.cap_stream, &g);
+    GraphCache gc;
+    DevGraph& g = gc.graph;  // (dropped with gc on every path that does not keep it)
+    const hipError_t ec = hipStreamEndCapture(c.cap_stream, g.put());
     // every stream the capture forked must have left capture mode with it (a stream still capturing
     // would fold the next direct launches into a dead graph): end the capture on any that did not
     bool stuck = false;
-    for (hipStream_t st : {c.cap_stream, c.cap_side, c.cap_side2}) {
+    for (hipStream_t st : std::initializer_list<hipStream_t>{c.cap_stream, c.cap_side, c.cap_side2}) {
       if (!st) continue;
       hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
       if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
         stuck = true;
-        hipGraph_t gs = nullptr;
-        (void)hipStreamEndCapture(st, &gs);
-        if (gs) (void)hipGraphDestroy(gs);
+        DevGraph gs;
+        (void)hipStreamEndCapture(st, gs.put());
       }
     }
-    if (stuck) {
-      if (g) (void)hipGraphDestroy(g);
+    if (stuck)
       return not_capturable(hipErrorStreamCaptureUnjoined, "graph capture: a forked stream was still capturing");
-    }
-    if (ec != hipSuccess || tm.err != hipSuccess || !g) {
-      if (g) (void)hipGraphDestroy(g);
+    if (ec != hipSuccess || tm.err != hipSuccess || !g)
       return not_capturable(ec != hipSuccess ? ec : tm.err,
                             ec != hipSuccess ? std::string("hipStreamEndCapture: ") + hipGetErrorString(ec)
                                              : tm.what + ": " + hipGetErrorString(tm.err));
-    }
     {
       std::string why;
-      if (!check_graph(g, gshape, why)) {
-        (void)hipGraphDestroy(g);
-        return not_capturable(hipErrorInvalidValue, "captured graph rejected: " + why);
-      }
+      if (!check_graph(g, gshape, why)) return not_capturable(hipErrorInvalidValue, "captured graph rejected: " + why);
     }
-    GraphCache gc;
-    gc.graph = g;
     gc.key = key;
     gc.waves = nw;
     gc.nodes = gshape.nodes + 1;  // + the k_frame_dyn head added below, ahead of every root
@@ -1212,13 +1198,10 @@ int run_call(Context& c, const GraphKey& key, uint32_t frame_begin, uint32_t res
     for (hipGraphNode_t r : roots) API_HIP(hipGraphAddDependencies(g, &gc.dyn_node, &r, 1));
     gc.edges = gshape.edges + (uint32_t)nr;
     gc.dyn_params = kp;
-    const hipError_t ei = hipGraphInstantiate(&gc.exec, g, nullptr, nullptr, 0);
-    if (ei != hipSuccess) {
-      (void)hipGraphDestroy(g);
-      return not_capturable(ei, std::string("hipGraphInstantiate: ") + hipGetErrorString(ei));
-    }
+    const hipError_t ei = hipGraphInstantiate(gc.exec.put(), g, nullptr, nullptr, 0);
+    if (ei != hipSuccess) return not_capturable(ei, std::string("hipGraphInstantiate: ") + hipGetErrorString(ei));
     gc.valid = true;
-    c.graph = gc;
+    c.graph = std::move(gc);
     ++c.captures;
   }
   // replay: the call's values into the k_frame_dyn node, the call span around the launch
@@ -1246,17 +1229,12 @@ int run_call(Context& c, const GraphKey& key, uint32_t frame_begin, uint32_t res
 
 namespace sptr {
 namespace {
-std::vector<hipEvent_t*> dep_events(Context& c) {
-  std::vector<hipEvent_t*> v;
-  for (Context::DepEvents& d : c.dev)
-    for (hipEvent_t* e : {&d.fork, &d.join, &d.sky}) v.push_back(e);
-  return v;
-}
 bool create_events(Context& c) {
-  for (hipEvent_t* e : dep_events(c))
-    if (hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) return false;
-  for (hipEvent_t& e : c.quiet_ev)
-    if (hipEventCreate(&e) != hipSuccess) return false;
+  for (Context::DepEvents& d : c.dev)
+    for (DevEvent* e : {&d.fork, &d.join, &d.sky})
+      if (hipEventCreateWithFlags(e->put(), hipEventDisableTiming) != hipSuccess) return false;
+  for (DevEvent& e : c.quiet_ev)
+    if (hipEventCreate(e.put()) != hipSuccess) return false;
   return true;
 }
 }  // namespace
@@ -1352,8 +1330,8 @@ int sptr_create(int device, sptr_ctx** out) {
   if (create_one(device, &x->lane, x) != SPTR_OK) x->lane = nullptr;
   if (x->lane) {
     x->lane->is_lane = true;
-    if (hipEventCreateWithFlags(&x->lane_fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&x->lane_join, hipEventDisableTiming) != hipSuccess) {
+    if (hipEventCreateWithFlags(x->lane_fork.put(), hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(x->lane_join.put(), hipEventDisableTiming) != hipSuccess) {
       (void)sptr_destroy(x);
       *out = nullptr;
       return SPTR_ERR_HIP;
@@ -1362,8 +1340,8 @@ int sptr_create(int device, sptr_ctx** out) {
   return SPTR_OK;
 }
 
-// parent: a pixel lane's context.  It creates no stream here: it borrows the parent's capture stream
-// (captures run one at a time on the calling thread), gets its render stream when it is given a scene
+// parent: a pixel lane's context.  It creates no stream here: it makes its own capture stream on its
+// first capture (run_call), gets its render stream when it is given a scene
 // (sptr_upload_scene) and has no side streams (it renders only scenes staged into LDS, whose launches
 // run on one stream).  r05zw: every stream a context creates is one more for the runtime to place on
 // the process's hardware queues, and a lane created with a full set of six slowed the parent's
@@ -1386,24 +1364,24 @@ static int create_one(int device, sptr_ctx** out, const sptr_ctx* parent) {
       delete x;
       return SPTR_ERR_HIP;
     }
-  } else if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking) != hipSuccess ||
-      hipStreamCreateWithFlags(&c.cap_stream, hipStreamNonBlocking) != hipSuccess ||
+  } else if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(c.stream.put(), hipStreamNonBlocking) != hipSuccess ||
+      hipStreamCreateWithFlags(c.cap_stream.put(), hipStreamNonBlocking) != hipSuccess ||
       // the side streams at the lowest priority: a priority of its own puts a stream on a hardware
       // queue of its own, so that its launches can run beside the main sequence's.  (r05t: the main
       // streams at the highest priority instead of the default changed nothing, C3 and C5.)
       hipDeviceGetStreamPriorityRange(&c.prio_lo, &c.prio_hi) != hipSuccess ||
-      hipStreamCreateWithPriority(&c.side_stream, hipStreamNonBlocking, c.prio_lo) != hipSuccess ||
-      hipStreamCreateWithPriority(&c.cap_side, hipStreamNonBlocking, c.prio_lo) != hipSuccess ||
-      hipStreamCreateWithPriority(&c.side2_stream, hipStreamNonBlocking, c.prio_lo) != hipSuccess ||
-      hipStreamCreateWithPriority(&c.cap_side2, hipStreamNonBlocking, c.prio_lo) != hipSuccess ||
+      hipStreamCreateWithPriority(c.side_stream.put(), hipStreamNonBlocking, c.prio_lo) != hipSuccess ||
+      hipStreamCreateWithPriority(c.cap_side.put(), hipStreamNonBlocking, c.prio_lo) != hipSuccess ||
+      hipStreamCreateWithPriority(c.side2_stream.put(), hipStreamNonBlocking, c.prio_lo) != hipSuccess ||
+      hipStreamCreateWithPriority(c.cap_side2.put(), hipStreamNonBlocking, c.prio_lo) != hipSuccess ||
       !create_events(c)) {
     delete x;
     return SPTR_ERR_HIP;
   }
   int khz = 0;
-  if (ensure_buf(c.wb.seg, seg_table_bytes()) != hipSuccess || ensure_buf(c.w_tot, kTotWords * 8) != hipSuccess ||
-      ensure_buf(c.dyn, kDynBytes) != hipSuccess || hipMemset(c.wb.seg.p, 0, seg_table_bytes()) != hipSuccess ||
-      ensure_buf(c.tslots, (size_t)kTimeSlots * kTimeSlotWords * 8) != hipSuccess ||
+  if (c.wb.seg.ensure(seg_table_bytes()) != hipSuccess || c.w_tot.ensure(kTotWords * 8) != hipSuccess ||
+      c.dyn.ensure(kDynBytes) != hipSuccess || hipMemset(c.wb.seg.p, 0, seg_table_bytes()) != hipSuccess ||
+      c.tslots.ensure((size_t)kTimeSlots * kTimeSlotWords * 8) != hipSuccess ||
       hipMemset(c.tslots.p, 0, (size_t)kTimeSlots * kTimeSlotWords * 8) != hipSuccess ||
       hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device) != hipSuccess || khz <= 0) {
     delete x;
@@ -1416,64 +1394,7 @@ static int create_one(int device, sptr_ctx** out, const sptr_ctx* parent) {
 
 int sptr_destroy(sptr_ctx* x) {
   if (!x) return SPTR_ERR_INVALID;
-  // this context's stream first: after an asynchronous two-lane call it may still run
-  // k_interleave_tiles, which reads the lane's tiles
-  (void)hipSetDevice(x->c.device);
-  if (x->c.pending) (void)hipStreamSynchronize(x->c.pending_stream);
-  if (x->c.stream) (void)hipStreamSynchronize(x->c.stream);
-  if (x->copy_stream) {  // the lagged readback's copy stream, snapshots and registered destination
-    (void)hipStreamSynchronize(x->copy_stream);
-    (void)hipStreamDestroy(x->copy_stream);
-  }
-  if (x->copy_done) (void)hipEventDestroy(x->copy_done);
-  for (auto& sn : x->snap) {
-    free_buf(sn.buf);
-    if (sn.ready) (void)hipEventDestroy(sn.ready);
-  }
-  if (x->reg_ptr) (void)hipHostUnregister(x->reg_ptr);
-  if (x->lane) (void)sptr_destroy(x->lane);
-  x->lane = nullptr;
-  for (hipEvent_t e : {x->lane_fork, x->lane_join})
-    if (e) (void)hipEventDestroy(e);
-  free_buf(x->tiles_full);
-  for (DevBuf* b : {&x->dn.nz, &x->dn.albedo, &x->dn.ids, &x->dn.geom_first, &x->dn.flag, &x->dn.col[0], &x->dn.col[1],
-                    &x->dn.image})
-    free_buf(*b);
-  for (hipEvent_t e : x->dn.ev)
-    if (e) (void)hipEventDestroy(e);
-  // a query enqueued on a caller's stream (the caller synchronises it first; this costs nothing then)
-  if (x->rq.issued) (void)hipEventSynchronize(x->rq.ev[2]);
-  for (DevBuf* b : {&x->rq.keys, &x->rq.index, &x->rq.keys_sorted, &x->rq.order, &x->rq.temp, &x->rq.flag,
-                    &x->rq.stage_in, &x->rq.stage_out})
-    free_buf(*b);
-  for (hipEvent_t e : x->rq.ev)
-    if (e) (void)hipEventDestroy(e);
-  Context& c = x->c;
-  (void)hipSetDevice(c.device);
-  if (c.pending) (void)hipStreamSynchronize(c.pending_stream);
-  if (c.stream) (void)hipStreamSynchronize(c.stream);
-  DevBuf* bufs[] = {&c.nodes,  &c.prim_ref, &c.tris,  &c.sph,   &c.tri_geom, &c.sph_geom, &c.tri_orig,
-                    &c.sph_orig, &c.geom_mat, &c.tri_mat, &c.mats, &c.env, &c.w_tot,  &c.accum,   &c.tiles,
-                    &c.image,    &c.qbuf,     &c.nodes4, &c.cull, &c.plist, &c.tslots};
-  for (DevBuf* b : bufs) free_buf(*b);
-  for (DevBuf* b : {&c.wb.hrec, &c.wb.rad, &c.wb.stask, &c.wb.seg, &c.wb.strag}) free_buf(*b);
-  for (auto& r : c.wb.rs)
-    for (DevBuf& x : r) free_buf(x);
-  for (hipStream_t st : {c.side2_stream, c.cap_side2})
-    if (st) (void)hipStreamDestroy(st);
-  drop_graph(c);
-  free_buf(c.dyn);
-  refit_release(c, true);
-  for (hipEvent_t e : c.events) (void)hipEventDestroy(e);
-  if (c.stream) (void)hipStreamDestroy(c.stream);
-  if (c.cap_stream) (void)hipStreamDestroy(c.cap_stream);
-  if (c.side_stream) (void)hipStreamDestroy(c.side_stream);
-  if (c.cap_side) (void)hipStreamDestroy(c.cap_side);
-  for (hipEvent_t* e : dep_events(c))
-    if (*e) (void)hipEventDestroy(*e);
-  for (hipEvent_t e : c.quiet_ev)
-    if (e) (void)hipEventDestroy(e);
-  delete x;
+  delete x;  // (~sptr_ctx waits for the context's work first)
   return SPTR_OK;
 }
 
@@ -1607,7 +1528,7 @@ static int set_materials_one(sptr_ctx* x, const sptr_material* m, uint32_t n) {
   API_HIP(hipSetDevice(c.device));
   c.mats_host.resize(n);
   std::memcpy(c.mats_host.data(), m, sizeof(DevMaterial) * n);
-  API_HIP(ensure_buf(c.mats, sizeof(DevMaterial) * n));
+  API_HIP(c.mats.ensure(sizeof(DevMaterial) * n));
   API_HIP(hipMemcpy(c.mats.p, c.mats_host.data(), sizeof(DevMaterial) * n, hipMemcpyHostToDevice));
   ++c.epoch;
   return resolve_geom_materials(c);
@@ -1643,7 +1564,7 @@ static int set_environment_one(sptr_ctx* x, const sptr_environment* e) {
   if (sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;  // a pending render may still read the old state
   API_HIP(hipSetDevice(c.device));
   if (!e || !e->faces) {
-    free_buf(c.env);
+    c.env.release();
     ++c.epoch;
     c.env_size = 0;
     if (e) {
@@ -1661,7 +1582,7 @@ static int set_environment_one(sptr_ctx* x, const sptr_environment* e) {
     tmp[i * 4 + 2] = e->faces[i * 3 + 2];
     tmp[i * 4 + 3] = 0.0f;
   }
-  API_HIP(ensure_buf(c.env, texels * 16));
+  API_HIP(c.env.ensure(texels * 16));
   API_HIP(hipMemcpy(c.env.p, tmp.data(), texels * 16, hipMemcpyHostToDevice));
   c.env_size = e->size;
   ++c.epoch;
@@ -1807,24 +1728,16 @@ int sptr_overlap_probe(sptr_ctx* x, double* ms) {
   API_HIP(hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, c.device));
   if (rate_khz <= 0) return fail(c, SPTR_ERR_HIP, "overlap probe: no wall clock rate");
   const uint64_t ticks = (uint64_t)rate_khz / 5u;  // 200 us per spin
-  // the events are destroyed on every exit path (Probe's destructor)
-  struct Probe {
-    hipEvent_t e0 = nullptr, e1 = nullptr, fk = nullptr, jn = nullptr;
-    ~Probe() {
-      for (hipEvent_t e : {e0, e1, fk, jn})
-        if (e) (void)hipEventDestroy(e);
-    }
-  } pe;
+  DevEvent e0, e1, fk, jn;
   hipError_t err = hipSuccess;
   auto ck = [&](hipError_t e) {
     if (e != hipSuccess && err == hipSuccess) err = e;
   };
-  ck(hipEventCreate(&pe.e0));
-  ck(hipEventCreate(&pe.e1));
-  ck(hipEventCreateWithFlags(&pe.fk, hipEventDisableTiming));
-  ck(hipEventCreateWithFlags(&pe.jn, hipEventDisableTiming));
+  ck(hipEventCreate(e0.put()));
+  ck(hipEventCreate(e1.put()));
+  ck(hipEventCreateWithFlags(fk.put(), hipEventDisableTiming));
+  ck(hipEventCreateWithFlags(jn.put(), hipEventDisableTiming));
   if (err != hipSuccess) return fail(c, SPTR_ERR_HIP, std::string("overlap probe: ") + hipGetErrorString(err));
-  hipEvent_t e0 = pe.e0, e1 = pe.e1, fk = pe.fk, jn = pe.jn;
   const hipStream_t s = c.stream;
   launch_spin(ticks / 8u, s);  // warm the kernel
   ck(hipStreamSynchronize(s));
@@ -1900,9 +1813,9 @@ int sptr_read_rgb8_lagged(sptr_ctx* x, uint8_t* rgb, uint32_t* got) {
   API_HIP(hipSetDevice(c.device));
   if (!x->copy_stream) {
     // a priority of its own (the lowest): its own hardware queue, apart from the render stream's
-    API_HIP(hipStreamCreateWithPriority(&x->copy_stream, hipStreamNonBlocking, c.prio_lo));
-    API_HIP(hipEventCreateWithFlags(&x->copy_done, hipEventDisableTiming));
-    for (auto& sn : x->snap) API_HIP(hipEventCreateWithFlags(&sn.ready, hipEventDisableTiming));
+    API_HIP(hipStreamCreateWithPriority(x->copy_stream.put(), hipStreamNonBlocking, c.prio_lo));
+    API_HIP(hipEventCreateWithFlags(x->copy_done.put(), hipEventDisableTiming));
+    for (auto& sn : x->snap) API_HIP(hipEventCreateWithFlags(sn.ready.put(), hipEventDisableTiming));
   }
   const size_t bytes = (size_t)c.W * c.H * 3;
   auto& cur = x->snap[x->snap_cur];
@@ -1910,7 +1823,7 @@ int sptr_read_rgb8_lagged(sptr_ctx* x, uint8_t* rgb, uint32_t* got) {
   // this call's image, snapshotted on its stream after it (with two lanes, the lane's resolve into this
   // image is joined into that stream before the call's last launch).  The slot's last reader was the copy
   // two calls back, which that call waited for.
-  API_HIP(ensure_buf(cur.buf, bytes));
+  API_HIP(cur.buf.ensure(bytes));
   API_HIP(hipMemcpyAsync(cur.buf.p, x->dn.ran ? x->dn.image.p : c.image.p, bytes, hipMemcpyDeviceToDevice, c.pending_stream));
   API_HIP(hipEventRecord(cur.ready, c.pending_stream));
   if (prev.valid && prev.W == c.W && prev.H == c.H) {
@@ -2005,7 +1918,7 @@ static int run_query(sptr_ctx* x, const float* rays, uint32_t n, bool anyhit, ui
   if (n == 0) return SPTR_OK;
   API_HIP(hipSetDevice(c.device));
   const size_t rb = (size_t)n * 32, refb = (size_t)n * 4, tb = (size_t)n * 4, nb = (size_t)n * 12, ob = (size_t)n;
-  API_HIP(ensure_buf(c.qbuf, rb + refb + tb + nb + ob + 64));
+  API_HIP(c.qbuf.ensure(rb + refb + tb + nb + ob + 64));
   char* base = static_cast<char*>(c.qbuf.p);
   uint32_t* d_sflag = reinterpret_cast<uint32_t*>(base + (rb + refb + tb + nb + ob + 15) / 16 * 16);
   float* d_rays = reinterpret_cast<float*>(base);
@@ -2069,13 +1982,12 @@ static bool query_sorts_by_default(const SceneView&, uint32_t) { return false; }
 // the triangle list's geomID offsets on the device (k_aov and k_rayquery derive primIDs from them)
 static int ensure_geom_first(sptr_ctx* x) {
   Context& c = x->c;
-  auto& d = x->dn;
-  if (d.geom_first_valid) return SPTR_OK;
+  if (x->geom_first_valid) return SPTR_OK;
   if (sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;
-  API_HIP(ensure_buf(d.geom_first, (c.geom_first.size() + 1) * 4));
+  API_HIP(x->geom_first.ensure((c.geom_first.size() + 1) * 4));
   if (!c.geom_first.empty())
-    API_HIP(hipMemcpy(d.geom_first.p, c.geom_first.data(), c.geom_first.size() * 4, hipMemcpyHostToDevice));
-  d.geom_first_valid = true;
+    API_HIP(hipMemcpy(x->geom_first.p, c.geom_first.data(), c.geom_first.size() * 4, hipMemcpyHostToDevice));
+  x->geom_first_valid = true;
   return SPTR_OK;
 }
 
@@ -2105,10 +2017,10 @@ static int enqueue_query(sptr_ctx* x, const sptr_ray_query& q, hipStream_t s) {
   const bool any = (q.flags & SPTR_QUERY_ANY_HIT) != 0u;
   const bool sort = (q.flags & SPTR_QUERY_SORT) != 0u ||
                     ((q.flags & SPTR_QUERY_NO_SORT) == 0u && sv.lds_bytes == 0u && query_sorts_by_default(sv, q.n));
-  for (hipEvent_t& e : rq.ev)
-    if (!e) API_HIP(hipEventCreate(&e));
+  for (DevEvent& e : rq.ev)
+    if (!e) API_HIP(hipEventCreate(e.put()));
   if (!rq.flag.p) {
-    API_HIP(ensure_buf(rq.flag, 16));
+    API_HIP(rq.flag.ensure(16));
     API_HIP(hipMemset(rq.flag.p, 0, 16));
   }
   const int rg = ensure_geom_first(x);
@@ -2121,11 +2033,11 @@ static int enqueue_query(sptr_ctx* x, const sptr_ray_query& q, hipStream_t s) {
         rq.temp.bytes < temp_bytes) {
       const int rw = query_wait(x);  // an enqueued query may still use the old scratch
       if (rw != SPTR_OK) return rw;
-      API_HIP(ensure_buf(rq.keys, kb));
-      API_HIP(ensure_buf(rq.keys_sorted, kb));
-      API_HIP(ensure_buf(rq.index, ib));
-      API_HIP(ensure_buf(rq.order, ib));
-      API_HIP(ensure_buf(rq.temp, temp_bytes));
+      API_HIP(rq.keys.ensure(kb));
+      API_HIP(rq.keys_sorted.ensure(kb));
+      API_HIP(rq.index.ensure(ib));
+      API_HIP(rq.order.ensure(ib));
+      API_HIP(rq.temp.ensure(temp_bytes));
     }
   }
   RayQueryView v{};
@@ -2141,7 +2053,7 @@ static int enqueue_query(sptr_ctx* x, const sptr_ray_query& q, hipStream_t s) {
     v.uv = q.uv;
   }
   v.tri_orig = static_cast<const uint32_t*>(c.tri_orig.p);
-  v.geom_first = static_cast<const uint32_t*>(x->dn.geom_first.p);
+  v.geom_first = static_cast<const uint32_t*>(x->geom_first.p);
   v.stack_overflow = static_cast<uint32_t*>(rq.flag.p);
   API_HIP(hipEventRecord(rq.ev[0], s));
   if (sort) {
@@ -2190,8 +2102,8 @@ int sptr_query_rays(sptr_ctx* x, const sptr_ray_query* q, void* stream) {
   const size_t off_prim = n * 4, off_t = n * 8, off_ng = n * 12, off_uv = n * 24, off_occ = n * 32;
   if (!dev) {
     auto& rq = x->rq;
-    API_HIP(ensure_buf(rq.stage_in, n * 32));
-    API_HIP(ensure_buf(rq.stage_out, n * 33));
+    API_HIP(rq.stage_in.ensure(n * 32));
+    API_HIP(rq.stage_out.ensure(n * 33));
     API_HIP(hipMemcpy(rq.stage_in.p, q->rays, n * 32, hipMemcpyHostToDevice));
     char* o = static_cast<char*>(rq.stage_out.p);
     d.rays = static_cast<const float*>(rq.stage_in.p);
@@ -2258,7 +2170,7 @@ int sptr_primary_rays(sptr_ctx* x, const sptr_camera* cam, int32_t W, int32_t H,
   f.max_depth = 1;
   FrameView fv = frame_view(c, f);
   const size_t n = (size_t)W * H;
-  API_HIP(ensure_buf(c.qbuf, n * 16 + 64));
+  API_HIP(c.qbuf.ensure(n * 16 + 64));
   float* d_dirs = static_cast<float*>(c.qbuf.p);
   uint32_t* d_rng = reinterpret_cast<uint32_t*>(static_cast<char*>(c.qbuf.p) + n * 12);
   launch_primary(fv, d_dirs, d_rng, c.stream);
@@ -2269,41 +2181,28 @@ int sptr_primary_rays(sptr_ctx* x, const sptr_camera* cam, int32_t W, int32_t H,
   return SPTR_OK;
 }
 
-// scratch of the primitive tests: freed on every exit path
-struct DevScratch {
-  std::vector<void*> p;
-  ~DevScratch() {
-    for (void* q : p) (void)hipFree(q);
-  }
-  hipError_t alloc(void** q, size_t bytes) {
-    *q = nullptr;
-    const hipError_t e = hipMalloc(q, bytes ? bytes : 16);
-    if (e == hipSuccess) p.push_back(*q);
-    return e;
-  }
-};
-
 int sptr_sort_pairs_u64(sptr_ctx* x, const uint64_t* keys, const uint32_t* vals, uint32_t n, uint64_t* keys_out,
                         uint32_t* vals_out) {
   if (!x || (n && (!keys || !vals || !keys_out || !vals_out))) return SPTR_ERR_INVALID;
   Context& c = x->c;
   if (sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;
   API_HIP(hipSetDevice(c.device));
-  DevScratch d;
-  void *ki = nullptr, *ko = nullptr, *vi = nullptr, *vo = nullptr, *tmp = nullptr;
+  DevTemps d;
+  uint64_t *ki = nullptr, *ko = nullptr;
+  uint32_t *vi = nullptr, *vo = nullptr;
+  char* tmp = nullptr;
   size_t tb = 0;
   API_HIP(radix_sort_pairs_u64(nullptr, tb, nullptr, nullptr, nullptr, nullptr, n, c.stream));
-  API_HIP(d.alloc(&ki, (size_t)n * 8));
-  API_HIP(d.alloc(&ko, (size_t)n * 8));
-  API_HIP(d.alloc(&vi, (size_t)n * 4));
-  API_HIP(d.alloc(&vo, (size_t)n * 4));
+  API_HIP(d.alloc(&ki, n));
+  API_HIP(d.alloc(&ko, n));
+  API_HIP(d.alloc(&vi, n));
+  API_HIP(d.alloc(&vo, n));
   API_HIP(d.alloc(&tmp, tb));
   if (n) {
     API_HIP(hipMemcpy(ki, keys, (size_t)n * 8, hipMemcpyHostToDevice));
     API_HIP(hipMemcpy(vi, vals, (size_t)n * 4, hipMemcpyHostToDevice));
   }
-  API_HIP(radix_sort_pairs_u64(tmp, tb, static_cast<const uint64_t*>(ki), static_cast<uint64_t*>(ko),
-                               static_cast<const uint32_t*>(vi), static_cast<uint32_t*>(vo), n, c.stream));
+  API_HIP(radix_sort_pairs_u64(tmp, tb, ki, ko, vi, vo, n, c.stream));
   API_HIP(hipStreamSynchronize(c.stream));
   if (n) {
     API_HIP(hipMemcpy(keys_out, ko, (size_t)n * 8, hipMemcpyDeviceToHost));
@@ -2320,12 +2219,12 @@ int sptr_eval_math(sptr_ctx* x, int fn, const float* in, uint32_t n, float* out)
   API_HIP(hipSetDevice(c.device));
   const uint32_t m = fn == SPTR_MATH_COSINE_SINCOS ? (1u << 24) : n;
   const size_t out_n = fn == SPTR_MATH_COSINE_SINCOS ? 2u * (size_t)m : (size_t)m;
-  DevScratch d;
-  void *di = nullptr, *dout = nullptr;
-  API_HIP(d.alloc(&di, fn == SPTR_MATH_GAMMA ? (size_t)n * 4 : 16));
-  API_HIP(d.alloc(&dout, out_n * 4));
+  DevTemps d;
+  float *di = nullptr, *dout = nullptr;
+  API_HIP(d.alloc(&di, fn == SPTR_MATH_GAMMA ? (size_t)n : 4));
+  API_HIP(d.alloc(&dout, out_n));
   if (fn == SPTR_MATH_GAMMA && n) API_HIP(hipMemcpy(di, in, (size_t)n * 4, hipMemcpyHostToDevice));
-  if (m) launch_eval_math(fn, static_cast<const float*>(di), m, static_cast<float*>(dout), c.stream);
+  if (m) launch_eval_math(fn, di, m, dout, c.stream);
   API_HIP(hipGetLastError());
   API_HIP(hipStreamSynchronize(c.stream));
   if (out_n) API_HIP(hipMemcpy(out, dout, out_n * 4, hipMemcpyDeviceToHost));
@@ -2337,15 +2236,16 @@ int sptr_scan_u32(sptr_ctx* x, const uint32_t* in, uint32_t n, uint32_t* out) {
   Context& c = x->c;
   if (sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;
   API_HIP(hipSetDevice(c.device));
-  DevScratch d;
-  void *di = nullptr, *dout = nullptr, *tmp = nullptr;
+  DevTemps d;
+  uint32_t *di = nullptr, *dout = nullptr;
+  char* tmp = nullptr;
   size_t tb = 0;
   API_HIP(scan_u32(nullptr, tb, nullptr, nullptr, n, c.stream));
-  API_HIP(d.alloc(&di, (size_t)n * 4));
-  API_HIP(d.alloc(&dout, (size_t)n * 4));
+  API_HIP(d.alloc(&di, n));
+  API_HIP(d.alloc(&dout, n));
   API_HIP(d.alloc(&tmp, tb));
   if (n) API_HIP(hipMemcpy(di, in, (size_t)n * 4, hipMemcpyHostToDevice));
-  API_HIP(scan_u32(tmp, tb, static_cast<const uint32_t*>(di), static_cast<uint32_t*>(dout), n, c.stream));
+  API_HIP(scan_u32(tmp, tb, di, dout, n, c.stream));
   API_HIP(hipStreamSynchronize(c.stream));
   if (n) API_HIP(hipMemcpy(out, dout, (size_t)n * 4, hipMemcpyDeviceToHost));
   return SPTR_OK;
@@ -2362,7 +2262,7 @@ static int lane_forward(sptr_ctx* x, int rc_lane) {
 int sptr_upload_scene(sptr_ctx* x, const sptr_scene* s) {
   const int rc = upload_scene_one(x, s);
   if (rc != SPTR_OK) return rc;
-  x->dn.geom_first_valid = false;
+  x->geom_first_valid = false;
   if (x->split) x->c.W = 0;  // the pixel buffers describe the even lane: re-laid out for the next call
   x->split = false;
   x->lane_scene = false;
@@ -2374,10 +2274,8 @@ int sptr_upload_scene(sptr_ctx* x, const sptr_scene* s) {
     // (a priority of its own puts the lane's stream on a hardware queue apart from the render stream's:
     // created at the default priority it shared that queue and the two chains ran one after the other,
     // r05zx, C2 3.24 ms; at the lowest priority, the side streams', 2.56-2.58; at the highest 2.67-2.69)
-    if (!cy.stream && hipStreamCreateWithPriority(&cy.stream, hipStreamNonBlocking, x->c.prio_lo) != hipSuccess) {
-      cy.stream = nullptr;
+    if (!cy.stream && hipStreamCreateWithPriority(cy.stream.put(), hipStreamNonBlocking, x->c.prio_lo) != hipSuccess)
       return fail(x->c, SPTR_ERR_HIP, "pixel lane: stream creation failed");
-    }
     const int r1 = upload_scene_one(x->lane, s);
     if (r1 != SPTR_OK) return lane_forward(x, r1);
     x->lane_scene = true;
@@ -2420,12 +2318,12 @@ int sptr_update_geometry(sptr_ctx* x, const float* positions, uint32_t num_verts
   const float *d_pos = positions, *d_sph = spheres;
   if (!(flags & SPTR_UPDATE_DEVICE_PTRS)) {
     if (positions) {
-      API_HIP(ensure_buf(c.rf.in_pos, (size_t)num_verts * 12));
+      API_HIP(c.rf.in_pos.ensure((size_t)num_verts * 12));
       API_HIP(hipMemcpyAsync(c.rf.in_pos.p, positions, (size_t)num_verts * 12, hipMemcpyHostToDevice, c.stream));
       d_pos = static_cast<const float*>(c.rf.in_pos.p);
     }
     if (spheres) {
-      API_HIP(ensure_buf(c.rf.in_sph, (size_t)num_spheres * 16));
+      API_HIP(c.rf.in_sph.ensure((size_t)num_spheres * 16));
       API_HIP(hipMemcpyAsync(c.rf.in_sph.p, spheres, (size_t)num_spheres * 16, hipMemcpyHostToDevice, c.stream));
       d_sph = static_cast<const float*>(c.rf.in_sph.p);
     }
@@ -2574,7 +2472,7 @@ static int render_call(sptr_ctx* x, const sptr_frame* f, void* stream, sptr_stat
     x->full_G = G;
     x->full_R = R;
     x->full_tiles = shard_tiles(f->width, f->height, G, R);
-    API_HIP(ensure_buf(x->tiles_full, (size_t)x->full_tiles * kTilePixels * 4));
+    API_HIP(x->tiles_full.ensure((size_t)x->full_tiles * kTilePixels * 4));
     API_HIP(hipMemsetAsync(x->tiles_full.p, 0, (size_t)x->full_tiles * kTilePixels * 4, s));
   }
   x->split = true;
@@ -2647,12 +2545,12 @@ static int ensure_aov(sptr_ctx* x, const sptr_camera& cam, int W, int H, hipStre
   const size_t n = (size_t)W * H;
   if (d.nz.bytes < n * 16 || d.albedo.bytes < n * 16 || d.ids.bytes < n * 8) {
     if (sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;  // a pending pass may still read the old planes
-    API_HIP(ensure_buf(d.nz, n * 16));
-    API_HIP(ensure_buf(d.albedo, n * 16));
-    API_HIP(ensure_buf(d.ids, n * 8));
+    API_HIP(d.nz.ensure(n * 16));
+    API_HIP(d.albedo.ensure(n * 16));
+    API_HIP(d.ids.ensure(n * 8));
   }
   if (!d.flag.p) {
-    API_HIP(ensure_buf(d.flag, 16));
+    API_HIP(d.flag.ensure(16));
     API_HIP(hipMemset(d.flag.p, 0, 16));
   }
   const int rg = ensure_geom_first(x);
@@ -2669,7 +2567,7 @@ static int ensure_aov(sptr_ctx* x, const sptr_camera& cam, int W, int H, hipStre
   a.albedo = static_cast<float4*>(d.albedo.p);
   a.ids = static_cast<uint2*>(d.ids.p);
   a.tri_orig = static_cast<const uint32_t*>(c.tri_orig.p);
-  a.geom_first = static_cast<const uint32_t*>(d.geom_first.p);
+  a.geom_first = static_cast<const uint32_t*>(x->geom_first.p);
   a.mats = static_cast<const DevMaterial*>(c.mats.p);
   a.geom_mat = static_cast<const uint32_t*>(c.geom_mat.p);
   a.stack_overflow = static_cast<uint32_t*>(d.flag.p);
@@ -2691,15 +2589,15 @@ static int ensure_aov(sptr_ctx* x, const sptr_camera& cam, int W, int H, hipStre
 static int enqueue_denoise(sptr_ctx* x, const sptr_frame* f, hipStream_t s) {
   Context& c = x->c;
   auto& d = x->dn;
-  for (hipEvent_t& e : d.ev)
-    if (!e) API_HIP(hipEventCreate(&e));
+  for (DevEvent& e : d.ev)
+    if (!e) API_HIP(hipEventCreate(e.put()));
   const int W = f->width, H = f->height;
   const size_t n = (size_t)W * H;
   if (d.col[0].bytes < n * 16 || d.col[1].bytes < n * 16 || d.image.bytes < n * 3) {
     if (sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;
-    API_HIP(ensure_buf(d.col[0], n * 16));
-    API_HIP(ensure_buf(d.col[1], n * 16));
-    API_HIP(ensure_buf(d.image, n * 3));
+    API_HIP(d.col[0].ensure(n * 16));
+    API_HIP(d.col[1].ensure(n * 16));
+    API_HIP(d.image.ensure(n * 3));
   }
   bool aov_ran = false;
   const int rc = ensure_aov(x, f->camera, W, H, s, true, &aov_ran);

@@ -19,6 +19,7 @@
 #include <utility>
 #include <vector>
 
+#include "dev_owned.h"
 #include "sptr_hip.h"
 #include "sptr_math.h"
 #include "tile_map.h"
@@ -331,10 +332,6 @@ struct DenoiseView {
   uint32_t normal_log2;     // the normal weight is max(0, Np.Nq) squared this many times
 };
 
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-};
 // One lane's path-state streams: ray streams, hit records, radiance, shadow tasks, and
 // the segment tables / per-block tallies / work counters (seg).
 struct WaveBufs {
@@ -379,8 +376,8 @@ struct GraphKey {
 struct GraphCache {
   bool valid = false;
   GraphKey key{};
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t exec = nullptr;
+  DevGraph graph;
+  DevGraphExec exec;  // (declared after graph: destroyed before it)
   hipGraphNode_t dyn_node = nullptr;  // k_frame_dyn: its arguments are the per-call values
   hipKernelNodeParams dyn_params{};
   uint32_t waves = 0;
@@ -403,29 +400,30 @@ struct RefitState {
   uint32_t max_h = 0;      // the root's height
   DevBuf wsrc;             // kWide words per wide node: (BVH2 node << 1 | side) each child box is read from, or kNoHit
   DevBuf in_pos, in_sph;   // device staging of host-pointer updates
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // begin, after the slot pass, after the BVH2 pass, end
+  DevEvent ev[4];          // begin, after the slot pass, after the BVH2 pass, end
   uint32_t refits = 0;     // since the upload
   double ms_wall = 0.0, ms_device = 0.0, ms_stage[3] = {0.0, 0.0, 0.0};  // of the last refit
 };
 
 struct Context {
   int device = 0;
-  hipStream_t stream = nullptr;
-  hipStream_t cap_stream = nullptr;  // launch-graph capture (a pixel lane's: created on its first capture)
+  // (the streams come first: members are destroyed in reverse order, so everything below goes before them)
+  DevStream stream;
+  DevStream cap_stream;  // launch-graph capture (a pixel lane's: created on its first capture)
   // side streams for launches that overlap the main sequence: the shadow launches (side) and k_sky /
   // k_strag (side2; k_sky beside the tail of scenes beyond an XCD's L2 runs on side after the last
   // shadow join), for direct launches and inside a capture (cap_*).  Star-shaped fork/join only: a side
   // stream waits on events of the call's main stream and the main stream on the side streams', never
   // one side stream on another (enqueue_wavefront, DESIGN.md §3 "Launch graphs").
-  hipStream_t side_stream = nullptr, cap_side = nullptr, side2_stream = nullptr, cap_side2 = nullptr;
+  DevStream side_stream, cap_side, side2_stream, cap_side2;
   // fork to a side stream, shadow join, k_sky join.  The direct launches and the captures each have
   // their own set (dev[0] direct, dev[1] captured), so an event recorded inside a capture is never
   // waited on by a direct launch.
   struct DepEvents {
-    hipEvent_t fork = nullptr, join = nullptr, sky = nullptr;
+    DevEvent fork, join, sky;
   } dev[2];
   int prio_lo = 0, prio_hi = 0;  // stream priority range (hipDeviceGetStreamPriorityRange)
-  hipEvent_t quiet_ev[2] = {nullptr, nullptr};  // dispatch events of untimed two-lane launches (StageTimer::quiet)
+  DevEvent quiet_ev[2];  // dispatch events of untimed two-lane launches (StageTimer::quiet)
   // 0: replay a captured graph for repeated call shapes that fork no side-stream launch (run_call);
   // 1: direct launches; 2: direct, one stream; 3: graph for every repeated shape
   uint32_t launch_mode = 0;
@@ -499,11 +497,11 @@ struct Context {
   DevBuf qbuf;
   // Render calls whose counters and events are not yet collected (SPTR_FRAME_ASYNC): the device
   // totals accumulate across them and the stage events stay in the pool until sptr_collect_stats.
-  std::vector<hipEvent_t> events;               // event pool
+  std::vector<DevEvent> events;                 // event pool
   std::vector<StageMark> marks;                 // recorded stage spans (event pool indices)
   size_t events_used = 0;
   uint32_t pending = 0;                         // render calls since the last collection
-  hipStream_t pending_stream = nullptr;
+  hipStream_t pending_stream = nullptr;         // (borrowed: this context's stream or a caller's)
   uint64_t pending_samples = 0, pending_waves = 0, pending_culls = 0;
 };
 
@@ -518,7 +516,7 @@ int build_lbvh(Context& c, const float* h_pos, uint32_t nverts, const uint32_t* 
 int refit_retain_slots(Context& c, const float* d_pos, const uint32_t* d_idx, const float4* d_sph);
 void launch_wide_sources(uint32_t ncur, const uint2* cur, uint32_t base, const BvhNode* nodes, uint32_t* wsrc, hipStream_t s);
 int refit_lbvh(Context& c, const float* d_pos, const float4* d_sph);
-void refit_release(Context& c, bool events);
+void refit_release(Context& c);  // the buffers; the events stay for the next dynamic upload
 
 // kernels_sort.hip: the build's device primitives (temp == nullptr: set temp_bytes only)
 hipError_t scan_u32(void* temp, size_t& temp_bytes, const uint32_t* in, uint32_t* out, uint32_t n, hipStream_t s);

@@ -88,6 +88,36 @@ def test_index_math_cpp(tmp_path):
     assert out.returncode == 0, out.stdout
 
 
+CSRC = os.path.join(ROOT, "simple-path-tracer_amd", "csrc")
+
+
+def test_dev_owned_cpp(tmp_path):
+    """The owners of device memory, events, streams and graphs (csrc/dev_owned.h) against a fake HIP
+    runtime that counts what is live, under the address and undefined-behaviour sanitizers."""
+    exe = tmp_path / "tdo"
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+    subprocess.run(["g++", "-std=c++20", "-g", "-fsanitize=address,undefined", "-D__HIP_PLATFORM_AMD__",
+                    "-I" + os.path.join(rocm, "include"), "-I" + CSRC,
+                    os.path.join(ROOT, "tests", "cpp", "test_dev_owned.cpp"), "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout + out.stderr
+
+
+def test_device_resources_are_released_only_by_their_owners():
+    """Under csrc/, device memory is allocated and freed, and events, streams and graphs are destroyed,
+    in dev_owned.h alone: whatever the library holds frees itself, and no cleanup list can miss it."""
+    calls = ("hipFree(", "hipMalloc(", "hipEventDestroy(", "hipStreamDestroy(", "hipGraphDestroy(", "hipGraphExecDestroy(")
+    found = []
+    for name in sorted(os.listdir(CSRC)):
+        if name == "dev_owned.h":
+            continue
+        text = open(os.path.join(CSRC, name)).read()
+        found += [(name, c) for c in calls if c in text]
+    assert not found, found
+    own = open(os.path.join(CSRC, "dev_owned.h")).read()
+    assert all(c.rstrip("(") in own for c in calls)  # (the destroy calls are template arguments there)
+
+
 @pytest.mark.parametrize("W,H,G", [(64, 64, 1), (75, 41, 2), (150, 70, 3), (1920, 1080, 8), (33, 31, 5)])
 def test_tile_pack_unpack_roundtrip(W, H, G):
     g = np.random.default_rng(W * H + G)
