@@ -387,6 +387,45 @@ int sptr_read_denoised(sptr_ctx* ctx, float* rgb);
  * pointer may be NULL. */
 int sptr_denoise_info(const sptr_ctx* ctx, double* ms_aov, double* ms_filter, uint32_t* aov_passes);
 
+/* ---- temporal reprojection: the denoiser's history across camera moves (symbols added within ABI 9: no
+ *      existing struct or entry point changed) --------------------------------------------------------
+ * A caller restarts the accumulation (frame_begin 1) when the camera moves, so every frame of a camera move
+ * is a fresh 1-spp image.  Two settings carry what earlier frames saw across such a restart (DESIGN.md
+ * "Temporal reprojection"); with both at their defaults a render call issues exactly the launches it issued
+ * before these entry points existed and returns the same bytes.
+ *
+ * Seed offset: a wavefront render call seeds its frames as if its accumulation index were frame_begin +
+ * offset, so that restarted accumulations need not draw the same per-pixel random streams again.  The clear
+ * of the accumulation (frame_begin == 1), the continuity check and the divisor still follow frame_begin.
+ * sptr_render returns SPTR_ERR_INVALID when offset + frame_begin + spp - 1 overflows 32 bits, and for a
+ * call of another integrator while the offset is not 0.  Default 0. */
+int sptr_set_seed_offset(sptr_ctx* ctx, uint32_t offset);
+/* History: while the denoiser is on, each denoise pass first integrates the accumulation's mean c_0 with
+ * the image an earlier pass integrated (the carry), reprojected through the first hit's world position:
+ * t_0 = (n c_0 + m h) / (n + m), where h and m <= max_history are the carry's colour and history length
+ * under the four bilinear taps that show the same surface (same geomID, normal and depth weights of the
+ * filter itself at least 0.5 together); when the carry's camera is not the call's, h is first clipped to
+ * the mean -+ half a standard deviation of c_0 over the pixel's 3x3 neighbours on the same geometry, since
+ * what a glossy surface shows belongs to the view.  The filter's colour sigma then fades with n + m per
+ * pixel instead of n.  When a call with frame_begin == 1 runs a pass, the image the previous pass integrated becomes the
+ * carry, with that pass's first-hit planes and camera; calls that continue the accumulation keep reading
+ * the same carry.  The carry is dropped when the size changes, when the scene state changes (whatever
+ * recomputes the first-hit planes of an unchanged camera: uploads, sptr_update_geometry, the material,
+ * light and environment setters, ...) and by any call of sptr_set_denoise_history.  Without a carry the
+ * pass equals the pass without history bit for bit.  Costs about 56 bytes per pixel of device memory. */
+typedef struct sptr_history_params {
+  uint32_t max_history;   /* 0 = off (default); else the cap M on a pixel's history length, in frames; at most 1024 */
+  uint32_t reserved[3];   /* 0 */
+} sptr_history_params;
+int sptr_set_denoise_history(sptr_ctx* ctx, const sptr_history_params* params);  /* NULL = off; any call drops the history held */
+/* The last pass's integrated colour t_0 and history length m' (n + m; 0 where the filter passes the pixel
+ * through): W*H*4 floats.  An error unless the last render call ran a pass with history on. */
+int sptr_read_history(sptr_ctx* ctx, float* rgbm);
+/* Waits for the last pass, as sptr_denoise_info: the pixels that took history (m > 0), the device time of
+ * the reprojection launch, and whether the pass had a carry to read.  All 0 when the last render call ran
+ * no pass with history on.  Any pointer may be NULL. */
+int sptr_history_info(sptr_ctx* ctx, uint32_t* reprojected, double* ms_reproject, uint32_t* carried);
+
 /* ---- dynamic scenes: refit the BVH in place when geometry moves (symbols added within ABI 9: no
  *      existing struct or entry point changed) --------------------------------------------------------
  * A scene whose coordinates change but whose topology does not (an animated or edited mesh, moving

@@ -7,6 +7,8 @@
 // reads neighbours up to 2 * 2^4 pixels away.  Arithmetic rule (DESIGN.md "Denoiser"): + - x, IEEE
 // division, max and compares only, no contraction, so tests/denoise_ref.py restates the filter bit for
 // bit in numpy float32.
+// k_dn_reproject (sptr_set_denoise_history, DESIGN.md "Temporal reprojection") integrates an earlier pass's
+// image into k_dn_mean's output under the same rule, with sqrtf and floorf besides (tests/temporal_ref.py).
 
 // --------------------------------------------------------------------------------- k_aov
 // One closest-hit query per image pixel along the pixel-centre ray.
@@ -96,7 +98,10 @@ __global__ void __launch_bounds__(kBlock) k_dn_mean(DenoiseView v, const float4*
 // segments of 512 B and vertically neighbouring taps of a block share cache lines.
 // The taps read global memory: the working set (133 MB at 1080p) stays in L2 / MALL.  (Staging the patch and
 // its 2 s halo in LDS for s = 1, 2 measured slower)
+// kPerPixel (history on, k_dn_reproject ran): the colour image's w holds the pixel's effective frame count
+// n_eff and S2 holds sigma_c 2^-i, so that S = S2 / n_eff(p) for the centre pixel; w rides through.
 constexpr int kDnTileW = 32, kDnTileH = kBlock / kDnTileW;
+template <bool kPerPixel>
 __global__ void __launch_bounds__(kBlock) k_atrous(DenoiseView v, const float4* __restrict__ cin, float4* __restrict__ cout, int s,
                                                    float S2) {
   const int x = (int)blockIdx.x * kDnTileW + (int)(threadIdx.x % kDnTileW);
@@ -108,6 +113,10 @@ __global__ void __launch_bounds__(kBlock) k_atrous(DenoiseView v, const float4* 
   if (np.w < 0.0f || !dn_finite(cp)) {  // the environment, or a mean that is not finite: passed through
     cout[p] = cp;
     return;
+  }
+  if constexpr (kPerPixel) {
+    const float S = S2 / cp.w;
+    S2 = S * S;
   }
   const float4 ap = v.albedo[p];
   const float h[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
@@ -139,7 +148,116 @@ __global__ void __launch_bounds__(kBlock) k_atrous(DenoiseView v, const float4* 
       wsum = wsum + w;
     }
   }
-  cout[p] = f4(sum / wsum, 0.0f);
+  cout[p] = f4(sum / wsum, kPerPixel ? cp.w : 0.0f);
+}
+
+// --------------------------------------------------------------------------------- temporal reprojection
+// One pixel of the history integration: the first hit's world position, projected into the
+// carry's camera, takes that pass's integrated colour t_0' and history length m' through the four bilinear
+// taps that show the same surface, and mixes them into this pass's mean c_0 = r.c0:
+//   t_0 = (n c_0 + m h) / (n + m), m' = n + m.
+// A miss, a mean that is not finite, or no acceptable tap: t_0 = c_0 bit-unchanged (m' = n, or 0 where the
+// filter passes the pixel through).  32 x 8 pixel blocks as k_atrous; no LDS; every tap is bounds-checked
+// before its loads.  Pixels that took history are counted with one ballot and one atomic per wave.
+__global__ void __launch_bounds__(kBlock) k_dn_reproject(DenoiseView v, FrameView f, ReprojView r) {
+  const int x = (int)blockIdx.x * kDnTileW + (int)(threadIdx.x % kDnTileW);
+  const int y = (int)blockIdx.y * kDnTileH + (int)(threadIdx.x / kDnTileW);
+  bool took = false;
+  if (x < v.W && y < v.H) {
+    const uint32_t p = (uint32_t)y * (uint32_t)v.W + (uint32_t)x;
+    const float4 c0 = r.c0[p];
+    const float4 np = v.nz[p];
+    const float nf = float(v.n);
+    float4 out = f4(xyz(c0), 0.0f);
+    if (!(np.w < 0.0f) && dn_finite(c0)) {
+      out.w = nf;
+      if (r.hist_prev) {
+        const ImageDiv idiv = image_div(f);
+        const vec3 d = camera_dir(f, div_nrm(float(x) + 0.5f, idiv.w), div_nrm(float(y) + 0.5f, idiv.h));  // as k_aov
+        const vec3 P = f.cam_pos + np.w * d;
+        const vec3 vv = P - r.pos;
+        const float zf = dot(vv, r.fw);
+        const float nx = dot(vv, r.rt) / (zf * r.hw);
+        const float ny = dot(vv, r.up) / (zf * r.hh);
+        const float fx = (nx * 0.5f + 0.5f) * float(v.W) - 0.5f;
+        const float fy = (0.5f - ny * 0.5f) * float(v.H) - 0.5f;
+        // (written so that a NaN or an infinity fails: no conversion to int and no load before it)
+        if (zf > 0.0f && fx > -1.0f && fx < float(v.W) && fy > -1.0f && fy < float(v.H)) {
+          const float x0f = floorf(fx), y0f = floorf(fy);
+          const float a = fx - x0f, b = fy - y0f;
+          const int x0 = (int)x0f, y0 = (int)y0f;
+          const float dist = sqrtf(dot(vv, vv));
+          const uint32_t gp = r.ids[p].x;
+          float ws = 0.0f, ms = 0.0f;
+          vec3 hs = v3(0.0f, 0.0f, 0.0f);
+#pragma unroll
+          for (int j = 0; j < 2; ++j) {
+            const int qy = y0 + j;
+            const float wy = j ? b : 1.0f - b;
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+              const int qx = x0 + i;
+              if (qx < 0 || qx >= v.W || qy < 0 || qy >= v.H) continue;
+              const uint32_t q = (uint32_t)qy * (uint32_t)v.W + (uint32_t)qx;
+              const float4 hq = r.hist_prev[q];
+              const float4 nq = r.nz_prev[q];
+              if (nq.w < 0.0f || !dn_finite(hq) || r.ids_prev[q].x != gp) continue;
+              float wn = fmax_g(0.0f, dot(xyz(np), xyz(nq)));
+              for (uint32_t k = 0; k < v.normal_log2; ++k) wn = wn * wn;
+              const float e = fabsf(dist - nq.w) / (v.sigma_z * fmax_g(dist, nq.w));
+              const float wz = 1.0f / (1.0f + e * e);
+              if (!(wn * wz >= 0.5f)) continue;
+              const float w = (i ? a : 1.0f - a) * wy;
+              ws = ws + w;
+              hs = hs + w * xyz(hq);
+              ms = ms + w * hq.w;
+            }
+          }
+          if (ws > 0.0f) {
+            vec3 h = hs / ws;
+            if (r.clip > 0.0f) {
+              // the view changed, and with it whatever the surface reflects: h is clipped to mu -+ clip sd of
+              // c_0 over the 3 x 3 neighbours on the same geometry (the centre always counts)
+              vec3 s1 = v3(0.0f, 0.0f, 0.0f), s2 = v3(0.0f, 0.0f, 0.0f);
+              float cnt = 0.0f;
+#pragma unroll
+              for (int dy = -1; dy <= 1; ++dy) {
+                const int qy = y + dy;
+                if (qy < 0 || qy >= v.H) continue;
+#pragma unroll
+                for (int dx = -1; dx <= 1; ++dx) {
+                  const int qx = x + dx;
+                  if (qx < 0 || qx >= v.W) continue;
+                  const uint32_t q = (uint32_t)qy * (uint32_t)v.W + (uint32_t)qx;
+                  const float4 cq = r.c0[q];
+                  if (v.nz[q].w < 0.0f || !dn_finite(cq) || r.ids[q].x != gp) continue;
+                  s1 = s1 + xyz(cq);
+                  s2 = s2 + xyz(cq) * xyz(cq);
+                  cnt = cnt + 1.0f;
+                }
+              }
+              const vec3 mu = s1 / cnt;
+              const vec3 var = s2 / cnt - mu * mu;
+              // (max(0, var) written so that a NaN, from sums that overflowed, gives 0)
+              const vec3 sd = v3(sqrtf(fmax_g(0.0f, var.x)), sqrtf(fmax_g(0.0f, var.y)), sqrtf(fmax_g(0.0f, var.z)));
+              const vec3 lo = mu - r.clip * sd, hi = mu + r.clip * sd;
+              h = v3(fmin_g(fmax_g(h.x, lo.x), hi.x), fmin_g(fmax_g(h.y, lo.y), hi.y), fmin_g(fmax_g(h.z, lo.z), hi.z));
+            }
+            float m = ms / ws;
+            m = m < r.max_history ? m : r.max_history;
+            if (m > 0.0f) {
+              const float neff = nf + m;
+              out = f4((nf * xyz(c0) + m * h) / neff, neff);
+              took = true;
+            }
+          }
+        }
+      }
+    }
+    r.hist[p] = out;
+  }
+  const unsigned long long bal = __ballot(took);
+  if (bal != 0ull && lane_id() == 0u) atomicAdd(r.count, (uint32_t)__popcll(bal));
 }
 
 // The resolve's last steps (ACES, gamma, 8 bit) on the filtered mean: resolve_rgba with a count of 1.
@@ -159,7 +277,15 @@ void launch_dn_mean(const DenoiseView& v, const float4* accum0, const float4* ac
 }
 void launch_atrous(const DenoiseView& v, const float4* cin, float4* cout, int step, float S2, hipStream_t s) {
   const dim3 grid((unsigned)((v.W + kDnTileW - 1) / kDnTileW), (unsigned)((v.H + kDnTileH - 1) / kDnTileH));
-  hipLaunchKernelGGL(k_atrous, grid, dim3(kBlock), 0, s, v, cin, cout, step, S2);
+  hipLaunchKernelGGL(k_atrous<false>, grid, dim3(kBlock), 0, s, v, cin, cout, step, S2);
+}
+void launch_atrous_history(const DenoiseView& v, const float4* cin, float4* cout, int step, float Si, hipStream_t s) {
+  const dim3 grid((unsigned)((v.W + kDnTileW - 1) / kDnTileW), (unsigned)((v.H + kDnTileH - 1) / kDnTileH));
+  hipLaunchKernelGGL(k_atrous<true>, grid, dim3(kBlock), 0, s, v, cin, cout, step, Si);
+}
+void launch_dn_reproject(const DenoiseView& v, const FrameView& f, const ReprojView& r, hipStream_t s) {
+  const dim3 grid((unsigned)((v.W + kDnTileW - 1) / kDnTileW), (unsigned)((v.H + kDnTileH - 1) / kDnTileH));
+  hipLaunchKernelGGL(k_dn_reproject, grid, dim3(kBlock), 0, s, v, f, r);
 }
 void launch_dn_resolve(const DenoiseView& v, const float4* c, uint8_t* image, hipStream_t s) {
   hipLaunchKernelGGL(k_dn_resolve, dim3(grid_for((uint64_t)v.W * v.H)), dim3(kBlock), 0, s, v, c, image);

@@ -69,6 +69,23 @@ struct sptr_ctx {
     uint32_t final_col = 0;
     sptr::DevEvent ev[4];                                     // AOV begin / end, filter begin / end
     bool aov_timed = false, filter_timed = false;             // ... recorded by the last pass
+    // sptr_set_denoise_history.  The {N, z} and id planes are double-buffered: nz / ids above
+    // are side 0, nz1 / ids1 side 1 (allocated with the history images); aov_side is the side the cached
+    // planes (aov_cam ...) are in, and a recomputation never writes the side the carry's planes are in.
+    sptr_history_params hp{};  // max_history 0: off
+    sptr::DevBuf nz1, ids1, hist[2], hcount;
+    int aov_side = 0;
+    struct Pass {  // a pass's history image with the planes, camera, size and state it ran for
+      bool valid = false;
+      int slot = 0, side = 0;
+      sptr_camera cam{};
+      int W = 0, H = 0;
+      uint64_t epoch = 0;
+    } last, carry;  // the last pass, and the pass the current accumulation takes its history from
+    bool hist_ran = false;     // the last render call ran a pass with history on
+    bool hist_carried = false; // ... and that pass had a carry to read
+    uint32_t hist_slot = 0;    // ... and wrote hist[hist_slot]
+    sptr::DevEvent hev[2];     // k_dn_reproject begin / end
   } dn;
   // sptr_query_rays (the caller's context; a pixel lane holds none): scratch that grows on demand (sort keys
   // and identity indices, their sorted copies, the radix sort's temporaries, the stack-overflow flag, the
@@ -1620,6 +1637,12 @@ static int render_one(sptr_ctx* x, const sptr_frame* f, void* stream, sptr_stats
   const bool timing = (f->flags & SPTR_FRAME_TIMING) != 0;
   const bool trace_timing = (f->flags & SPTR_FRAME_TIMING_TRACE) != 0;
   const uint32_t total = f->frame_begin + f->spp - 1;
+  if (c.seed_offset != 0u) {  // sptr_set_seed_offset
+    if (f->integrator != SPTR_INTEGRATOR_WAVEFRONT)
+      return fail(c, SPTR_ERR_INVALID, "render: a seed offset applies to SPTR_INTEGRATOR_WAVEFRONT only (sptr_set_seed_offset)");
+    if ((uint64_t)c.seed_offset + f->frame_begin + f->spp - 1 > 0xFFFFFFFFull)
+      return fail(c, SPTR_ERR_INVALID, "render: seed offset + frame_begin + spp - 1 overflows 32 bits");
+  }
   GraphKey key{};
   key.epoch = c.epoch;
   key.frame = *f;
@@ -1680,7 +1703,8 @@ static int render_one(sptr_ctx* x, const sptr_frame* f, void* stream, sptr_stats
     // an in-sequence cull (SPTR_FRAME_RECULL) counts its unculled pixels from zero: k_frame_dyn clears it
     uint32_t* clear = ((f->flags & SPTR_FRAME_RECULL) && !(f->flags & SPTR_FRAME_NO_CULL))
                           ? static_cast<uint32_t*>(c.plist.p) + c.P : nullptr;
-    rc = run_call(c, key, f->frame_begin, reset ? 1u : 0u, total, (uint64_t)frame_view(c, *f).valid * f->spp, clear,
+    // (the seeds' accumulation index: frame_begin + the seed offset, the k_frame_dyn word they read)
+    rc = run_call(c, key, f->frame_begin + c.seed_offset, reset ? 1u : 0u, total, (uint64_t)frame_view(c, *f).valid * f->spp, clear,
                   timing || trace_timing, !timing, s,
                   [&](hipStream_t cs, StageTimer& tm) { return enqueue_wavefront(c, *f, k, T, cs, tm); }, waves);
     if (rc != SPTR_OK) return rc;
@@ -2516,6 +2540,8 @@ static int render_call(sptr_ctx* x, const sptr_frame* f, void* stream, sptr_stat
 }
 
 // ---- first-hit AOVs and the denoiser --------------------------------------------------------------
+// Half a standard deviation: the tightest of the clips tried on the CPU (tests/test_temporal_cpu.py)
+static constexpr float kHistoryClip = 0.5f;
 int sptr_set_denoise(sptr_ctx* x, const sptr_denoise_params* p) {
   if (!x) return SPTR_ERR_INVALID;
   Context& c = x->c;
@@ -2543,12 +2569,17 @@ static int ensure_aov(sptr_ctx* x, const sptr_camera& cam, int W, int H, hipStre
   if (d.aov_epoch == c.epoch && d.aov_W == W && d.aov_H == H && std::memcmp(&d.aov_cam, &cam, sizeof(cam)) == 0)
     return SPTR_OK;
   const size_t n = (size_t)W * H;
-  if (d.nz.bytes < n * 16 || d.albedo.bytes < n * 16 || d.ids.bytes < n * 8) {
+  // the side written: never the one that holds the carry's planes (history off: always side 0)
+  const int side = d.carry.valid ? d.carry.side ^ 1 : d.aov_side;
+  sptr::DevBuf& nzb = side ? d.nz1 : d.nz;
+  sptr::DevBuf& idb = side ? d.ids1 : d.ids;
+  if (nzb.bytes < n * 16 || d.albedo.bytes < n * 16 || idb.bytes < n * 8) {
     if (sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;  // a pending pass may still read the old planes
-    API_HIP(d.nz.ensure(n * 16));
+    API_HIP(nzb.ensure(n * 16));
     API_HIP(d.albedo.ensure(n * 16));
-    API_HIP(d.ids.ensure(n * 8));
+    API_HIP(idb.ensure(n * 8));
   }
+  if (d.last.valid && d.last.side == side) d.last.valid = false;  // its planes are overwritten below
   if (!d.flag.p) {
     API_HIP(d.flag.ensure(16));
     API_HIP(hipMemset(d.flag.p, 0, 16));
@@ -2563,9 +2594,9 @@ static int ensure_aov(sptr_ctx* x, const sptr_camera& cam, int W, int H, hipStre
   fr.max_depth = 1;
   const FrameView fv = frame_view(c, fr);
   AovView a{};
-  a.nz = static_cast<float4*>(d.nz.p);
+  a.nz = static_cast<float4*>(nzb.p);
   a.albedo = static_cast<float4*>(d.albedo.p);
-  a.ids = static_cast<uint2*>(d.ids.p);
+  a.ids = static_cast<uint2*>(idb.p);
   a.tri_orig = static_cast<const uint32_t*>(c.tri_orig.p);
   a.geom_first = static_cast<const uint32_t*>(x->geom_first.p);
   a.mats = static_cast<const DevMaterial*>(c.mats.p);
@@ -2579,6 +2610,7 @@ static int ensure_aov(sptr_ctx* x, const sptr_camera& cam, int W, int H, hipStre
   d.aov_cam = cam;
   d.aov_W = W;
   d.aov_H = H;
+  d.aov_side = side;
   ++d.aov_passes;
   *ran = true;
   return SPTR_OK;
@@ -2599,6 +2631,28 @@ static int enqueue_denoise(sptr_ctx* x, const sptr_frame* f, hipStream_t s) {
     API_HIP(d.col[1].ensure(n * 16));
     API_HIP(d.image.ensure(n * 3));
   }
+  const bool history = d.hp.max_history != 0u;
+  d.hist_ran = false;
+  if (history) {
+    // the carry rules: a pass of another size or scene state is no history; a call that starts an
+    // accumulation takes the last pass as its carry, one that continues it keeps the carry it has
+    auto stale = [&](const sptr_ctx::Denoise::Pass& p) { return !p.valid || p.W != W || p.H != H || p.epoch != c.epoch; };
+    if (stale(d.last)) d.last.valid = false;
+    if (stale(d.carry)) d.carry.valid = false;
+    if (f->frame_begin == 1) d.carry = d.last;
+    if (d.hist[0].bytes < n * 16 || d.hist[1].bytes < n * 16 || d.nz1.bytes < n * 16 || d.ids1.bytes < n * 8 ||
+        d.nz.bytes < n * 16 || d.ids.bytes < n * 8 || !d.hcount.p) {
+      if (sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;
+      d.last.valid = d.carry.valid = false;  // (a size none of them was made for)
+      d.aov_epoch = 0;
+      d.aov_side = 0;
+      for (sptr::DevBuf* b : {&d.hist[0], &d.hist[1], &d.nz, &d.nz1}) API_HIP(b->ensure(n * 16));
+      for (sptr::DevBuf* b : {&d.ids, &d.ids1}) API_HIP(b->ensure(n * 8));
+      API_HIP(d.hcount.ensure(16));
+    }
+    for (DevEvent& e : d.hev)
+      if (!e) API_HIP(hipEventCreate(e.put()));
+  }
   bool aov_ran = false;
   const int rc = ensure_aov(x, f->camera, W, H, s, true, &aov_ran);
   if (rc != SPTR_OK) return rc;
@@ -2607,7 +2661,7 @@ static int enqueue_denoise(sptr_ctx* x, const sptr_frame* f, hipStream_t s) {
   v.W = W;
   v.H = H;
   v.n = f->frame_begin + f->spp - 1;
-  v.nz = static_cast<const float4*>(d.nz.p);
+  v.nz = static_cast<const float4*>(d.aov_side ? d.nz1.p : d.nz.p);
   v.albedo = static_cast<const float4*>(d.albedo.p);
   v.sigma_z = d.p.sigma_depth;
   v.sigma_a2 = d.p.sigma_albedo * d.p.sigma_albedo;
@@ -2618,10 +2672,64 @@ static int enqueue_denoise(sptr_ctx* x, const sptr_frame* f, hipStream_t s) {
   launch_dn_mean(v, static_cast<const float4*>(c.accum.p), x->split ? static_cast<const float4*>(x->lane->c.accum.p) : nullptr,
                  x->split ? 2 : 1, col[0], s);
   uint32_t cur = 0;
-  for (uint32_t i = 0; i < d.p.iterations; ++i) {
-    const float S = d.p.sigma_color * (1.0f / float(1u << i)) / float(v.n);  // sigma_c 2^-i / n
-    launch_atrous(v, col[cur], col[cur ^ 1u], 1 << i, S * S, s);
-    cur ^= 1u;
+  if (!history) {
+    for (uint32_t i = 0; i < d.p.iterations; ++i) {
+      const float S = d.p.sigma_color * (1.0f / float(1u << i)) / float(v.n);  // sigma_c 2^-i / n
+      launch_atrous(v, col[cur], col[cur ^ 1u], 1 << i, S * S, s);
+      cur ^= 1u;
+    }
+  } else {
+    // c_0 and the carry integrated into the history slot the carry is not in; iteration 0 reads that slot
+    // directly, and the iterations divide sigma_c 2^-i by the pixel's n_eff (the slot's w)
+    const uint32_t slot = d.carry.valid ? (uint32_t)(d.carry.slot ^ 1) : (d.last.valid ? (uint32_t)d.last.slot : 0u);
+    ReprojView r{};
+    r.c0 = col[0];
+    r.ids = static_cast<const uint2*>(d.aov_side ? d.ids1.p : d.ids.p);
+    if (d.carry.valid) {
+      r.hist_prev = static_cast<const float4*>(d.hist[d.carry.slot].p);
+      r.nz_prev = static_cast<const float4*>(d.carry.side ? d.nz1.p : d.nz.p);
+      r.ids_prev = static_cast<const uint2*>(d.carry.side ? d.ids1.p : d.ids.p);
+      const sptr_camera& k = d.carry.cam;
+      r.pos = v3(k.pos[0], k.pos[1], k.pos[2]);
+      r.fw = v3(k.forward[0], k.forward[1], k.forward[2]);
+      r.rt = v3(k.right[0], k.right[1], k.right[2]);
+      r.up = v3(k.up[0], k.up[1], k.up[2]);
+      r.hw = k.half_width;
+      r.hh = k.half_height;
+      // a history seen from elsewhere is clipped to the current neighbourhood's colours; a
+      // standing camera's estimates the same integrand and is taken whole
+      r.clip = std::memcmp(&k, &f->camera, sizeof(k)) != 0 ? kHistoryClip : 0.0f;
+    }
+    r.hist = static_cast<float4*>(d.hist[slot].p);
+    r.max_history = float(d.hp.max_history);
+    r.count = static_cast<uint32_t*>(d.hcount.p);
+    sptr_frame fr{};
+    fr.width = W;
+    fr.height = H;
+    fr.camera = f->camera;
+    fr.frame_begin = 1;
+    fr.max_depth = 1;
+    API_HIP(hipMemsetAsync(d.hcount.p, 0, 4, s));
+    API_HIP(hipEventRecord(d.hev[0], s));
+    launch_dn_reproject(v, frame_view(c, fr), r, s);
+    API_HIP(hipEventRecord(d.hev[1], s));
+    const float4* in = r.hist;
+    for (uint32_t i = 0; i < d.p.iterations; ++i) {
+      launch_atrous_history(v, in, col[cur], 1 << i, d.p.sigma_color * (1.0f / float(1u << i)), s);
+      in = col[cur];
+      cur ^= 1u;
+    }
+    cur ^= 1u;  // (the image the last iteration wrote)
+    d.hist_ran = true;
+    d.hist_carried = d.carry.valid;
+    d.hist_slot = slot;
+    d.last.valid = true;
+    d.last.slot = (int)slot;
+    d.last.side = d.aov_side;
+    d.last.cam = f->camera;
+    d.last.W = W;
+    d.last.H = H;
+    d.last.epoch = c.epoch;
   }
   launch_dn_resolve(v, col[cur], static_cast<uint8_t*>(d.image.p), s);
   API_HIP(hipGetLastError());
@@ -2689,11 +2797,12 @@ int sptr_read_aov(sptr_ctx* x, int kind, void* out) {
   if (flag) return fail(c, SPTR_ERR_HIP, "read_aov: BVH traversal stack overflow (internal error)");
   const size_t n = (size_t)d.last_W * d.last_H;
   if (kind == SPTR_AOV_ID) {
-    API_HIP(hipMemcpy(out, d.ids.p, n * 8, hipMemcpyDeviceToHost));
+    API_HIP(hipMemcpy(out, d.aov_side ? d.ids1.p : d.ids.p, n * 8, hipMemcpyDeviceToHost));
     return SPTR_OK;
   }
   std::vector<float> tmp(n * 4);
-  API_HIP(hipMemcpy(tmp.data(), kind == SPTR_AOV_ALBEDO ? d.albedo.p : d.nz.p, n * 16, hipMemcpyDeviceToHost));
+  API_HIP(hipMemcpy(tmp.data(), kind == SPTR_AOV_ALBEDO ? d.albedo.p : (d.aov_side ? d.nz1.p : d.nz.p), n * 16,
+                    hipMemcpyDeviceToHost));
   float* o = static_cast<float*>(out);
   for (size_t i = 0; i < n; ++i) {
     if (kind == SPTR_AOV_DEPTH) {
@@ -2737,6 +2846,70 @@ int sptr_denoise_info(const sptr_ctx* x, double* ms_aov, double* ms_filter, uint
   if (ms_aov) *ms_aov = a;
   if (ms_filter) *ms_filter = fl;
   if (aov_passes) *aov_passes = d.aov_passes;
+  return SPTR_OK;
+}
+
+// ---- temporal reprojection ------------------------------------------------------------------------
+static int set_seed_offset_one(sptr_ctx* x, uint32_t offset) {
+  if (!x) return SPTR_ERR_INVALID;
+  x->c.seed_offset = offset;  // (a k_frame_dyn argument: no captured graph depends on it)
+  return SPTR_OK;
+}
+int sptr_set_seed_offset(sptr_ctx* x, uint32_t offset) {
+  const int rc = set_seed_offset_one(x, offset);
+  return rc == SPTR_OK ? lane_forward(x, set_seed_offset_one(x->lane, offset)) : rc;
+}
+
+int sptr_set_denoise_history(sptr_ctx* x, const sptr_history_params* p) {
+  if (!x) return SPTR_ERR_INVALID;
+  Context& c = x->c;
+  if (x->is_lane) return fail(c, SPTR_ERR_INVALID, "denoise history: not on a lane context");
+  sptr_history_params q{};
+  if (p) q = *p;
+  if (q.max_history > 1024u) return fail(c, SPTR_ERR_INVALID, "denoise history: max_history above 1024");
+  for (uint32_t r : q.reserved)
+    if (r != 0u) return fail(c, SPTR_ERR_INVALID, "denoise history: reserved words must be 0");
+  auto& d = x->dn;
+  d.hp = q;
+  // the history held is dropped; so is the plane cache, so that the next pass writes side 0 again (a pending
+  // pass keeps the buffers it was enqueued with: nothing is freed here)
+  d.last.valid = d.carry.valid = false;
+  d.hist_ran = false;
+  d.aov_epoch = 0;
+  d.aov_side = 0;
+  return SPTR_OK;
+}
+
+int sptr_read_history(sptr_ctx* x, float* rgbm) {
+  if (!x || !rgbm) return SPTR_ERR_INVALID;
+  Context& c = x->c;
+  auto& d = x->dn;
+  if (x->is_lane) return fail(c, SPTR_ERR_INVALID, "read_history: not on a lane context");
+  if (!d.ran || !d.hist_ran)
+    return fail(c, SPTR_ERR_INVALID, "read_history: the last render call ran no pass with history on (sptr_set_denoise_history)");
+  API_HIP(hipSetDevice(c.device));
+  if (sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;
+  API_HIP(hipMemcpy(rgbm, d.hist[d.hist_slot].p, (size_t)d.last_W * d.last_H * 16, hipMemcpyDeviceToHost));
+  return SPTR_OK;
+}
+
+int sptr_history_info(sptr_ctx* x, uint32_t* reprojected, double* ms_reproject, uint32_t* carried) {
+  if (!x) return SPTR_ERR_INVALID;
+  Context& c = x->c;
+  if (x->is_lane) return fail(c, SPTR_ERR_INVALID, "history_info: not on a lane context");
+  const auto& d = x->dn;
+  uint32_t n = 0;
+  float ms = 0.0f;
+  const bool ran = d.ran && d.hist_ran;
+  if (ran) {
+    API_HIP(hipSetDevice(c.device));
+    API_HIP(hipEventSynchronize(d.ev[3]));  // the pass's end
+    (void)hipEventElapsedTime(&ms, d.hev[0], d.hev[1]);
+    API_HIP(hipMemcpy(&n, d.hcount.p, 4, hipMemcpyDeviceToHost));
+  }
+  if (reprojected) *reprojected = n;
+  if (ms_reproject) *ms_reproject = ms;
+  if (carried) *carried = ran && d.hist_carried ? 1u : 0u;
   return SPTR_OK;
 }
 

@@ -331,6 +331,21 @@ struct DenoiseView {
   float sigma_z, sigma_a2;  // sigma_depth; sigma_albedo squared
   uint32_t normal_log2;     // the normal weight is max(0, Np.Nq) squared this many times
 };
+// The history integration's buffers (k_dn_reproject), image space.  The current pass's {N, z} plane is
+// DenoiseView::nz; the carry is an earlier pass's history image with the planes and the camera it ran for.
+struct ReprojView {
+  const float4* c0;         // k_dn_mean's output
+  const uint2* ids;         // the current camera's id plane
+  const float4* hist_prev;  // the carry: t_0' rgb | m' (null: no carry) ...
+  const float4* nz_prev;    // ... its {N, z} plane ...
+  const uint2* ids_prev;    // ... and its id plane
+  float4* hist;             // out: t_0 rgb | m'
+  vec3 pos, fw, rt, up;     // the carry's camera
+  float hw, hh;
+  float max_history;        // M
+  float clip;               // gamma of the variance clip of h (0: none, the carry's camera is the call's)
+  uint32_t* count;          // pixels that took history (zeroed before the launch)
+};
 
 // One lane's path-state streams: ray streams, hit records, radiance, shadow tasks, and
 // the segment tables / per-block tallies / work counters (seg).
@@ -493,6 +508,9 @@ struct Context {
   sptr_camera cull_cam{};
   uint32_t cull_depth = 0;  // depth the cached mask was computed with
   uint32_t last_samples = 0;  // accumulation count after the last render
+  // sptr_set_seed_offset: a wavefront call seeds its frames as if its accumulation index were frame_begin +
+  // seed_offset (the k_frame_dyn word the seeds read; reset and total follow frame_begin alone)
+  uint32_t seed_offset = 0;
   // query scratch
   DevBuf qbuf;
   // Render calls whose counters and events are not yet collected (SPTR_FRAME_ASYNC): the device
@@ -593,6 +611,10 @@ void launch_aov(const SceneView& sv, const FrameView& f, const AovView& a, hipSt
 void launch_dn_mean(const DenoiseView& v, const float4* accum0, const float4* accum1, int G, float4* out, hipStream_t s);
 void launch_atrous(const DenoiseView& v, const float4* cin, float4* cout, int step, float S2, hipStream_t s);
 void launch_dn_resolve(const DenoiseView& v, const float4* c, uint8_t* image, hipStream_t s);
+// history on: the integration after launch_dn_mean, and the iterations whose colour sigma is per pixel
+// (Si = sigma_c 2^-i; the pixel's n_eff is the colour image's w)
+void launch_dn_reproject(const DenoiseView& v, const FrameView& f, const ReprojView& r, hipStream_t s);
+void launch_atrous_history(const DenoiseView& v, const float4* cin, float4* cout, int step, float Si, hipStream_t s);
 // kernels_query.h: one batch of ray queries (sptr_query_rays), and the sort keys of a batch with the
 // identity indices 0..n-1 beside them (the radix sort's values)
 void launch_rayquery(const SceneView& sv, const RayQueryView& q, bool anyhit, hipStream_t s);

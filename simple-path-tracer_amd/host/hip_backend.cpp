@@ -110,6 +110,10 @@ bool HipBackend::syncState() {
     if (sptr_set_denoise(ctx_, &settings_.denoise) != SPTR_OK) return false;
     denoise_applied_ = settings_.denoise;  // (the accumulation goes on: the filter only reads it)
   }
+  if (std::memcmp(&settings_.history, &history_applied_, sizeof(sptr_history_params)) != 0) {
+    if (sptr_set_denoise_history(ctx_, &settings_.history) != SPTR_OK) return false;
+    history_applied_ = settings_.history;
+  }
   return true;
 }
 
@@ -160,6 +164,23 @@ bool HipBackend::renderInternal(int w, int h, const Camera& camera, bool async) 
     changed = true;  // a new accumulation in the new lane mode
   }
   if (changed) frame_index_ = 0;
+  // history on: a restart draws the samples after those of the accumulation it ends; off: the seeds as ever
+  const bool history = settings_.history.max_history != 0u && settings_.denoise.iterations != 0u &&
+                       settings_.integrator == SPTR_INTEGRATOR_WAVEFRONT;
+  uint32_t offset = 0;
+  if (history) {
+    offset = seed_offset_;
+    if (frame_index_ == 0) offset += acc_frames_;
+    if (offset > 0xF0000000u) offset = 0;  // (far from the 32-bit end of the accumulation indices)
+  }
+  if (frame_index_ == 0) acc_frames_ = 0;
+  if (offset != seed_offset_) {
+    if (sptr_set_seed_offset(ctx_, offset) != SPTR_OK) {
+      err_ = std::string("HipBackend::render: ") + sptr_last_error(ctx_);
+      return false;
+    }
+    seed_offset_ = offset;
+  }
   has_last_camera_ = true;
   last_cam_ = cam;
   last_w_ = w;
@@ -195,6 +216,7 @@ bool HipBackend::renderInternal(int w, int h, const Camera& camera, bool async) 
     async_calls_ = 0;
   }
   frame_index_ += fr.spp;
+  acc_frames_ = frame_index_;
   return true;
 }
 

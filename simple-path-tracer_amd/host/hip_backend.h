@@ -40,11 +40,17 @@ class HipBackend {
     // the edge-avoiding a-trous denoiser (wavefront integrator only; with lagged_readback, the denoised
     // previous frame).  Zero sigmas / power take the defaults.  A change does not restart the accumulation.
     sptr_denoise_params denoise{};
+    // sptr_set_denoise_history: max_history 0 = off (default); else, while the denoiser is on, its passes carry
+    // the integrated image across the restarts a camera move causes (kDefaultMaxHistory is the cap to ask for
+    // without a number of one's own), and each restart advances the seed offset (sptr_set_seed_offset) by the
+    // frames of the accumulation it ends, so that consecutive restarts draw fresh samples
+    sptr_history_params history{};
     // sptr_set_dynamic, applied before build(): the build keeps what update() needs to refit the BVH in
     // place when only coordinates change
     bool dynamic = false;
   };
   static constexpr uint32_t kLaggedCollect = 32;
+  static constexpr uint32_t kDefaultMaxHistory = 4;  // lowest last-frame RMSE of the caps tried
 
   explicit HipBackend(int device = 0);
   ~HipBackend();
@@ -84,6 +90,11 @@ class HipBackend {
   // (waits for that pass), and the AOV passes computed so far
   bool denoiseInfo(double* ms_aov, double* ms_filter, uint32_t* aov_passes) const {
     return ctx_ && sptr_denoise_info(ctx_, ms_aov, ms_filter, aov_passes) == SPTR_OK;
+  }
+  // sptr_history_info of the last render(): pixels that took history, device ms of the reprojection launch
+  // (waits for that pass), whether the pass had a carry
+  bool historyInfo(uint32_t* reprojected, double* ms_reproject, uint32_t* carried) const {
+    return ctx_ && sptr_history_info(ctx_, reprojected, ms_reproject, carried) == SPTR_OK;
   }
   // sptr_query_rays with host pointers: n rays of 8 floats (o3, d3, tnear, tfar) against the built scene,
   // traced by the renderer's traversal.  Closest hit fills geom, prim, t, ng (n x 3) and uv (n x 2) as
@@ -126,6 +137,9 @@ class HipBackend {
   int debug_mode_ = 0;
   uint32_t lanes_applied_ = 0;  // the pixel-lane setting the context holds
   sptr_denoise_params denoise_applied_{};  // the denoiser parameters the context holds
+  sptr_history_params history_applied_{};  // the history parameters the context holds
+  uint32_t seed_offset_ = 0;    // the seed offset the context holds (history on: advanced at every restart)
+  uint32_t acc_frames_ = 0;     // frames of the accumulation the last render() call added to
   sptr_stats flushed_{};        // counters since the last flushStats()
   uint32_t async_calls_ = 0;    // lagged mode: render calls not yet collected
 };

@@ -116,6 +116,11 @@ class DenoiseParams(C.Structure):
                 ("sigma_albedo", C.c_float), ("normal_log2_power", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
+class HistoryParams(C.Structure):
+    """sptr_history_params."""
+    _fields_ = [("max_history", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
 class RayQuery(C.Structure):
     """sptr_ray_query: pointers as addresses (host or device, by SPTR_QUERY_DEVICE_PTRS)."""
     _fields_ = [("rays", C.c_void_p), ("n", C.c_uint32), ("flags", C.c_uint32), ("geom", C.c_void_p),
@@ -124,6 +129,7 @@ class RayQuery(C.Structure):
 
 
 SPTR_AOV_ALBEDO, SPTR_AOV_NORMAL, SPTR_AOV_DEPTH, SPTR_AOV_ID = 0, 1, 2, 3
+DEFAULT_MAX_HISTORY = 4  # the cap to ask set_denoise_history for without a number of one's own
 
 _lib = None
 
@@ -137,6 +143,7 @@ EXPORTS = [
     "sptr_tiles_device", "sptr_unpack_tiles", "sptr_intersect", "sptr_occluded", "sptr_primary_rays",
     "sptr_sort_pairs_u64", "sptr_scan_u32", "sptr_eval_math",
     "sptr_set_denoise", "sptr_read_aov", "sptr_read_denoised", "sptr_denoise_info",
+    "sptr_set_seed_offset", "sptr_set_denoise_history", "sptr_read_history", "sptr_history_info",
     "sptr_set_dynamic", "sptr_update_geometry", "sptr_refit_info",
     "sptr_query_rays", "sptr_query_info",
     "sptr_host_builtin_scene", "sptr_host_scene_view", "sptr_host_scene_free", "sptr_host_camera_lookat",
@@ -196,6 +203,10 @@ def lib() -> C.CDLL:
         "sptr_read_aov": (C.c_int, [vp, C.c_int, vp]),
         "sptr_read_denoised": (C.c_int, [vp, fp]),
         "sptr_denoise_info": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), up]),
+        "sptr_set_seed_offset": (C.c_int, [vp, u32]),
+        "sptr_set_denoise_history": (C.c_int, [vp, C.POINTER(HistoryParams)]),
+        "sptr_read_history": (C.c_int, [vp, fp]),
+        "sptr_history_info": (C.c_int, [vp, up, C.POINTER(C.c_double), up]),
         "sptr_set_dynamic": (C.c_int, [vp, u32]),
         "sptr_update_geometry": (C.c_int, [vp, vp, u32, vp, u32, u32]),
         "sptr_refit_info": (C.c_int, [vp, up, C.POINTER(C.c_double), C.POINTER(C.c_double), up]),
@@ -596,6 +607,30 @@ class Renderer:
         a, f, n = C.c_double(), C.c_double(), C.c_uint32()
         self._check(self._L.sptr_denoise_info(self._h, C.byref(a), C.byref(f), C.byref(n)), "denoise_info")
         return {"ms_aov": a.value, "ms_filter": f.value, "aov_passes": n.value}
+
+    def set_seed_offset(self, offset: int = 0):
+        """sptr_set_seed_offset: wavefront calls seed their frames as accumulation index frame_begin + offset."""
+        self._check(self._L.sptr_set_seed_offset(self._h, offset), "set_seed_offset")
+
+    def set_denoise_history(self, max_history: int = 0, reserved=(0, 0, 0)):
+        """sptr_set_denoise_history: 0 = off, else the cap on a pixel's history length in frames (at most
+        1024); while the denoiser is on, its passes carry the integrated image across restarts of the
+        accumulation (camera moves).  Any call drops the history held."""
+        p = HistoryParams(max_history, (C.c_uint32 * 3)(*reserved))
+        self._check(self._L.sptr_set_denoise_history(self._h, C.byref(p) if (max_history or any(reserved)) else None),
+                    "set_denoise_history")
+
+    def read_history(self) -> np.ndarray:
+        """The last pass's integrated colour t_0 and history length m': (H, W, 4) float32."""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        self._check(self._L.sptr_read_history(self._h, _f(out)), "read_history")
+        return out
+
+    def history_info(self) -> dict:
+        """Of the last pass: pixels that took history, device ms of the reprojection launch, whether it had a carry."""
+        n, ms, k = C.c_uint32(), C.c_double(), C.c_uint32()
+        self._check(self._L.sptr_history_info(self._h, C.byref(n), C.byref(ms), C.byref(k)), "history_info")
+        return {"reprojected": n.value, "ms_reproject": ms.value, "carried": bool(k.value)}
 
     def tiles_device(self) -> tuple[int, int]:
         p = C.c_void_p()

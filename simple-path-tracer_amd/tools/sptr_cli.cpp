@@ -5,7 +5,7 @@
 //   sptr_cli [--scene default|default_emitter|test_triangle|sphere_mesh:STACKS:SLICES|gltf:PATH]
 //            [--w 800] [--h 600] [--spp 4] [--depth 6] [--env sky|FILE.hdr] [--out image.ppm]
 //            [--warmup N] [--json] [--integrator wavefront|pathtracer|optix] [--spf 4] [--launch-mode 0-3]
-//            [--lagged] [--denoise N] [--animate K [--rebuild]] [--query-centre-rays]
+//            [--lagged] [--denoise N] [--history [M]] [--orbit DEG] [--animate K [--rebuild]] [--query-centre-rays]
 // --spp N renders N progressive frames of 1 spp each (GLRenderer's m_accumulated_samples loop);
 // --warmup N renders N untimed frames first (then restarts the accumulation by a camera change);
 // --json prints one line with per-frame wall-clock statistics (render + RGB8 read back, as the
@@ -14,6 +14,12 @@
 // --denoise N: HipBackend::Settings::denoise with N a-trous iterations (1..5, default parameters): every
 // frame comes back filtered, and the --json line's ms_aov / ms_filter are the per-frame means of the
 // pass's device times (sptr_denoise_info; with --lagged, the last frame's alone).
+// --history [M]: HipBackend::Settings::history with the cap M on a pixel's history length (without a number:
+// HipBackend::kDefaultMaxHistory): with --denoise, the passes carry the integrated image across restarts of the
+// accumulation, and every restart draws fresh samples; the --json line's reprojected / ms_reproject are the
+// per-frame means of the pixels that took history and of the reprojection launch's device time.
+// --orbit DEG: before every frame the camera moves on about the target by DEG degrees (about the vertical
+// axis), so that every frame restarts the accumulation: the camera move the history is for.
 // --animate K: K frames of --spp samples each; before frame k > 0 analytic sphere i moves by a fixed step
 // (0.06 sin 1.7i, 0.04 (i mod 3), 0.05 cos 2.3i), the scene goes through HipBackend::update (a refit in
 // place: Settings::dynamic) and the accumulation restarts; the last frame is written.  --rebuild: the same
@@ -59,7 +65,8 @@ int main(int argc, char** argv) {
   bool json = false, lagged = false, rebuild = false, query_centre = false;
   int animate = 0;
   std::string integrator = "wavefront";
-  int spf = 4, launch_mode = 0, denoise = 0;
+  int spf = 4, launch_mode = 0, denoise = 0, history = 0;
+  double orbit = 0.0;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
     auto next = [&](void) -> const char* { return i + 1 < argc ? argv[++i] : ""; };
@@ -77,11 +84,15 @@ int main(int argc, char** argv) {
     else if (a == "--launch-mode") launch_mode = std::atoi(next());
     else if (a == "--lagged") lagged = true;
     else if (a == "--denoise") denoise = std::atoi(next());
+    else if (a == "--history") {
+      history = int(backends::HipBackend::kDefaultMaxHistory);
+      if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') history = std::atoi(next());
+    } else if (a == "--orbit") orbit = std::atof(next());
     else if (a == "--animate") animate = std::atoi(next());
     else if (a == "--rebuild") rebuild = true;
     else if (a == "--query-centre-rays") query_centre = true;
     else {
-      std::fprintf(stderr, "usage: %s [--scene S] [--w W] [--h H] [--spp N] [--depth D] [--env sky|F.hdr] [--out F] [--warmup N] [--json] [--lagged] [--denoise N] [--animate K [--rebuild]] [--query-centre-rays]\n",
+      std::fprintf(stderr, "usage: %s [--scene S] [--w W] [--h H] [--spp N] [--depth D] [--env sky|F.hdr] [--out F] [--warmup N] [--json] [--lagged] [--denoise N] [--history [M]] [--orbit DEG] [--animate K [--rebuild]] [--query-centre-rays]\n",
                    argv[0]);
       return 2;
     }
@@ -116,6 +127,7 @@ int main(int argc, char** argv) {
   st.launch_mode = uint32_t(launch_mode);
   st.lagged_readback = lagged;
   st.denoise.iterations = uint32_t(std::max(0, denoise));
+  st.history.max_history = uint32_t(std::max(0, history));
   st.dynamic = animate > 0 && !rebuild;
   be.setSettings(st);
   if (!be.build(sd)) {
@@ -129,7 +141,7 @@ int main(int argc, char** argv) {
   }
   std::vector<double> frame_ms;
   frame_ms.reserve(size_t(spp) * size_t(std::max(1, animate)));
-  double ms_aov = 0.0, ms_filter = 0.0;
+  double ms_aov = 0.0, ms_filter = 0.0, ms_reproject = 0.0, reprojected = 0.0;
   uint32_t aov_passes = 0;
   int dn_frames = 0;
   (void)be.flushStats();  // (the warmup's counters)
@@ -159,6 +171,11 @@ int main(int argc, char** argv) {
         ms_refit_device += md;
       }
     }
+    if (orbit != 0.0) {  // the next camera on the orbit about the target
+      const double a = orbit * double(f + 1) * 3.14159265358979323846 / 180.0;
+      cam = Camera(vec3{float(8.0 * std::sin(a)), 3.0f, float(8.0 * std::cos(a))}, vec3{0.0f, 1.0f, 0.0f}, vec3{0.0f, 1.0f, 0.0f},
+                   60.0f, float(w) / float(h));
+    }
     const auto f0 = std::chrono::steady_clock::now();
     be.render(img.data(), w, h, cam);
     if (denoise > 0 && (!lagged || f == total_frames - 1)) {  // (waits for the pass: a lagged loop asks once, at its end)
@@ -167,6 +184,12 @@ int main(int argc, char** argv) {
         ms_aov += a;
         ms_filter += fl;
         ++dn_frames;
+      }
+      uint32_t took = 0;
+      double mr = 0.0;
+      if (history > 0 && be.historyInfo(&took, &mr, nullptr)) {
+        reprojected += double(took);
+        ms_reproject += mr;
       }
     }
     frame_ms.push_back(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - f0).count());
@@ -208,10 +231,11 @@ int main(int argc, char** argv) {
     std::printf("{\"scene\": \"%s\", \"launch_mode\": %d, \"width\": %d, \"height\": %d, \"frames\": %d, \"spp_per_frame\": 1, "
                 "\"depth\": %d, \"ms_per_frame_wall\": %.4f, \"ms_per_frame_p50\": %.4f, \"ms_per_frame_p99\": %.4f, "
                 "\"ms_per_frame_device\": %.4f, \"fps\": %.1f, \"mrays_per_s_wall\": %.1f, "
-                "\"lagged_readback\": %s, \"denoise\": %d, \"ms_aov\": %.4f, \"ms_filter\": %.4f, \"aov_passes\": %u, \"animate\": %d, \"refits\": %u, \"ms_refit_wall\": %.4f, \"ms_refit_device\": %.4f, \"ms_build\": %.4f, \"path\": \"backends::HipBackend::render (sptr_render + %s per frame)\"",
+                "\"lagged_readback\": %s, \"denoise\": %d, \"ms_aov\": %.4f, \"ms_filter\": %.4f, \"aov_passes\": %u, \"history\": %d, \"reprojected\": %.1f, \"ms_reproject\": %.4f, \"animate\": %d, \"refits\": %u, \"ms_refit_wall\": %.4f, \"ms_refit_device\": %.4f, \"ms_build\": %.4f, \"path\": \"backends::HipBackend::render (sptr_render + %s per frame)\"",
                 scene_name.c_str(), launch_mode, w, h, total_frames, depth, wall / total_frames, pct(0.5), pct(0.99), ms / total_frames,
                 wall > 0 ? 1e3 * total_frames / wall : 0.0, wall > 0 ? rays / (wall * 1e3) : 0.0, lagged ? "true" : "false", denoise, dn_frames ? ms_aov / dn_frames : 0.0,
-                dn_frames ? ms_filter / dn_frames : 0.0, aov_passes, animate, refits,
+                dn_frames ? ms_filter / dn_frames : 0.0, aov_passes, history, dn_frames ? reprojected / dn_frames : 0.0,
+                dn_frames ? ms_reproject / dn_frames : 0.0, animate, refits,
                 moves && !rebuild ? ms_refit_wall / moves : 0.0, moves && !rebuild ? ms_refit_device / moves : 0.0,
                 moves && rebuild ? ms_build / moves : 0.0,
                 lagged ? "sptr_read_rgb8_lagged" : "sptr_read_rgb8");
