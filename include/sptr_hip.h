@@ -215,6 +215,12 @@ typedef struct sptr_stats {
 
 /* ---- context ---------------------------------------------------------------------------------- */
 int sptr_abi_version(void);
+/* Contexts alive at once in one process: every context creates six streams, which the HIP runtime maps onto
+ * the process's four hardware queues.  The library is tested with the session's context and up to two more
+ * alive at once.  A process that held eight (and had filled the library's per-process table of launch sizes, as
+ * it stood then) saw a later launch-graph replay of the first context end in a host segmentation fault inside
+ * the HIP runtime; which of the two conditions it takes is not established, so hold as few as
+ * the work needs and destroy the ones that are done. */
 int sptr_create(int device, sptr_ctx** out);
 int sptr_destroy(sptr_ctx* ctx);
 const char* sptr_last_error(const sptr_ctx* ctx);

@@ -21,6 +21,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <mutex>
 
 #include "sptr_internal.h"
 
@@ -282,11 +283,13 @@ __device__ __forceinline__ Ray make_ray(vec3 o, vec3 d) {
   Ray r;
   r.o = o;
   r.d = d;
-  // v_rcp_f32 (1 ulp): the inverse direction only feeds the conservative box test
+  // v_rcp_f32 (1 ulp): the inverse direction only feeds the conservative box test.  A component of at most
+  // 1e-20 counts as zero and keeps its sign: its inverse is +-inf (v_rcp_f32 of +-0), which slab() relies on
+  // for rays parallel to a box plane; q_axis caps it at 1e20
   const float eps = 1e-20f;
-  r.inv = v3(__builtin_amdgcn_rcpf(fabsf(d.x) > eps ? d.x : copysignf(eps, d.x)),
-             __builtin_amdgcn_rcpf(fabsf(d.y) > eps ? d.y : copysignf(eps, d.y)),
-             __builtin_amdgcn_rcpf(fabsf(d.z) > eps ? d.z : copysignf(eps, d.z)));
+  r.inv = v3(__builtin_amdgcn_rcpf(fabsf(d.x) > eps ? d.x : copysignf(0.0f, d.x)),
+             __builtin_amdgcn_rcpf(fabsf(d.y) > eps ? d.y : copysignf(0.0f, d.y)),
+             __builtin_amdgcn_rcpf(fabsf(d.z) > eps ? d.z : copysignf(0.0f, d.z)));
   r.oinv = v3(0.0f, 0.0f, 0.0f);
   return r;
 }
@@ -295,13 +298,20 @@ __device__ __forceinline__ Ray make_ray(vec3 o, vec3 d) {
 // form near the origin; the exit distance is padded by 2^-20 relative (~8 ulp) to absorb the
 // subtraction, product and v_rcp rounding, so the test only prunes and never rejects a box that
 // the exact test would accept at a primitive's hit distance.
+// The near and far plane of an axis are chosen by the direction's sign (for a non-zero component the same
+// values as min / max of the two products).  For a component that counts as zero the inverse is +-inf: a
+// plane strictly on one side of the origin gives -+inf (no constraint, or an empty interval when the origin
+// is outside the slab), and a plane the origin lies on gives 0 * inf = NaN, which fmaxf / fminf drop: a ray
+// running inside a box face is inside the box.  (With a finite capped inverse that product was 0, an exit
+// at t = 0: rays through the vertices and edges on a mesh's upper boundary missed everything.)
 __device__ __forceinline__ bool slab(float xlo, float xhi, float ylo, float yhi, float zlo, float zhi, const Ray& r,
                                      float tnear, float tfar, float& tent) {
-  const float tx0 = (xlo - r.o.x) * r.inv.x, tx1 = (xhi - r.o.x) * r.inv.x;
-  const float ty0 = (ylo - r.o.y) * r.inv.y, ty1 = (yhi - r.o.y) * r.inv.y;
-  const float tz0 = (zlo - r.o.z) * r.inv.z, tz1 = (zhi - r.o.z) * r.inv.z;
-  const float tmin = fmaxf(fmaxf(fminf(tx0, tx1), fminf(ty0, ty1)), fmaxf(fminf(tz0, tz1), tnear));
-  const float tmax = fminf(fminf(fmaxf(tx0, tx1), fmaxf(ty0, ty1)), fminf(fmaxf(tz0, tz1), tfar));
+  const bool px = r.inv.x >= 0.0f, py = r.inv.y >= 0.0f, pz = r.inv.z >= 0.0f;
+  const float tx0 = ((px ? xlo : xhi) - r.o.x) * r.inv.x, tx1 = ((px ? xhi : xlo) - r.o.x) * r.inv.x;
+  const float ty0 = ((py ? ylo : yhi) - r.o.y) * r.inv.y, ty1 = ((py ? yhi : ylo) - r.o.y) * r.inv.y;
+  const float tz0 = ((pz ? zlo : zhi) - r.o.z) * r.inv.z, tz1 = ((pz ? zhi : zlo) - r.o.z) * r.inv.z;
+  const float tmin = fmaxf(fmaxf(tx0, ty0), fmaxf(tz0, tnear));
+  const float tmax = fminf(fminf(tx1, ty1), fminf(tz1, tfar));
   tent = tmin;
   return tmin <= tmax * 1.00000095f;
 }
@@ -512,8 +522,11 @@ struct QAxis {
   uint32_t qn[1], qf[1];
 };
 __device__ __forceinline__ QAxis q_axis(float org, uint32_t ebyte, const uint32_t* qlo, const uint32_t* qhi, float ro,
-                                        float inv) {
+                                        float inv_d) {
   QAxis a;
+  // a direction component that counts as zero (inverse +-inf, make_ray): finite here, so that A, B and the pad stay finite;
+  // the pad's 256 |A| term then exceeds any distance, which accepts a ray running inside a child's plane
+  const float inv = __builtin_amdgcn_fmed3f(inv_d, -1e20f, 1e20f);
   a.A = __uint_as_float(ebyte << 23) * inv;
   const float B = (org - ro) * inv;
   const float pad = __builtin_fmaf(fabsf(a.A), 256.0f, fabsf(B)) * 0x1p-20f;
@@ -3733,6 +3746,8 @@ struct GridCache {
 static unsigned resident_grid(const void* fn, uint32_t lds_bytes) {
   static GridCache cache[64];
   static int cus = 0;
+  static std::mutex mu;  // contexts of one process may launch from different threads
+  const std::lock_guard<std::mutex> lock(mu);
   int per = 0;
   for (GridCache& g : cache)
     if (g.fn == fn && g.lds == lds_bytes) return g.blocks;
@@ -3752,11 +3767,17 @@ static unsigned resident_grid(const void* fn, uint32_t lds_bytes) {
 #endif
   unsigned blocks = (unsigned)(cus * per);
   if (blocks > kMaxSegs) blocks = kMaxSegs;  // producer grids index the segment tables
+  // a full table replaces its entries in turn: a process that has uploaded many scenes (each staged size is
+  // a key) keeps caching its current ones, instead of querying the occupancy again at every launch
+  static unsigned next = 0;
+  bool stored = false;
   for (GridCache& g : cache)
     if (g.fn == nullptr) {
       g = GridCache{fn, lds_bytes, blocks};
+      stored = true;
       break;
     }
+  if (!stored) cache[next++ % 64u] = GridCache{fn, lds_bytes, blocks};
   return blocks;
 }
 

@@ -40,12 +40,21 @@ struct WideBoxes {
 // plane, step 2^e the smallest power of two (e in [-100, 60]) with extent <= 255 * 2^e, qlo =
 // floor((lo - org) / 2^e) and qhi = ceil((hi - org) / 2^e) evaluated in double (exact for the
 // scene's float coordinates), so the decoded box always contains the child box.
+// An axis of zero extent has every plane at org (q = 0) whatever its step; it takes the largest step
+// of the node's other axes (or, with all three flat, 2^-16 of the largest |org|), because q_axis pads
+// a decoded plane by 2^-20 * 256 * 2^e / |d|: with the step 2^-100 that pad was too small to accept a ray
+// parallel to the axis whose origin lies in the node's plane (zero-radius spheres on a line, hit by the
+// ray through them); with the node's own scale it exceeds every distance for such a ray and stays
+// 2^-12 of a step of the other axes for all others.
 __device__ __forceinline__ WideNode quantize_wide(const WideBoxes& b, int n, uint32_t parent) {
   WideNode o;
   float org[3];
+  int es[3];
+  bool flat[3];
   uint32_t ex = (uint32_t)n << 24;
   for (int w = 0; w < 6; ++w)
     for (int j = 0; j < kQWords; ++j) o.q[w][j] = 0u;
+  int emax = -101;
   for (int a = 0; a < 3; ++a) {
     float mn = b.lo[a][0], mx = b.hi[a][0];
     for (int k = 1; k < n; ++k) {
@@ -55,13 +64,27 @@ __device__ __forceinline__ WideNode quantize_wide(const WideBoxes& b, int n, uin
     org[a] = mn;
     const double ext = (double)mx - (double)mn;
     int e = -100;
+    flat[a] = !(ext > 0.0);
     if (ext > 0.0) {
       int x;
       (void)frexp(ext / 255.0, &x);  // ext / 255 in (2^(x-1), 2^x]
       e = x;
       if (ext <= 255.0 * ldexp(1.0, e - 1)) --e;
       e = e < -100 ? -100 : (e > 60 ? 60 : e);
+      emax = e > emax ? e : emax;
     }
+    es[a] = e;
+  }
+  if (emax < -100) {  // a point: the scale of its coordinates
+    const float m = fmaxf(fmaxf(fabsf(org[0]), fabsf(org[1])), fabsf(org[2]));
+    int x = -84;
+    if (m > 0.0f) (void)frexp((double)m, &x);
+    emax = x - 16;
+    emax = emax < -100 ? -100 : (emax > 60 ? 60 : emax);
+  }
+  for (int a = 0; a < 3; ++a) {
+    const float mn = org[a];
+    const int e = flat[a] ? emax : es[a];
     ex |= (uint32_t)(e + 127) << (8 * a);
     const double inv_step = ldexp(1.0, -e);
     for (int k = 0; k < n; ++k) {
