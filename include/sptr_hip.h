@@ -234,6 +234,14 @@ int sptr_set_wave_paths(sptr_ctx* ctx, uint64_t max_paths);
  * of a sharded 1080p frame), none for larger batches; >= max_depth = none.  The image and the query
  * counts do not depend on it. */
 int sptr_set_tail_depth(sptr_ctx* ctx, uint32_t depth);
+/* Bounce chain (a symbol added within ABI 9: no existing struct or entry point changed): the wavefront
+ * bounces 1 .. tail_depth-1 of an LDS-staged one-light scene (with bounce 0's shading) run as one launch, in
+ * which every block traces the continuation rays it wrote itself, instead of one launch per bounce.
+ * 0 = automatic (the default): off for every batch size measured so far (no gain outside the run-to-run
+ * spread); 1 = off; 2 = on wherever it applies (other scenes and the visit-count pass
+ * keep their launch sequence whatever the setting).  The image and the counters do not
+ * depend on it. */
+int sptr_set_bounce_chain(sptr_ctx* ctx, uint32_t mode);
 /* Maximum primitives per BVH leaf range (1..16; 0 = automatic, the default: 8 for scenes staged in
  * LDS, 1 otherwise); applies to the next sptr_upload_scene. */
 int sptr_set_leaf_size(sptr_ctx* ctx, uint32_t max_prims);

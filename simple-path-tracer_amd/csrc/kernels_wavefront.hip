@@ -2359,6 +2359,70 @@ __global__ void __launch_bounds__(kBlock, SPTR_SHADE_WAVES)
 // order of the radiance updates of the two kernels — so no hit-record stream and one launch less
 // per bounce.  Input: the rays of w.segN / rs[d & 1]; output: the continuation rays in this
 // block's segment of w.segH / rs[(d + 1) & 1] (the host alternates the two tables between bounces).
+//
+// bounce_ray is the per-ray body, shared with k_bounce_chain's later phases: the ray of slot id of rin
+// (valid: this thread holds one), its continuation appended to the block's segment [seg0, ..) of rout
+// through the LDS counter s_cnt.  Every lane of the wave calls it together (block_append ballots).
+template <bool kCube>
+__device__ __forceinline__ void bounce_ray(const Staged& sc, const SceneView& sv, const ShadeView& sh, const DevMaterial* smat,
+                                           uint32_t nm, const WaveView& w, const RayStream& rin, const RayStream& rout,
+                                           int depth, bool last, bool valid, uint32_t id, uint32_t seg0, uint32_t* s_cnt,
+                                           Visits& vc, LdsStack& s_stack, uint32_t& rays) {
+  bool cont = false, dirty = false, lit = false;
+  uint32_t p = 0u, rng = 0u;
+  vec3 thr, radv = v3(0.0f, 0.0f, 0.0f), no, nd, so, ldir, contrib;
+  float stfar = 0.0f;
+  if (valid) {
+    const float4 o4 = rin.o[id], d4 = rin.d[id];
+    const vec3 ro = xyz(o4), rd = xyz(d4);
+    p = __float_as_uint(d4.w);
+    rng = __float_as_uint(o4.w);
+    thr = xyz(rin.thr[id]);
+    float tfar = __builtin_huge_valf();
+    uint32_t ref = kNoHit;
+    if (!traverse_w<false, false, false>(sc, sv, make_ray(ro, rd), 0.0f, tfar, ref, vc, s_stack)) {
+      if (sh.debug_mode == 1) {
+        w.rad[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      } else {
+        const vec3 e = env_color<kCube>(sh.env, renormalized_again(rd));
+        w.rad[p] = f4(xyz(w.rad[p]) + thr * e, 0.0f);
+      }
+    } else if (sh.debug_mode == 1) {
+      radv = v3(1.0f, 1.0f, 1.0f);
+      dirty = true;
+    } else {
+      const Surface sf = surface_at(sv, sh, smat, nm, ro, rd, tfar, ref);
+      const vec3 emission = v3(sf.m.emission[0], sf.m.emission[1], sf.m.emission[2]);
+      if (dot(emission, emission) > 0.0f) {
+        radv = xyz(w.rad[p]) + thr * emission;
+        dirty = true;
+      }
+      if (light_faces(sh.lights[0], sf)) lit = light_term(sh.lights[0], sf, -rd, thr, so, ldir, stfar, contrib);
+      cont = continue_path(sf, rd, (uint32_t)depth, thr, rng, no, nd) && !last;
+    }
+  }
+  const uint32_t jn = block_append(s_cnt, cont);
+  if (cont && seg0 + jn >= w.seg_cap) {
+    cont = false;
+    w.tot[kTotOverflow] = 1ull;
+  }
+  if (cont) {
+    rout.o[seg0 + jn] = f4(no, __uint_as_float(rng));
+    rout.d[seg0 + jn] = f4(nd, __uint_as_float(p));
+    rout.thr[seg0 + jn] = f4(thr, 0.0f);
+  }
+  if (lit) {
+    uint32_t ref = kNoHit;
+    ++rays;
+    if (!traverse_w<false, true, false>(sc, sv, make_ray(so, ldir), 1e-4f, stfar, ref, vc, s_stack)) {
+      if (!dirty) radv = xyz(w.rad[p]);
+      dirty = true;
+      radv = radv + contrib;
+    }
+  }
+  if (dirty) w.rad[p] = f4(radv, 0.0f);
+}
+
 template <bool kCube, bool kTimed = false>
 __global__ void __launch_bounds__(kBlock, SPTR_BOUNCE_WAVES)
     k_bounce(SceneView sv, ShadeView sh, FrameView fin, WaveView w, int depth, uint32_t nseg_in) {
@@ -2386,60 +2450,9 @@ __global__ void __launch_bounds__(kBlock, SPTR_BOUNCE_WAVES)
   const Sched sd = block_sched(n);
   for (uint32_t base = sd.first; base < sd.end; base += sd.step) {
     const uint32_t i = base + threadIdx.x;
-    bool cont = false, dirty = false, lit = false;
-    uint32_t p = 0u, rng = 0u;
-    vec3 thr, radv = v3(0.0f, 0.0f, 0.0f), no, nd, so, ldir, contrib;
-    float stfar = 0.0f;
-    if (i < n) {
-      const uint32_t id = seg_slot(s_off, nseg_in, per_in, i);
-      const float4 o4 = rin.o[id], d4 = rin.d[id];
-      const vec3 ro = xyz(o4), rd = xyz(d4);
-      p = __float_as_uint(d4.w);
-      rng = __float_as_uint(o4.w);
-      thr = xyz(rin.thr[id]);
-      float tfar = __builtin_huge_valf();
-      uint32_t ref = kNoHit;
-      if (!traverse_w<false, false, false>(sc, sv, make_ray(ro, rd), 0.0f, tfar, ref, vc, s_stack)) {
-        if (sh.debug_mode == 1) {
-          w.rad[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        } else {
-          const vec3 e = env_color<kCube>(sh.env, renormalized_again(rd));
-          w.rad[p] = f4(xyz(w.rad[p]) + thr * e, 0.0f);
-        }
-      } else if (sh.debug_mode == 1) {
-        radv = v3(1.0f, 1.0f, 1.0f);
-        dirty = true;
-      } else {
-        const Surface sf = surface_at(sv, sh, smat, nm, ro, rd, tfar, ref);
-        const vec3 emission = v3(sf.m.emission[0], sf.m.emission[1], sf.m.emission[2]);
-        if (dot(emission, emission) > 0.0f) {
-          radv = xyz(w.rad[p]) + thr * emission;
-          dirty = true;
-        }
-        if (light_faces(sh.lights[0], sf)) lit = light_term(sh.lights[0], sf, -rd, thr, so, ldir, stfar, contrib);
-        cont = continue_path(sf, rd, (uint32_t)depth, thr, rng, no, nd) && !last;
-      }
-    }
-    const uint32_t jn = block_append(&s_cnt_n, cont);
-    if (cont && sd.seg0 + jn >= w.seg_cap) {
-      cont = false;
-      w.tot[kTotOverflow] = 1ull;
-    }
-    if (cont) {
-      rout.o[sd.seg0 + jn] = f4(no, __uint_as_float(rng));
-      rout.d[sd.seg0 + jn] = f4(nd, __uint_as_float(p));
-      rout.thr[sd.seg0 + jn] = f4(thr, 0.0f);
-    }
-    if (lit) {
-      uint32_t ref = kNoHit;
-      ++rays;
-      if (!traverse_w<false, true, false>(sc, sv, make_ray(so, ldir), 1e-4f, stfar, ref, vc, s_stack)) {
-        if (!dirty) radv = xyz(w.rad[p]);
-        dirty = true;
-        radv = radv + contrib;
-      }
-    }
-    if (dirty) w.rad[p] = f4(radv, 0.0f);
+    const bool valid = i < n;
+    const uint32_t id = valid ? seg_slot(s_off, nseg_in, per_in, i) : 0u;
+    bounce_ray<kCube>(sc, sv, sh, smat, nm, w, rin, rout, depth, last, valid, id, sd.seg0, &s_cnt_n, vc, s_stack, rays);
   }
   for (int off = 32; off > 0; off >>= 1) rays += __shfl_xor(rays, off);
   if (lane_id() == 0u) atomicAdd(&s_rays, rays);
@@ -2463,6 +2476,78 @@ __global__ void __launch_bounds__(kBlock, SPTR_BOUNCE_WAVES)
 // starts after bounce 2), so the lanes stay as full as k_shade's.  Input: the hit records of w.segH (the
 // bounce-0 trace's); output: the rays of bounce 2 in w.segN / rs[0].  No continuation ray of bounce 1 is
 // written or read back, and the k_shade launch and its tail are gone.  
+//
+// bounce01_path is the per-path body, shared with k_bounce_chain's first phase: the bounce-0 hit record of
+// slot `slot` (valid: this thread holds one), its bounce-2 ray appended to the block's segment [seg0, ..) of
+// rout through the LDS counter s_cnt.  Every lane of the wave calls it together (block_append ballots).
+template <bool kCube>
+__device__ __forceinline__ void bounce01_path(const Staged& sc, const SceneView& sv, const ShadeView& sh, const DevMaterial* smat,
+                                              uint32_t nm, const FrameView& f, const ImageDiv& idiv, const WaveView& w,
+                                              const RayStream& rout, bool last1, bool last2, bool valid, uint32_t slot,
+                                              uint32_t seg0, uint32_t* s_cnt, Visits& vc, LdsStack& s_stack, uint32_t& rays,
+                                              uint32_t& traced) {
+  bool cont = false, active = valid;
+  uint32_t p = 0u, rng = 0u;
+  vec3 thr = v3(1.0f, 1.0f, 1.0f), radv = v3(0.0f, 0.0f, 0.0f), ro, rd;
+  if (active) {  // bounce 0's shading (k_shade<true, true>)
+    uint3 h;
+    w.hrec.get(slot, h.x, h.y, h.z);
+    p = h.x;
+    Primary pr;
+    primary_path(f, idiv, p, pr);
+    rng = pr.rng;
+    if (sh.debug_mode == 1) {
+      radv = v3(1.0f, 1.0f, 1.0f);
+      active = false;
+    } else {
+      const Surface sf = surface_at(sv, sh, smat, nm, f.cam_pos, pr.d, __uint_as_float(h.y), h.z);
+      const vec3 emission = v3(sf.m.emission[0], sf.m.emission[1], sf.m.emission[2]);
+      if (dot(emission, emission) > 0.0f) radv = radv + thr * emission;
+      vec3 so, ldir, contrib;
+      float stfar = 0.0f;
+      const bool lit = light_faces(sh.lights[0], sf) && light_term(sh.lights[0], sf, -pr.d, thr, so, ldir, stfar, contrib);
+      active = continue_path(sf, pr.d, 0u, thr, rng, ro, rd) && !last1;
+      if (lit) {
+        uint32_t sref = kNoHit;
+        ++rays;
+        if (!traverse_w<false, true, false>(sc, sv, make_ray(so, ldir), 1e-4f, stfar, sref, vc, s_stack)) radv = radv + contrib;
+      }
+    }
+  }
+  bool lit = false;
+  vec3 no, nd, so, ldir, contrib;
+  float stfar = 0.0f;
+  if (active) {  // bounce 1 (k_bounce, depth 1): radv holds what rad[p] would
+    ++traced;
+    float tfar = __builtin_huge_valf();
+    uint32_t ref = kNoHit;
+    if (!traverse_w<false, false, false>(sc, sv, make_ray(ro, rd), 0.0f, tfar, ref, vc, s_stack)) {
+      radv = radv + thr * env_color<kCube>(sh.env, renormalized_again(rd));
+    } else {
+      const Surface sf = surface_at(sv, sh, smat, nm, ro, rd, tfar, ref);
+      const vec3 emission = v3(sf.m.emission[0], sf.m.emission[1], sf.m.emission[2]);
+      if (dot(emission, emission) > 0.0f) radv = radv + thr * emission;
+      if (light_faces(sh.lights[0], sf)) lit = light_term(sh.lights[0], sf, -rd, thr, so, ldir, stfar, contrib);
+      cont = continue_path(sf, rd, 1u, thr, rng, no, nd) && !last2;
+    }
+  }
+  const uint32_t jn = block_append(s_cnt, cont);
+  if (cont && seg0 + jn >= w.seg_cap) {
+    cont = false;
+    w.tot[kTotOverflow] = 1ull;  // cannot happen (ensure_wave slack); reported, never written
+  }
+  if (cont) {
+    rout.o[seg0 + jn] = f4(no, __uint_as_float(rng));
+    rout.d[seg0 + jn] = f4(nd, __uint_as_float(p));
+    rout.thr[seg0 + jn] = f4(thr, 0.0f);
+  }
+  if (lit) {
+    uint32_t sref = kNoHit;
+    ++rays;
+    if (!traverse_w<false, true, false>(sc, sv, make_ray(so, ldir), 1e-4f, stfar, sref, vc, s_stack)) radv = radv + contrib;
+  }
+  if (valid) w.rad[p] = f4(radv, 0.0f);
+}
 #ifndef SPTR_BOUNCE01_WAVES
 #define SPTR_BOUNCE01_WAVES 5
 #endif
@@ -2489,67 +2574,10 @@ __global__ void __launch_bounds__(kBlock, SPTR_BOUNCE01_WAVES)
   const Sched sd = block_sched(n);
   for (uint32_t base = sd.first; base < sd.end; base += sd.step) {
     const uint32_t i = base + threadIdx.x;
-    bool cont = false, active = i < n;
-    uint32_t p = 0u, rng = 0u;
-    vec3 thr = v3(1.0f, 1.0f, 1.0f), radv = v3(0.0f, 0.0f, 0.0f), ro, rd;
-    if (active) {  // bounce 0's shading (k_shade<true, true>)
-      uint3 h;
-      w.hrec.get(seg_slot(s_off, nseg_in, per_in, i), h.x, h.y, h.z);
-      p = h.x;
-      Primary pr;
-      primary_path(f, idiv, p, pr);
-      rng = pr.rng;
-      if (sh.debug_mode == 1) {
-        radv = v3(1.0f, 1.0f, 1.0f);
-        active = false;
-      } else {
-        const Surface sf = surface_at(sv, sh, smat, nm, f.cam_pos, pr.d, __uint_as_float(h.y), h.z);
-        const vec3 emission = v3(sf.m.emission[0], sf.m.emission[1], sf.m.emission[2]);
-        if (dot(emission, emission) > 0.0f) radv = radv + thr * emission;
-        vec3 so, ldir, contrib;
-        float stfar = 0.0f;
-        const bool lit = light_faces(sh.lights[0], sf) && light_term(sh.lights[0], sf, -pr.d, thr, so, ldir, stfar, contrib);
-        active = continue_path(sf, pr.d, 0u, thr, rng, ro, rd) && !last1;
-        if (lit) {
-          uint32_t sref = kNoHit;
-          ++rays;
-          if (!traverse_w<false, true, false>(sc, sv, make_ray(so, ldir), 1e-4f, stfar, sref, vc, s_stack)) radv = radv + contrib;
-        }
-      }
-    }
-    bool lit = false;
-    vec3 no, nd, so, ldir, contrib;
-    float stfar = 0.0f;
-    if (active) {  // bounce 1 (k_bounce, depth 1): radv holds what rad[p] would
-      ++traced;
-      float tfar = __builtin_huge_valf();
-      uint32_t ref = kNoHit;
-      if (!traverse_w<false, false, false>(sc, sv, make_ray(ro, rd), 0.0f, tfar, ref, vc, s_stack)) {
-        radv = radv + thr * env_color<kCube>(sh.env, renormalized_again(rd));
-      } else {
-        const Surface sf = surface_at(sv, sh, smat, nm, ro, rd, tfar, ref);
-        const vec3 emission = v3(sf.m.emission[0], sf.m.emission[1], sf.m.emission[2]);
-        if (dot(emission, emission) > 0.0f) radv = radv + thr * emission;
-        if (light_faces(sh.lights[0], sf)) lit = light_term(sh.lights[0], sf, -rd, thr, so, ldir, stfar, contrib);
-        cont = continue_path(sf, rd, 1u, thr, rng, no, nd) && !last2;
-      }
-    }
-    const uint32_t jn = block_append(&s_cnt_n, cont);
-    if (cont && sd.seg0 + jn >= w.seg_cap) {
-      cont = false;
-      w.tot[kTotOverflow] = 1ull;  // cannot happen (ensure_wave slack); reported, never written
-    }
-    if (cont) {
-      rout.o[sd.seg0 + jn] = f4(no, __uint_as_float(rng));
-      rout.d[sd.seg0 + jn] = f4(nd, __uint_as_float(p));
-      rout.thr[sd.seg0 + jn] = f4(thr, 0.0f);
-    }
-    if (lit) {
-      uint32_t sref = kNoHit;
-      ++rays;
-      if (!traverse_w<false, true, false>(sc, sv, make_ray(so, ldir), 1e-4f, stfar, sref, vc, s_stack)) radv = radv + contrib;
-    }
-    if (i < n) w.rad[p] = f4(radv, 0.0f);
+    const bool valid = i < n;
+    const uint32_t slot = valid ? seg_slot(s_off, nseg_in, per_in, i) : 0u;
+    bounce01_path<kCube>(sc, sv, sh, smat, nm, f, idiv, w, rout, last1, last2, valid, slot, sd.seg0, &s_cnt_n, vc, s_stack, rays,
+                         traced);
   }
   for (int off = 32; off > 0; off >>= 1) {
     rays += __shfl_xor(rays, off);
@@ -2567,6 +2595,107 @@ __global__ void __launch_bounds__(kBlock, SPTR_BOUNCE01_WAVES)
     if (blockIdx.x == 0) *w.segN.per = sd.per;
     atomicAdd(&w.tot[kTotClosest], (unsigned long long)s_traced);
     atomicAdd(&w.tot[kTotTracedF], (unsigned long long)s_traced);
+    atomicAdd(&w.tot[kTotTracedD + 1], (unsigned long long)s_traced);
+  }
+  if constexpr (kTimed) ktime_end(w);
+}
+
+// --------------------------------------------------------------------------------- k_bounce_chain
+// Bounces 1 .. T-1 (with bounce 0's shading) of an LDS-staged one-light scene in one launch: k_bounce01's
+// loop as phase 1, then one phase per bounce d = 2 .. T-1 in which the block traces the rays it wrote itself.
+// A path's bounce d + 1 depends only on that path's bounce d (its own rad[p], its own rng), so the block's
+// output segment [seg0, seg0 + count) of rs[(d + 1) & 1] is its input of the next phase: no grid-wide
+// ordering, no seg_scan / seg_slot after phase 1, scene and materials staged once, and per launch one ramp
+// and one drain instead of T - 1.  Per ray the phases run bounce_ray, k_bounce's body, so the operations and
+// the order of the rad[p] updates are those of the separate launches; which block and lane a path runs on
+// does not enter a result.  Output never exceeds input, so phase 1's segment stride bounds every phase.
+// Every ray-stream slot a block touches lies in its own segment (phase 1 reads hit records, which no phase
+// writes), which is what lets the two streams ping-pong without a grid-wide boundary: a chain that began
+// with a dealt k_bounce phase would overwrite, from its second phase on, input rays that slower blocks
+// have not read yet.
+//
+// Between phases: __syncthreads(), whose workgroup-scope release/acquire fence orders the block's global
+// stores (ray streams, rad[]) before its own later loads.  Producer and consumer are waves of one
+// workgroup, which share their CU's L1, so workgroup scope is enough; an agent-scope fence
+// (__threadfence) would add an L2 write-back per thread and is not used (the form k_refit_nodes_block
+// takes between heights).  Every thread reaches every barrier: the phase loops run on block-uniform counts.
+// The phases' append counters rotate over three LDS words (phase d appends to s_cnt[d % 3], reads its input
+// count from s_cnt[(d - 1) % 3] and zeroes s_cnt[(d + 1) % 3], last read one barrier earlier), so one
+// barrier per phase suffices.
+//
+// T < D: the block's last count and the stride go to w.segN, which k_tail scans next, and its rays are in
+// rs[T & 1].  (Never to w.segH, whatever the parity of T: a block that is dispatched late still scans it
+// for phase 1 when the first blocks publish.)  T >= D: the last phase ends every path, nothing is
+// published.  Tallies as the launches it replaces: one atomic per block and depth for traced_by_depth, the
+// any-hit queries in bstat.
+#ifndef SPTR_CHAIN_WAVES
+#define SPTR_CHAIN_WAVES 6  // 8-way C2 shard 0.455-0.458 ms at 5 (k_bounce01's), 0.445 at 6
+#endif
+template <bool kCube, bool kTimed = false>
+__global__ void __launch_bounds__(kBlock, SPTR_CHAIN_WAVES)
+    k_bounce_chain(SceneView sv, ShadeView sh, FrameView fin, WaveView w, int T, uint32_t nseg_in) {
+  if constexpr (kTimed) ktime_begin(w);
+  const FrameView f = frame_dyn(fin);
+  extern __shared__ float4 lds[];
+  uint32_t* s_off = reinterpret_cast<uint32_t*>(lds + sv.lds_bytes / 16u);
+  __shared__ DevMaterial smat[32];
+  __shared__ uint32_t s_cnt[3], s_rays, s_traced;
+  __shared__ LdsStack s_stack;
+  const uint32_t nm = stage_materials(sh, smat);
+  if (threadIdx.x == 0) s_cnt[0] = s_cnt[1] = s_cnt[2] = s_rays = s_traced = 0u;
+  const Staged sc = stage_scene<true>(sv, lds);
+  uint32_t per_in = 0u;
+  const uint32_t n = seg_scan(w.segH, nseg_in, s_off, per_in);
+  const bool last1 = 1u >= f.max_depth, last2 = 2u >= f.max_depth;
+  const ImageDiv idiv = image_div(f);
+  Visits vc;
+  uint32_t rays = 0u, traced = 0u;
+  const Sched sd = block_sched(n);
+  {  // phase 1: bounce 0's shading and bounce 1 (k_bounce01), appended to s_cnt[1]
+    const RayStream rout = w.rs[0];
+    for (uint32_t base = sd.first; base < sd.end; base += sd.step) {
+      const uint32_t i = base + threadIdx.x;
+      const bool valid = i < n;
+      const uint32_t slot = valid ? seg_slot(s_off, nseg_in, per_in, i) : 0u;
+      bounce01_path<kCube>(sc, sv, sh, smat, nm, f, idiv, w, rout, last1, last2, valid, slot, sd.seg0, &s_cnt[1], vc, s_stack,
+                           rays, traced);
+    }
+  }
+  unsigned long long later = 0ull;  // (thread 0) rays traced by the phases from 2 on
+  for (int d = 2; d < T; ++d) {
+    __syncthreads();  // phase d - 1's rays and radiance before this phase's loads; its count is final
+    const uint32_t cnt = s_cnt[(d - 1) % 3];
+    if (threadIdx.x == 0) {
+      s_cnt[(d + 1) % 3] = 0u;
+      if (cnt) atomicAdd(&w.tot[kTotTracedD + stat_depth(d)], (unsigned long long)cnt);
+      later += cnt;
+    }
+    const RayStream rin = w.rs[d & 1], rout = w.rs[(d + 1) & 1];
+    const bool last = (uint32_t)(d + 1) >= f.max_depth;
+    for (uint32_t j = 0u; j < cnt; j += kBlock) {
+      const uint32_t id = sd.seg0 + j + threadIdx.x;
+      const bool valid = j + threadIdx.x < cnt && id < w.seg_cap;  // (an overflowing append was reported, not written)
+      bounce_ray<kCube>(sc, sv, sh, smat, nm, w, rin, rout, d, last, valid, id, sd.seg0, &s_cnt[d % 3], vc, s_stack, rays);
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    rays += __shfl_xor(rays, off);
+    traced += __shfl_xor(traced, off);
+  }
+  if (lane_id() == 0u) {
+    atomicAdd(&s_rays, rays);
+    atomicAdd(&s_traced, traced);
+  }
+  report_stack(vc, w.tot);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    if ((uint32_t)T < f.max_depth) {
+      w.segN.cnt[logical_block()] = s_cnt[(T - 1) % 3];
+      if (blockIdx.x == 0) *w.segN.per = sd.per;
+    }
+    w.bstat[blockIdx.x] += s_rays;
+    atomicAdd(&w.tot[kTotClosest], (unsigned long long)s_traced + later);
+    atomicAdd(&w.tot[kTotTracedF], (unsigned long long)s_traced + later);
     atomicAdd(&w.tot[kTotTracedD + 1], (unsigned long long)s_traced);
   }
   if constexpr (kTimed) ktime_end(w);
@@ -4002,6 +4131,21 @@ unsigned launch_bounce01(const SceneView& sv, const ShadeView& sh, const FrameVi
         return [&]<bool Cube, bool T>(Flags<Cube, T>) {
           const unsigned g = resident_grid((const void*)&k_bounce01<Cube, T>, lb);
           SPTR_TIMED_LAUNCH((k_bounce01<Cube, T>), dim3(g), dim3(kBlock), lb, s, sv, sh, f, w, nseg);
+          return g;
+        }(fl);
+      },
+      Flags<>{}, sh.env.env != nullptr, w.tslot != nullptr);
+}
+
+unsigned launch_bounce_chain(const SceneView& sv, const ShadeView& sh, const FrameView& f, const WaveView& w_in, int T,
+                             uint32_t nseg, hipStream_t s) {
+  const WaveView w = with_tslot(w_in);
+  const unsigned lb = sv.lds_bytes + (4u * (nseg + 1u) + 15u) / 16u * 16u;
+  return dispatch(
+      [&](auto fl) -> unsigned {
+        return [&]<bool Cube, bool Tm>(Flags<Cube, Tm>) {
+          const unsigned g = resident_grid((const void*)&k_bounce_chain<Cube, Tm>, lb);
+          SPTR_TIMED_LAUNCH((k_bounce_chain<Cube, Tm>), dim3(g), dim3(kBlock), lb, s, sv, sh, f, w, T, nseg);
           return g;
         }(fl);
       },

@@ -160,6 +160,24 @@ uint32_t auto_tail_depth(uint64_t batch_paths, const SceneView& sv) {
   if (sv.lds_bytes == 0u) return sv.scene_bytes <= (4ull << 20) ? 2u : 3u;
   return batch_paths <= kSmallBatchPaths ? kSmallBatchTailDepth : (uint32_t)kMaxDepth;
 }
+// Bounces 1 .. T-1 of an LDS-staged one-light scene as one launch whose blocks trace the continuation rays
+// they wrote themselves (k_bounce_chain) instead of k_bounce01 and one k_bounce per bounce
+// (sptr_set_bounce_chain: 1 never, 2 wherever those kernels run).
+// Automatic policy (mode 0): off.  Measured on MI355X, bench.py runs alternated on one box (C2, two lanes,
+// ms/step, separate launches -> chain; profiles/r07_chain_ab.txt).  The chain is bounces 1 .. 3 in the sharded
+// frames (tail from bounce 4) and 1 .. 5 on one GPU:
+//   8-way shard (2^23 paths per lane batch), same build with the chain off / on, five runs each:
+//   0.452-0.454 -> 0.452-0.457; against the parent build 0.457-0.461 -> 0.443-0.451 on one box and
+//   0.450-0.455 -> 0.448-0.454 on another: not told from the spread;
+//   4-way (2^24) 0.720-0.725 -> 0.723-0.726 and 2-way (2^25) 1.319-1.325 -> 1.321-1.333: inside the spread;
+//   1 GPU (2^26) 2.286-2.286 -> 2.347-2.355: slower.  Nothing re-deals the rays between the phases, and one
+//   launch bound serves both k_bounce01's registers (96, 5 waves/SIMD) and k_bounce's occupancy (80, 6): at 5
+//   the 8-way shard was 0.449-0.454 -> 0.455-0.458 and 1 GPU 2.294-2.298 -> 2.468-2.472, so the chain runs at 6.
+// No batch size gains outside the spread, so only mode 2 takes the chain.
+bool bounce_chain_on(const Context& c, uint64_t batch_paths) {
+  (void)batch_paths;
+  return c.bounce_chain == 2u;
+}
 
 // MaterialManager::getMaterialFromHit (src/MaterialManager.cpp:91-103): the geomID's mapped
 // material when it is in range, else MaterialManager::getMaterialByID(geomID) (:79-89).
@@ -935,6 +953,18 @@ uint32_t enqueue_wavefront(Context& c, const sptr_frame& f, uint32_t k, int T, h
           launch_strag(sv, sh, fv, w, d, s);
         }
       }
+      if (d == 0 && fuse_bounce && T >= 2 && D >= 2 && bounce_chain_on(c, (uint64_t)kk * c.P)) {
+        // bounce 0's shading and bounces 1 .. T-1 in one launch (k_bounce_chain) in place of k_bounce01 and the
+        // fused bounces' launches: the rays of bounce T (if the tail follows) are in rs[T & 1], counted in w.segN
+        const int Tc = std::min(T, D);
+        tm.begin(9);
+        g_shade = launch_bounce_chain(sv, sh, fv, w, Tc, g_trace, s);
+        tm.end();
+        rays_tab = w.segN;
+        spare_tab = w.segH;
+        d = Tc - 1;
+        continue;
+      }
       if (d == 0 && fuse && !no_bounce && T >= 2 && D >= 2) {
         // bounce 0's shading and bounce 1 in one launch (k_bounce01), in batches of every size: its rays of
         // bounce 2 go to w.segN, where the fused bounces from 2 on (or k_trace(2)) take them.  r06 A/B on one
@@ -1449,6 +1479,13 @@ static int set_tail_depth_one(sptr_ctx* x, uint32_t depth) {
   return SPTR_OK;
 }
 
+static int set_bounce_chain_one(sptr_ctx* x, uint32_t mode) {
+  if (!x) return SPTR_ERR_INVALID;
+  if (mode > 2u) return fail(x->c, SPTR_ERR_INVALID, "bounce chain must be 0 (automatic), 1 (off) or 2 (on)");
+  x->c.bounce_chain = mode;  // (part of the launch-graph key: sptr_render)
+  return SPTR_OK;
+}
+
 static int set_split_refs_one(sptr_ctx* x, uint32_t max_pieces) {
   if (!x) return SPTR_ERR_INVALID;
   if (max_pieces == 0u) max_pieces = 1u;
@@ -1697,6 +1734,7 @@ static int render_one(sptr_ctx* x, const sptr_frame* f, void* stream, sptr_stats
     key.epoch = c.epoch;  // ensure_wave may have reallocated
     key.k = k;
     key.tail = (uint32_t)T;
+    key.chain = c.bounce_chain;
     if (c.pending == 0) API_HIP(hipMemsetAsync(c.w_tot.p, 0, kTotWords * 8, s));
     rc = refresh_cull(c, *f, s, timing || trace_timing);
     if (rc != SPTR_OK) return rc;
@@ -2941,6 +2979,11 @@ int sptr_set_bvh_width(sptr_ctx* x, uint32_t width) {
 int sptr_set_tail_depth(sptr_ctx* x, uint32_t depth) {
   const int rc = set_tail_depth_one(x, depth);
   return rc == SPTR_OK ? lane_forward(x, set_tail_depth_one(x ? x->lane : nullptr, depth)) : rc;
+}
+
+int sptr_set_bounce_chain(sptr_ctx* x, uint32_t mode) {
+  const int rc = set_bounce_chain_one(x, mode);
+  return rc == SPTR_OK ? lane_forward(x, set_bounce_chain_one(x ? x->lane : nullptr, mode)) : rc;
 }
 
 int sptr_set_split_refs(sptr_ctx* x, uint32_t max_pieces) {

@@ -387,6 +387,7 @@ struct GraphKey {
   uint64_t epoch;
   sptr_frame frame;
   uint32_t k, tail;
+  uint32_t chain, spare;  // sptr_set_bounce_chain's mode (spare: zero, keeps the key free of padding)
 };
 struct GraphCache {
   bool valid = false;
@@ -466,6 +467,7 @@ struct Context {
   int debug_mode = 0;
   uint64_t wave_paths = 0;  // 0 = default
   uint32_t tail_depth = 0;  // first bounce traced path-per-thread by k_tail (0 = automatic)
+  uint32_t bounce_chain = 0;  // sptr_set_bounce_chain: 0 automatic, 1 off, 2 on wherever applicable
   // scene
   DevBuf nodes, prim_ref, tris, sph, tri_geom, sph_geom, tri_orig, sph_orig, geom_mat;
   DevBuf tri_mat;  // ShadeView::tri_mat (resolve_geom_materials)
@@ -558,6 +560,10 @@ unsigned launch_bounce01(const SceneView& sv, const ShadeView& sh, const FrameVi
 // one fused bounce (k_bounce): rays of w.segN in, continuation rays of w.segH out
 unsigned launch_bounce(const SceneView& sv, const ShadeView& sh, const FrameView& f, const WaveView& w, int depth,
                        uint32_t nseg, hipStream_t s);
+// bounce 0's shading and bounces 1 .. T-1 in one launch (k_bounce_chain, 2 <= T <= max_depth): bounce 0's hit
+// records of w.segH in; with T < max_depth the rays of bounce T out in rs[T & 1], counted in w.segN
+unsigned launch_bounce_chain(const SceneView& sv, const ShadeView& sh, const FrameView& f, const WaveView& w, int T,
+                             uint32_t nseg, hipStream_t s);
 unsigned launch_tail(const SceneView& sv, const ShadeView& sh, const FrameView& f, const WaveView& w, int depth0,
                      uint32_t nseg_in, hipStream_t s);
 unsigned launch_shadow(const SceneView& sv, const ShadeView& sh, const WaveView& w, int depth, bool count, uint32_t nseg_in,

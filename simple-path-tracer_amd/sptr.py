@@ -136,7 +136,7 @@ _lib = None
 # every symbol include/sptr_hip.h declares
 EXPORTS = [
     "sptr_abi_version", "sptr_create", "sptr_destroy", "sptr_last_error", "sptr_set_debug_mode",
-    "sptr_set_wave_paths", "sptr_set_launch_mode", "sptr_set_pixel_lanes", "sptr_pixel_lanes_info", "sptr_graph_info", "sptr_capture_error", "sptr_overlap_probe", "sptr_set_tail_depth", "sptr_set_leaf_size", "sptr_set_split_refs", "sptr_set_stragglers", "sptr_set_bvh_width", "sptr_upload_scene", "sptr_set_materials", "sptr_set_lights",
+    "sptr_set_wave_paths", "sptr_set_launch_mode", "sptr_set_pixel_lanes", "sptr_pixel_lanes_info", "sptr_graph_info", "sptr_capture_error", "sptr_overlap_probe", "sptr_set_tail_depth", "sptr_set_bounce_chain", "sptr_set_leaf_size", "sptr_set_split_refs", "sptr_set_stragglers", "sptr_set_bvh_width", "sptr_upload_scene", "sptr_set_materials", "sptr_set_lights",
     "sptr_set_environment", "sptr_scene_info", "sptr_scene_layout_info", "sptr_render", "sptr_collect_stats",
     "sptr_read_rgb8", "sptr_read_rgb8_lagged",
     "sptr_read_accum",
@@ -176,6 +176,7 @@ def lib() -> C.CDLL:
         "sptr_capture_error": (C.c_char_p, [vp]),
         "sptr_overlap_probe": (C.c_int, [vp, C.POINTER(C.c_double)]),
         "sptr_set_tail_depth": (C.c_int, [vp, u32]),
+        "sptr_set_bounce_chain": (C.c_int, [vp, u32]),
         "sptr_set_leaf_size": (C.c_int, [vp, u32]),
         "sptr_set_split_refs": (C.c_int, [vp, u32]),
         "sptr_set_stragglers": (C.c_int, [vp, u32]),
@@ -522,6 +523,10 @@ class Renderer:
 
     def set_tail_depth(self, n: int):
         self._check(self._L.sptr_set_tail_depth(self._h, n), "set_tail_depth")
+
+    def set_bounce_chain(self, mode: int):
+        """0 automatic, 1 off (one launch per bounce), 2 on wherever applicable (sptr_set_bounce_chain)."""
+        self._check(self._L.sptr_set_bounce_chain(self._h, mode), "set_bounce_chain")
 
     def set_leaf_size(self, n: int):
         self._check(self._L.sptr_set_leaf_size(self._h, n), "set_leaf_size")
