@@ -2353,6 +2353,7 @@ __global__ void __launch_bounds__(kBlock, SPTR_SHADE_WAVES)
 }
 
 // --------------------------------------------------------------------------------- k_bounce
+// (The launch per fused bounce of the small batches; larger ones run k_shade_trace: launch_bounce.)
 // One whole bounce d >= 1 of an LDS-staged one-light scene in one launch: k_trace (closest hit; a
 // miss adds thr * env to rad[p]) and k_shade with its in-place shadow ray (emission, the light's
 // contribution if unoccluded, continuation) per queued ray, with the per-path operations and the
@@ -2467,6 +2468,7 @@ __global__ void __launch_bounds__(kBlock, SPTR_BOUNCE_WAVES)
 }
 
 // --------------------------------------------------------------------------------- k_bounce01
+// (The first fused launch of the small batches; larger ones run k_shade_trace<first>: launch_bounce01.)
 // The shading of bounce 0's hits and the whole of bounce 1 in one launch (LDS-staged one-light scenes whose
 // bounces fuse, after a lane-group or pixel-major bounce 0): per hit record of bounce 0, k_shade<primary,
 // fuse>'s steps (the path's camera ray recomputed from its id, emission, the light's contribution if its
@@ -2697,6 +2699,205 @@ __global__ void __launch_bounds__(kBlock, SPTR_CHAIN_WAVES)
     atomicAdd(&w.tot[kTotClosest], (unsigned long long)s_traced + later);
     atomicAdd(&w.tot[kTotTracedF], (unsigned long long)s_traced + later);
     atomicAdd(&w.tot[kTotTracedD + 1], (unsigned long long)s_traced);
+  }
+  if constexpr (kTimed) ktime_end(w);
+}
+
+// --------------------------------------------------------------------------------- k_shade_trace
+// The fused bounce launches of an LDS-staged one-light scene, cut after the trace instead of after the
+// shading: launch d (1 <= d < T) shades the hits of bounce d - 1 and then traces bounce d.  Its input is a
+// dense stream of hits, so every lane of a wave runs the shading (surface, emission, the light's term and its
+// in-place shadow ray, the continuation), which k_bounce issued for whole waves with the lanes that missed
+// masked off (about half of them on C2).  Its output is the dense stream of bounce d's hits: a miss adds
+// thr * env and the path ends there, the last thing the lane does.
+//
+// Hit-ray record (RayStream slot j): the ray that was traced and what it hit — o = {origin, rng}, d =
+// {direction, path id}, thr = {throughput, t}, ref[j] = the primitive; throughput and rng as the previous
+// shading left them.  A launch emits at most one record per input record, so the segment strides of the
+// first launch's input bound every later stream.
+//
+// kFirst (d = 1): the input is bounce 0's hit records (w.segH / hrec), the camera ray is recomputed from the
+// path id, and the radiance starts at zero in a register and is written once.  Later launches read the
+// records of w.segN / rs[d & 1] and update rad[p] lazily (read when something is first added, written back
+// once).  Output: w.segN / rs[0] of the first launch, w.segH / rs[(d + 1) & 1] of a later one (the host
+// alternates the two tables).
+//
+// kClose (d = T - 1, the last wavefront bounce): the hits of bounce d are shaded in the lane that traced them
+// (k_bounce's steps), and what is written are plain continuation rays for k_tail — or nothing when d is the
+// path's last bounce, where the continuation is not computed at all (`last` is uniform).
+//
+// Per path the radiance updates keep the order of the separate launches — emission(d - 1), the light's
+// contribution(d - 1) if unoccluded, thr * env(d) on a miss — with the same operands, so rad[], the images
+// and every tally are those of k_trace / k_shade / k_shadow and of bounce01_path / bounce_ray.
+//
+// Waves per SIMD (C2, two lanes, ms/step, builds alternated on one box, three runs each; this build
+// 2.170-2.174; profiles/r08_bounce_order_ab.txt): no instantiation spills a VGPR at its bound.
+#ifndef SPTR_ST_FIRST_WAVES
+#define SPTR_ST_FIRST_WAVES 5  // 96 VGPRs; at 6 (80): 2.179-2.197
+#endif
+#ifndef SPTR_ST_WAVES
+#define SPTR_ST_WAVES 6  // 80 VGPRs; at 5: 2.184-2.187
+#endif
+#ifndef SPTR_ST_CLOSE_WAVES
+#define SPTR_ST_CLOSE_WAVES 5  // 96 VGPRs; at 6: 2.171-2.175, not told apart (one launch per chain)
+#endif
+// radv += c, where radv holds rad[p] from the first addition on (dirty)
+__device__ __forceinline__ void rad_add(const WaveView& w, uint32_t p, bool& dirty, vec3& radv, vec3 c) {
+  if (!dirty) radv = xyz(w.rad[p]);
+  dirty = true;
+  radv = radv + c;
+}
+// One lit light's in-place shadow ray (Light::isOccluded): the contribution is added if nothing is hit.
+__device__ __forceinline__ void shadow_add(const Staged& sc, const SceneView& sv, const WaveView& w, uint32_t p, vec3 so,
+                                           vec3 ldir, float stfar, vec3 contrib, bool& dirty, vec3& radv, Visits& vc,
+                                           LdsStack& s_stack, uint32_t& rays) {
+  uint32_t sref = kNoHit;
+  ++rays;
+  if (!traverse_w<false, true, false>(sc, sv, make_ray(so, ldir), 1e-4f, stfar, sref, vc, s_stack))
+    rad_add(w, p, dirty, radv, contrib);
+}
+// The per-record body: the record of slot `slot` (valid: this thread holds one), its output appended to the
+// block's segment [seg0, ..) of rout through the LDS counter s_cnt.  Every lane of the wave calls it together
+// (block_append ballots).  depth: the bounce traced; last: depth is the path's last bounce.
+template <bool kCube, bool kFirst, bool kClose>
+__device__ __forceinline__ void shade_trace(const Staged& sc, const SceneView& sv, const ShadeView& sh, const DevMaterial* smat,
+                                            uint32_t nm, const FrameView& f, const ImageDiv& idiv, const WaveView& w,
+                                            const RayStream& rin, const RayStream& rout, int depth, bool last, bool valid,
+                                            uint32_t slot, uint32_t seg0, uint32_t* s_cnt, Visits& vc, LdsStack& s_stack,
+                                            uint32_t& rays, uint32_t& traced) {
+  bool active = false, dirty = kFirst && valid, lit = false;
+  uint32_t p = 0u, rng = 0u;
+  vec3 thr = v3(1.0f, 1.0f, 1.0f), radv = v3(0.0f, 0.0f, 0.0f), no, nd, so, ldir, contrib;
+  float stfar = 0.0f;
+  if (valid) {  // shade(depth - 1)
+    vec3 ro, rd;
+    float t;
+    uint32_t ref;
+    if constexpr (kFirst) {
+      uint32_t tb;
+      w.hrec.get(slot, p, tb, ref);
+      t = __uint_as_float(tb);
+      Primary pr;
+      primary_path(f, idiv, p, pr);
+      ro = f.cam_pos;
+      rd = pr.d;
+      rng = pr.rng;
+    } else {
+      const float4 o4 = rin.o[slot], d4 = rin.d[slot], t4 = rin.thr[slot];
+      ref = rin.ref[slot];
+      ro = xyz(o4);
+      rd = xyz(d4);
+      thr = xyz(t4);
+      t = t4.w;
+      rng = __float_as_uint(o4.w);
+      p = __float_as_uint(d4.w);
+    }
+    if (sh.debug_mode == 1) {
+      radv = v3(1.0f, 1.0f, 1.0f);
+      dirty = true;
+    } else {
+      const Surface sf = surface_at(sv, sh, smat, nm, ro, rd, t, ref);
+      const vec3 emission = v3(sf.m.emission[0], sf.m.emission[1], sf.m.emission[2]);
+      if (dot(emission, emission) > 0.0f) rad_add(w, p, dirty, radv, thr * emission);
+      if (light_faces(sh.lights[0], sf)) lit = light_term(sh.lights[0], sf, -rd, thr, so, ldir, stfar, contrib);
+      active = continue_path(sf, rd, (uint32_t)(depth - 1), thr, rng, no, nd);
+    }
+  }
+  if (lit) shadow_add(sc, sv, w, p, so, ldir, stfar, contrib, dirty, radv, vc, s_stack, rays);
+  bool hit = false;
+  float tfar = __builtin_huge_valf();
+  uint32_t href = kNoHit;
+  if (active) {  // trace(depth)
+    ++traced;
+    hit = traverse_w<false, false, false>(sc, sv, make_ray(no, nd), 0.0f, tfar, href, vc, s_stack);
+    if (!hit) rad_add(w, p, dirty, radv, thr * env_color<kCube>(sh.env, renormalized_again(nd)));
+  }
+  if constexpr (!kClose) {
+    const uint32_t jn = block_append(s_cnt, hit);
+    if (hit && seg0 + jn >= w.seg_cap) {
+      hit = false;
+      w.tot[kTotOverflow] = 1ull;  // cannot happen (ensure_wave slack); reported, never written
+    }
+    if (hit) {
+      rout.o[seg0 + jn] = f4(no, __uint_as_float(rng));
+      rout.d[seg0 + jn] = f4(nd, __uint_as_float(p));
+      rout.thr[seg0 + jn] = f4(thr, tfar);
+      rout.ref[seg0 + jn] = href;
+    }
+  } else {  // shade(depth) in this lane (bounce_ray's steps)
+    bool cont = false;
+    vec3 no2, nd2;
+    lit = false;
+    if (hit) {
+      const Surface sf = surface_at(sv, sh, smat, nm, no, nd, tfar, href);
+      const vec3 emission = v3(sf.m.emission[0], sf.m.emission[1], sf.m.emission[2]);
+      if (dot(emission, emission) > 0.0f) rad_add(w, p, dirty, radv, thr * emission);
+      if (light_faces(sh.lights[0], sf)) lit = light_term(sh.lights[0], sf, -nd, thr, so, ldir, stfar, contrib);
+      if (!last) cont = continue_path(sf, nd, (uint32_t)depth, thr, rng, no2, nd2);
+    }
+    const uint32_t jn = block_append(s_cnt, cont);
+    if (cont && seg0 + jn >= w.seg_cap) {
+      cont = false;
+      w.tot[kTotOverflow] = 1ull;
+    }
+    if (cont) {
+      rout.o[seg0 + jn] = f4(no2, __uint_as_float(rng));
+      rout.d[seg0 + jn] = f4(nd2, __uint_as_float(p));
+      rout.thr[seg0 + jn] = f4(thr, 0.0f);
+    }
+    if (lit) shadow_add(sc, sv, w, p, so, ldir, stfar, contrib, dirty, radv, vc, s_stack, rays);
+  }
+  if (dirty) w.rad[p] = f4(radv, 0.0f);
+}
+
+template <bool kCube, bool kFirst, bool kClose, bool kTimed = false>
+__global__ void __launch_bounds__(kBlock, kClose ? SPTR_ST_CLOSE_WAVES : (kFirst ? SPTR_ST_FIRST_WAVES : SPTR_ST_WAVES))
+    k_shade_trace(SceneView sv, ShadeView sh, FrameView fin, WaveView w, int depth, uint32_t nseg_in) {
+  if constexpr (kTimed) ktime_begin(w);
+  const FrameView f = frame_dyn(fin);
+  extern __shared__ float4 lds[];
+  uint32_t* s_off = reinterpret_cast<uint32_t*>(lds + sv.lds_bytes / 16u);
+  __shared__ DevMaterial smat[32];
+  __shared__ uint32_t s_cnt_n, s_rays, s_traced;
+  __shared__ LdsStack s_stack;
+  const uint32_t nm = stage_materials(sh, smat);
+  if (threadIdx.x == 0) s_cnt_n = s_rays = s_traced = 0u;
+  const Staged sc = stage_scene<true>(sv, lds);
+  const SegTable tin = kFirst ? w.segH : w.segN, tout = kFirst ? w.segN : w.segH;
+  uint32_t per_in = 0u;
+  const uint32_t n = seg_scan(tin, nseg_in, s_off, per_in);
+  const RayStream rin = w.rs[depth & 1], rout = w.rs[(depth + 1) & 1];
+  const bool last = (uint32_t)(depth + 1) >= f.max_depth;
+  const ImageDiv idiv = image_div(f);
+  Visits vc;
+  uint32_t rays = 0u, traced = 0u;
+  const Sched sd = block_sched(n);
+  for (uint32_t base = sd.first; base < sd.end; base += sd.step) {
+    const uint32_t i = base + threadIdx.x;
+    const bool valid = i < n;
+    const uint32_t slot = valid ? seg_slot(s_off, nseg_in, per_in, i) : 0u;
+    shade_trace<kCube, kFirst, kClose>(sc, sv, sh, smat, nm, f, idiv, w, rin, rout, depth, last, valid, slot, sd.seg0, &s_cnt_n,
+                                       vc, s_stack, rays, traced);
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    rays += __shfl_xor(rays, off);
+    traced += __shfl_xor(traced, off);
+  }
+  if (lane_id() == 0u) {
+    atomicAdd(&s_rays, rays);
+    atomicAdd(&s_traced, traced);
+  }
+  report_stack(vc, w.tot);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    tout.cnt[logical_block()] = s_cnt_n;
+    w.bstat[blockIdx.x] += s_rays;
+    if (blockIdx.x == 0) *tout.per = sd.per;
+    if (s_traced) {
+      atomicAdd(&w.tot[kTotClosest], (unsigned long long)s_traced);
+      atomicAdd(&w.tot[kTotTracedF], (unsigned long long)s_traced);
+      atomicAdd(&w.tot[kTotTracedD + stat_depth(depth)], (unsigned long long)s_traced);
+    }
   }
   if constexpr (kTimed) ktime_end(w);
 }
@@ -4108,33 +4309,53 @@ void launch_cull(const SceneView& sv, const FrameView& f, uint32_t* mask, uint32
 }
 
 unsigned launch_bounce(const SceneView& sv, const ShadeView& sh, const FrameView& f, const WaveView& w_in, int depth,
-                       uint32_t nseg, hipStream_t s) {
+                       uint32_t nseg, bool shade_first, bool close, hipStream_t s) {
   const WaveView w = with_tslot(w_in);
   const unsigned lb = sv.lds_bytes + (4u * (nseg + 1u) + 15u) / 16u * 16u;
+  if (!shade_first)
+    return dispatch(
+        [&](auto fl) -> unsigned {
+          return [&]<bool Cube, bool T>(Flags<Cube, T>) {
+            const unsigned g = resident_grid((const void*)&k_bounce<Cube, T>, lb);
+            SPTR_TIMED_LAUNCH((k_bounce<Cube, T>), dim3(g), dim3(kBlock), lb, s, sv, sh, f, w, depth, nseg);
+            return g;
+          }(fl);
+        },
+        Flags<>{}, sh.env.env != nullptr, w.tslot != nullptr);
   return dispatch(
       [&](auto fl) -> unsigned {
-        return [&]<bool Cube, bool T>(Flags<Cube, T>) {
-          const unsigned g = resident_grid((const void*)&k_bounce<Cube, T>, lb);
-          SPTR_TIMED_LAUNCH((k_bounce<Cube, T>), dim3(g), dim3(kBlock), lb, s, sv, sh, f, w, depth, nseg);
+        return [&]<bool Cube, bool Cl, bool T>(Flags<Cube, Cl, T>) {
+          const unsigned g = resident_grid((const void*)&k_shade_trace<Cube, false, Cl, T>, lb);
+          SPTR_TIMED_LAUNCH((k_shade_trace<Cube, false, Cl, T>), dim3(g), dim3(kBlock), lb, s, sv, sh, f, w, depth, nseg);
           return g;
         }(fl);
       },
-      Flags<>{}, sh.env.env != nullptr, w.tslot != nullptr);
+      Flags<>{}, sh.env.env != nullptr, close, w.tslot != nullptr);
 }
 
 unsigned launch_bounce01(const SceneView& sv, const ShadeView& sh, const FrameView& f, const WaveView& w_in, uint32_t nseg,
-                         hipStream_t s) {
+                         bool shade_first, bool close, hipStream_t s) {
   const WaveView w = with_tslot(w_in);
   const unsigned lb = sv.lds_bytes + (4u * (nseg + 1u) + 15u) / 16u * 16u;
+  if (!shade_first)
+    return dispatch(
+        [&](auto fl) -> unsigned {
+          return [&]<bool Cube, bool T>(Flags<Cube, T>) {
+            const unsigned g = resident_grid((const void*)&k_bounce01<Cube, T>, lb);
+            SPTR_TIMED_LAUNCH((k_bounce01<Cube, T>), dim3(g), dim3(kBlock), lb, s, sv, sh, f, w, nseg);
+            return g;
+          }(fl);
+        },
+        Flags<>{}, sh.env.env != nullptr, w.tslot != nullptr);
   return dispatch(
       [&](auto fl) -> unsigned {
-        return [&]<bool Cube, bool T>(Flags<Cube, T>) {
-          const unsigned g = resident_grid((const void*)&k_bounce01<Cube, T>, lb);
-          SPTR_TIMED_LAUNCH((k_bounce01<Cube, T>), dim3(g), dim3(kBlock), lb, s, sv, sh, f, w, nseg);
+        return [&]<bool Cube, bool Cl, bool T>(Flags<Cube, Cl, T>) {
+          const unsigned g = resident_grid((const void*)&k_shade_trace<Cube, true, Cl, T>, lb);
+          SPTR_TIMED_LAUNCH((k_shade_trace<Cube, true, Cl, T>), dim3(g), dim3(kBlock), lb, s, sv, sh, f, w, 1, nseg);
           return g;
         }(fl);
       },
-      Flags<>{}, sh.env.env != nullptr, w.tslot != nullptr);
+      Flags<>{}, sh.env.env != nullptr, close, w.tslot != nullptr);
 }
 
 unsigned launch_bounce_chain(const SceneView& sv, const ShadeView& sh, const FrameView& f, const WaveView& w_in, int T,

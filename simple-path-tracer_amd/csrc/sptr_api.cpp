@@ -178,6 +178,15 @@ bool bounce_chain_on(const Context& c, uint64_t batch_paths) {
   (void)batch_paths;
   return c.bounce_chain == 2u;
 }
+// The fused launches per bounce: k_shade_trace (shade the previous bounce's hits on dense lanes, then trace)
+// for batches of more than kShadeFirstMinPaths paths, k_bounce01 + k_bounce for the others.  In a small batch
+// a launch lasts as long as its longest wave, and k_shade_trace's closing launch (shade, trace, shade) is the
+// heaviest kernel on the smallest stream.  Measured: DESIGN.md §4 "Shade first", profiles/r08_bounce_order_ab.txt.
+#ifndef SPTR_SHADE_FIRST_MIN_PATHS
+#define SPTR_SHADE_FIRST_MIN_PATHS (5ull << 22)  // 21.0 M: lost at 16.7 M and below, level at 22.3 M, ahead from 33.4 M
+#endif
+constexpr uint64_t kShadeFirstMinPaths = SPTR_SHADE_FIRST_MIN_PATHS;
+bool shade_first_on(uint64_t batch_paths) { return batch_paths > kShadeFirstMinPaths; }
 
 // MaterialManager::getMaterialFromHit (src/MaterialManager.cpp:91-103): the geomID's mapped
 // material when it is in range, else MaterialManager::getMaterialByID(geomID) (:79-89).
@@ -217,16 +226,16 @@ inline bool host_local_pixel(const Context& c, uint32_t l, int& x, int& y) {
 // segment tables (3 x (kMaxSegs + 4) u32), per-block tallies (2 x kMaxSegs u64), work counters
 size_t seg_table_bytes() { return 3 * (kMaxSegs + 4) * 4 + 2 * kMaxSegs * 8 + kWorkWords * 4; }
 
-// device bytes per path slot of a wave: ray streams 2 x (o, d, thr), hit record(s), radiance, and
+// device bytes per path slot of a wave: ray streams 2 x (o, d, thr, ref), hit record(s), radiance, and
 // L shadow tasks of ts float4s.  hrec_mult: hit-record segments per static share (2 when the trace
 // takes its rays from the per-XCD queues, trace_queue_applies; else 1).
 uint64_t wave_path_bytes(uint32_t L, uint32_t ts, uint32_t hrec_mult) {
-  return 2 * 3 * 16 + hrec_mult * kHitBytes + 16 + (uint64_t)L * ts * 16;
+  return 2 * (3 * 16 + 4) + hrec_mult * kHitBytes + 16 + (uint64_t)L * ts * 16;
 }
 // fixed segment slack of a wave's streams (see ensure_wave); k_slack = hit-record slack multiplier
 uint64_t wave_slack_bytes(uint32_t L, uint32_t ts, uint32_t k_slack, uint32_t hrec_mult) {
   const uint64_t recs = (uint64_t)kMaxSegs * kBlock;
-  return recs * (2 * 3 * 16 + (uint64_t)(L ? L : 1u) * ts * 16) + hrec_mult * recs * k_slack * kHitBytes;
+  return recs * (2 * (3 * 16 + 4) + (uint64_t)(L ? L : 1u) * ts * 16) + hrec_mult * recs * k_slack * kHitBytes;
 }
 
 // k_slack: the pixel-major bounce-0 trace gives each block a hit-record segment of k records per
@@ -253,6 +262,7 @@ int ensure_wave(Context& c, uint64_t cap, uint32_t L, uint32_t ts, uint32_t k_sl
   const size_t n = (size_t)cap, ns = n + (size_t)kMaxSegs * kBlock;
   for (auto& r : b.rs)
     for (DevBuf& x : r) API_HIP(x.ensure(ns * 16));
+  for (DevBuf& x : b.rs_ref) API_HIP(x.ensure(ns * 4));
   API_HIP(b.rad.ensure(n * 16));
   API_HIP(b.stask.ensure(ns * L * ts * 16));
   b.cap = cap;
@@ -274,6 +284,7 @@ WaveView wave_view(Context& c) {
     w.rs[b].o = static_cast<float4*>(wb.rs[b][0].p);
     w.rs[b].d = static_cast<float4*>(wb.rs[b][1].p);
     w.rs[b].thr = static_cast<float4*>(wb.rs[b][2].p);
+    w.rs[b].ref = static_cast<uint32_t*>(wb.rs_ref[b].p);
   }
   const uint64_t hcap = std::min<uint64_t>(wb.hrec.bytes / kHitBytes, 0xFFFFFFFFull);
   w.hrec.tr = static_cast<uint2*>(wb.hrec.p);
@@ -370,7 +381,7 @@ ShadeView shade_view(const Context& cc) {
 
 // Stage events on the render stream, kept in the context's pool until collected.  Stages: 0 whole
 // render call, 1 trace (bounce >= 1), 2 shade (>= 1), 3 shadow, 4 accum + resolve, 5 trace bounce 0
-// (raygen fused), 6 shade bounce 0, 7 tail, 8 pixel cull, 9 fused bounce (k_bounce: the trace and the
+// (raygen fused), 6 shade bounce 0, 7 tail, 8 pixel cull, 9 fused bounce (k_shade_trace, or k_bounce01 / k_bounce: the trace and the
 // shading of a bounce in one launch, counted with the trace launches); 0-9 with SPTR_FRAME_TIMING,
 // 1, 3, 5 and 9 with SPTR_FRAME_TIMING_TRACE.
 constexpr int kStages = 10;
@@ -866,11 +877,13 @@ uint32_t enqueue_wavefront(Context& c, const sptr_frame& f, uint32_t k, int T, h
     // (r04s: handing them to k_sky beside the thread-per-pixel bounce 0 too: C2 3.09-3.20 -> 3.54-3.57 ms)
     fv.sky_fold = (fv.cull != nullptr && fv.pixel_major == kFoldNone) ? 1u : 0u;
     fv.plist = fv.sky_fold ? static_cast<const uint32_t*>(c.plist.p) : nullptr;
-    // fused bounces (k_bounce), in batches of every size since r06: r02 measured them on C2 only where
+    // fused bounces (k_shade_trace since r08; the figures here are its predecessors k_bounce01 / k_bounce's), in
+    // batches of every size since r06: r02 measured them on C2 only where
     // launches are short (8-way shard 0.627 -> 0.590 ms, 2-way 1.887 -> 1.822, but 1 GPU (133 M paths) 3.39
     // -> 3.46 ms: the traversal at the shading kernel's occupancy); after k_bounce01 they gain on the large
     // batches too (r06s: C4, 535 M-path batches, 122.2-122.6 -> 119.2-119.4 ms/step; C2 unchanged)
     const bool fuse_bounce = fuse && !no_bounce;
+    const bool shade_first = shade_first_on((uint64_t)kk * c.P);  // k_shade_trace, or k_bounce01 + k_bounce
     // larger batches could fuse only their late bounces, whose queues are short: no gain measured
     // (r03zx, SPTR_FUSE_FROM 2/3/4 on C2: 3.16-3.25 vs 3.17 ms/step)
     const int fuse_from = fuse_bounce ? 1 : ((fuse && !no_bounce && fuse_from_env > 0) ? fuse_from_env : D + 1);
@@ -903,12 +916,12 @@ uint32_t enqueue_wavefront(Context& c, const sptr_frame& f, uint32_t k, int T, h
         tm.end();
         break;
       }
-      if (d >= fuse_from) {  // trace + shade (+ shadow) of this bounce in one launch
+      if (d >= fuse_from) {  // shade(d - 1) (+ shadow) and trace(d) in one launch; the last of them shades bounce d too
         WaveView wf = w;
         wf.segN = rays_tab;
         wf.segH = spare_tab;
         tm.begin(9);  // (a trace launch that also shades: ms_trace, trace_launches)
-        g_shade = launch_bounce(sv, sh, fv, wf, d, g_shade, s);
+        g_shade = launch_bounce(sv, sh, fv, wf, d, g_shade, shade_first, d + 1 >= std::min(T, D), s);
         tm.end();
         std::swap(rays_tab, spare_tab);
         continue;
@@ -966,13 +979,14 @@ uint32_t enqueue_wavefront(Context& c, const sptr_frame& f, uint32_t k, int T, h
         continue;
       }
       if (d == 0 && fuse && !no_bounce && T >= 2 && D >= 2) {
-        // bounce 0's shading and bounce 1 in one launch (k_bounce01), in batches of every size: its rays of
-        // bounce 2 go to w.segN, where the fused bounces from 2 on (or k_trace(2)) take them.  r06 A/B on one
+        // bounce 0's shading and bounce 1's trace in one launch (k_shade_trace<first>), in batches of every size:
+        // bounce 1's hit-ray records go to w.segN, where the fused launches from 2 on take them (as the closing
+        // launch, T or D = 2, it shades bounce 1 too and writes the rays of bounce 2).  k_bounce01's r06 A/B on one
         // box: C2 (two lanes, fused bounces) 2.58-2.60 -> 2.36 ms/step, 8-way shard 0.52 -> 0.49; C4 (batches
         // of 535 M paths, separate stages from bounce 2) 136.6 -> 122.4 ms, C2 as one chain 3.01 -> 2.76
         // (gpurun_out/r06p, r06q)
         tm.begin(9);
-        g_shade = launch_bounce01(sv, sh, fv, w, g_trace, s);
+        g_shade = launch_bounce01(sv, sh, fv, w, g_trace, shade_first, std::min(T, D) <= 2, s);
         tm.end();
         rays_tab = w.segN;
         spare_tab = w.segH;

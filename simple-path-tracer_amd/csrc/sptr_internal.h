@@ -221,7 +221,7 @@ enum : int {
   kTotHitB,                          // closest hits found by the later trace kernels (COUNT_VISITS)
   kTotStrag,                         // paths k_trace_dyn handed off to k_strag
   kTotStragNodes, kTotStragTris, kTotStragSph,  // the handed-off walks' visits made by k_strag (every call)
-  kTotTracedF,                       // queued rays of bounces >= 1 traced by the fused k_bounce (every call)
+  kTotTracedF,                       // queued rays of bounces >= 1 traced by the fused bounce launches (every call)
   kTotWords
 };
 
@@ -259,7 +259,8 @@ struct HitStream {
 struct RayStream {
   float4* o;    // origin.xyz, rng state bits
   float4* d;    // direction.xyz, path id bits
-  float4* thr;  // throughput.xyz
+  float4* thr;  // throughput.xyz; w: of a hit-ray record (k_shade_trace), the hit's t
+  uint32_t* ref;  // hit-ray records only: the primitive the ray hit
 };
 
 struct WaveView {
@@ -352,7 +353,7 @@ struct ReprojView {
 struct WaveBufs {
   uint64_t cap = 0;  // paths
   uint32_t L = 0, ts = 0;
-  DevBuf rs[2][3], hrec, rad, stask, seg, strag;
+  DevBuf rs[2][3], rs_ref[2], hrec, rad, stask, seg, strag;
 };
 
 struct StageMark {
@@ -553,13 +554,19 @@ bool shade_fuses_shadows(const SceneView& sv, const ShadeView& sh, bool count);
 bool shadow_overlaps(const SceneView& sv, const WaveView& w);
 unsigned launch_shade(const SceneView& sv, const ShadeView& sh, const FrameView& f, const WaveView& w, int depth,
                       uint32_t nseg, bool fuse, hipStream_t s);
-// bounce 0's shading and bounce 1 in one launch (k_bounce01): bounce 0's hit records of w.segH in, the rays
-// of bounce 2 out in w.segN / rs[0]
+// The fused bounce launches (k_shade_trace): each shades the hits of bounce depth - 1 and traces bounce depth.
+// close: the last wavefront bounce, which also shades its own hits and writes plain continuation rays (for
+// k_tail) or, at the last bounce of the path, nothing.  !shade_first (small batches, sptr_api.cpp shade_first_on):
+// k_bounce01 (bounce 0's shading and the whole of bounce 1; the rays of bounce 2 out) and k_bounce (one whole
+// bounce: rays in, continuation rays out), with the same tables and streams; close is not used.
+// the first of them: bounce 0's hit records of w.segH in; the hit-ray records of bounce 1 (close: the rays of
+// bounce 2) out in w.segN / rs[0]
 unsigned launch_bounce01(const SceneView& sv, const ShadeView& sh, const FrameView& f, const WaveView& w, uint32_t nseg,
-                         hipStream_t s);
-// one fused bounce (k_bounce): rays of w.segN in, continuation rays of w.segH out
+                         bool shade_first, bool close, hipStream_t s);
+// a later one: the hit-ray records of bounce depth - 1 of w.segN / rs[depth & 1] in; those of bounce depth
+// (close: the rays of bounce depth + 1) out in w.segH / rs[(depth + 1) & 1]
 unsigned launch_bounce(const SceneView& sv, const ShadeView& sh, const FrameView& f, const WaveView& w, int depth,
-                       uint32_t nseg, hipStream_t s);
+                       uint32_t nseg, bool shade_first, bool close, hipStream_t s);
 // bounce 0's shading and bounces 1 .. T-1 in one launch (k_bounce_chain, 2 <= T <= max_depth): bounce 0's hit
 // records of w.segH in; with T < max_depth the rays of bounce T out in rs[T & 1], counted in w.segN
 unsigned launch_bounce_chain(const SceneView& sv, const ShadeView& sh, const FrameView& f, const WaveView& w, int T,
