@@ -388,10 +388,13 @@ int sptr_set_denoise(sptr_ctx* ctx, const sptr_denoise_params* params);
  *   SPTR_AOV_ALBEDO: W*H*3 floats, materials[geom_material[geomID]].albedo;
  *   SPTR_AOV_NORMAL: W*H*3 floats, the normalised geometric normal, facing the camera (N.d <= 0);
  *   SPTR_AOV_DEPTH : W*H floats, the hit distance t;
- *   SPTR_AOV_ID    : W*H*2 uint32, (geomID, primID) as sptr_intersect reports them.
- * A miss gives albedo 0, normal 0, depth -1 and ids 0xFFFFFFFF.  The buffers are cached per camera, size
+ *   SPTR_AOV_ID    : W*H*2 uint32, (geomID, primID) as sptr_intersect reports them;
+ *   SPTR_AOV_UV    : W*H*2 floats, the hit's barycentrics u, v exactly as sptr_query_rays defines them
+ *                    (0, 0 on a sphere).  This plane is allocated and written only when it is asked for or
+ *                    sptr_set_history_motion is on; cached buffers that lack it are computed again.
+ * A miss gives albedo 0, normal 0, depth -1, ids 0xFFFFFFFF and uv 0.  The buffers are cached per camera, size
  * and scene state, as the cull mask is: a static camera pays for them once (sptr_denoise_info). */
-enum { SPTR_AOV_ALBEDO = 0, SPTR_AOV_NORMAL = 1, SPTR_AOV_DEPTH = 2, SPTR_AOV_ID = 3 };
+enum { SPTR_AOV_ALBEDO = 0, SPTR_AOV_NORMAL = 1, SPTR_AOV_DEPTH = 2, SPTR_AOV_ID = 3, SPTR_AOV_UV = 4 };
 int sptr_read_aov(sptr_ctx* ctx, int kind, void* out);
 /* The filter's output before the resolve: W*H*3 linear radiance.  An error unless the last render call
  * ran the denoise pass. */
@@ -424,8 +427,9 @@ int sptr_set_seed_offset(sptr_ctx* ctx, uint32_t offset);
  * pixel instead of n.  When a call with frame_begin == 1 runs a pass, the image the previous pass integrated becomes the
  * carry, with that pass's first-hit planes and camera; calls that continue the accumulation keep reading
  * the same carry.  The carry is dropped when the size changes, when the scene state changes (whatever
- * recomputes the first-hit planes of an unchanged camera: uploads, sptr_update_geometry, the material,
- * light and environment setters, ...) and by any call of sptr_set_denoise_history.  Without a carry the
+ * recomputes the first-hit planes of an unchanged camera: uploads, sptr_update_geometry unless
+ * sptr_set_history_motion is on, the material, light and environment setters, ...) and by any call of
+ * sptr_set_denoise_history.  Without a carry the
  * pass equals the pass without history bit for bit.  Costs about 56 bytes per pixel of device memory. */
 typedef struct sptr_history_params {
   uint32_t max_history;   /* 0 = off (default); else the cap M on a pixel's history length, in frames; at most 1024 */
@@ -439,6 +443,31 @@ int sptr_read_history(sptr_ctx* ctx, float* rgbm);
  * the reprojection launch, and whether the pass had a carry to read.  All 0 when the last render call ran
  * no pass with history on.  Any pointer may be NULL. */
 int sptr_history_info(sptr_ctx* ctx, uint32_t* reprojected, double* ms_reproject, uint32_t* carried);
+
+/* ---- motion vectors: the history survives geometry updates (symbols added within ABI 9: no existing
+ *      struct or entry point changed) --------------------------------------------------------------------
+ * With this setting on, sptr_update_geometry no longer drops the denoiser's history (DESIGN.md "Motion
+ * vectors").  Before a refit overwrites them, the triangle records and spheres the last history pass saw
+ * are copied device-to-device into a snapshot (48 B per triangle, 16 B per sphere; only if that pass ran on
+ * the current geometry, so several updates between two passes keep the carry's geometry).  The next pass
+ * whose carry saw that geometry carries each pixel's surface point there (a triangle hit through its
+ * barycentrics, a sphere hit through its unit offset from the centre), projects that point into the carry's
+ * camera, and uses its distance and the old geometry's normal there in the taps' weights; the history taken
+ * is always clipped as after a camera move, since shadows and reflections belong to the scene state as they
+ * belong to the view.  A carry whose geometry the snapshot does not hold is dropped.  Everything else that
+ * changes the scene state (uploads, the material, light and environment setters, a size change) drops the
+ * history as before.  Default 0: every call issues the launches it issued before this entry point existed
+ * and returns the same bytes.  Any call drops the history held and the snapshot.  SPTR_ERR_INVALID on a
+ * lane context. */
+int sptr_set_history_motion(sptr_ctx* ctx, uint32_t on);
+/* The motion vectors of the last pass that read its carry through a snapshot: W*H*2 floats, per pixel
+ * (fx - x, fy - y), where (fx, fy) is the place of the pixel's surface point in the carry's image (pixel
+ * centres at integers).  A quiet NaN twice for a pixel that never reaches the projection (a miss, a mean
+ * that is not finite).  An error unless the last render call ran such a pass. */
+int sptr_read_motion(sptr_ctx* ctx, float* out);
+/* Snapshots taken since the upload, device ms of the last one, and whether the last pass read its carry
+ * through a snapshot (0 / 1).  Any pointer may be NULL. */
+int sptr_motion_info(sptr_ctx* ctx, uint32_t* snapshots, double* ms_snapshot, uint32_t* used);
 
 /* ---- dynamic scenes: refit the BVH in place when geometry moves (symbols added within ABI 9: no
  *      existing struct or entry point changed) --------------------------------------------------------

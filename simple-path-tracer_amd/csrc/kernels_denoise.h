@@ -8,7 +8,9 @@
 // division, max and compares only, no contraction, so tests/denoise_ref.py restates the filter bit for
 // bit in numpy float32.
 // k_dn_reproject (sptr_set_denoise_history, DESIGN.md "Temporal reprojection") integrates an earlier pass's
-// image into k_dn_mean's output under the same rule, with sqrtf and floorf besides (tests/temporal_ref.py).
+// image into k_dn_mean's output under the same rule, with sqrtf and floorf besides (tests/temporal_ref.py);
+// k_dn_reproject<true> (sptr_set_history_motion, DESIGN.md "Motion vectors") does so through the geometry that
+// pass saw (tests/motion_ref.py).
 
 // --------------------------------------------------------------------------------- k_aov
 // One closest-hit query per image pixel along the pixel-centre ray.
@@ -31,6 +33,7 @@ __global__ void __launch_bounds__(kBlock, SPTR_PT_WAVES) k_aov(SceneView sv, Fra
     const bool hit = traverse_w<kW4, false, false>(sc, sv, r, 0.0f, t, ref, vc, s_stack);
     float4 nz = make_float4(0.0f, 0.0f, 0.0f, -1.0f), al = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     uint2 id = make_uint2(kNoHit, kNoHit);
+    float bu = 0.0f, bv = 0.0f;
     if (hit) {
       const uint32_t idx = ref & kIndexMask;
       vec3 ng;
@@ -44,6 +47,15 @@ __global__ void __launch_bounds__(kBlock, SPTR_PT_WAVES) k_aov(SceneView sv, Fra
         ng = v3(c.y, c.z, c.w);
         const uint32_t g = sv.tri_geom[idx];
         id = make_uint2(g, a.tri_orig[idx] - a.geom_first[g]);
+        if (a.ruv) {  // as k_rayquery: tri_hit4's U, V and den for this triangle
+          const float4 ta = sv.tris[3 * idx + 0], tb = sv.tris[3 * idx + 1];
+          const vec3 v0 = v3(ta.x, ta.y, ta.z), e1 = v3(ta.w, tb.x, tb.y), e2 = v3(tb.z, tb.w, c.x);
+          const vec3 R = e_cross(v0 - f.cam_pos, d);
+          const float den = e_dot(ng, d);
+          const float aden = fabsf(den);
+          bu = xorsign(e_dot(R, e2), den) / aden;
+          bv = xorsign(e_dot(R, e1), den) / aden;
+        }
       }
       vec3 n = safe_normalize(ng);
       if (dot(n, d) > 0.0f) n = -n;
@@ -54,6 +66,7 @@ __global__ void __launch_bounds__(kBlock, SPTR_PT_WAVES) k_aov(SceneView sv, Fra
     a.nz[i] = nz;
     a.albedo[i] = al;
     a.ids[i] = id;
+    if (a.ruv) a.ruv[i] = make_float4(__uint_as_float(ref), bu, bv, 0.0f);
   }
   if (__ballot(vc.stack_overflow != 0u) && lane_id() == 0u) *a.stack_overflow = 1u;
 }
@@ -159,6 +172,12 @@ __global__ void __launch_bounds__(kBlock) k_atrous(DenoiseView v, const float4* 
 // A miss, a mean that is not finite, or no acceptable tap: t_0 = c_0 bit-unchanged (m' = n, or 0 where the
 // filter passes the pixel through).  32 x 8 pixel blocks as k_atrous; no LDS; every tap is bounds-checked
 // before its loads.  Pixels that took history are counted with one ballot and one atomic per wave.
+// kMotion (sptr_set_history_motion): the carry saw the geometry of the snapshot.  The surface
+// point is carried there (a triangle's through its barycentrics and the snapshot's record, a sphere's through
+// its unit offset from the centre), that point is projected, its distance and the snapshot's normal there
+// take the place of dist and N_p in the taps' weights, and the offset of the projection from the pixel is
+// written out.  A reference beyond the snapshot's slots takes no history; no snapshot load comes before that check.
+template <bool kMotion>
 __global__ void __launch_bounds__(kBlock) k_dn_reproject(DenoiseView v, FrameView f, ReprojView r) {
   const int x = (int)blockIdx.x * kDnTileW + (int)(threadIdx.x % kDnTileW);
   const int y = (int)blockIdx.y * kDnTileH + (int)(threadIdx.x / kDnTileW);
@@ -169,20 +188,50 @@ __global__ void __launch_bounds__(kBlock) k_dn_reproject(DenoiseView v, FrameVie
     const float4 np = v.nz[p];
     const float nf = float(v.n);
     float4 out = f4(xyz(c0), 0.0f);
+    float2 mv = make_float2(__uint_as_float(0x7FC00000u), __uint_as_float(0x7FC00000u));
     if (!(np.w < 0.0f) && dn_finite(c0)) {
       out.w = nf;
       if (r.hist_prev) {
         const ImageDiv idiv = image_div(f);
         const vec3 d = camera_dir(f, div_nrm(float(x) + 0.5f, idiv.w), div_nrm(float(y) + 0.5f, idiv.h));  // as k_aov
-        const vec3 P = f.cam_pos + np.w * d;
+        vec3 P = f.cam_pos + np.w * d;
+        vec3 nrm = xyz(np);
+        bool known = true;
+        if constexpr (kMotion) {
+          const float4 ru = r.ruv[p];
+          const uint32_t ref = __float_as_uint(ru.x), slot = ref & kIndexMask;
+          if (ref & kSphereBit) {
+            known = slot < r.num_sph;
+            if (known) {
+              const float4 c = r.sph[slot], cp = r.sph_prev[slot];
+              const vec3 g = v3((P.x - c.x) / c.w, (P.y - c.y) / c.w, (P.z - c.z) / c.w);
+              P = v3(cp.x + cp.w * g.x, cp.y + cp.w * g.y, cp.z + cp.w * g.z);
+              nrm = safe_normalize(g);
+            }
+          } else {
+            known = slot < r.num_tris;
+            if (known) {
+              const float4 ta = r.tris_prev[3 * slot + 0], tb = r.tris_prev[3 * slot + 1], tc = r.tris_prev[3 * slot + 2];
+              const vec3 v0 = v3(ta.x, ta.y, ta.z), e1 = v3(ta.w, tb.x, tb.y), e2 = v3(tb.z, tb.w, tc.x);
+              P = (v0 - ru.y * e1) + ru.z * e2;  // e1 = v0 - v1
+              nrm = safe_normalize(v3(tc.y, tc.z, tc.w));
+            }
+          }
+        }
         const vec3 vv = P - r.pos;
+        if constexpr (kMotion) {
+          if (dot(nrm, vv) > 0.0f) nrm = -nrm;
+        }
         const float zf = dot(vv, r.fw);
         const float nx = dot(vv, r.rt) / (zf * r.hw);
         const float ny = dot(vv, r.up) / (zf * r.hh);
         const float fx = (nx * 0.5f + 0.5f) * float(v.W) - 0.5f;
         const float fy = (0.5f - ny * 0.5f) * float(v.H) - 0.5f;
+        if constexpr (kMotion) {
+          if (known) mv = make_float2(fx - float(x), fy - float(y));
+        }
         // (written so that a NaN or an infinity fails: no conversion to int and no load before it)
-        if (zf > 0.0f && fx > -1.0f && fx < float(v.W) && fy > -1.0f && fy < float(v.H)) {
+        if (known && zf > 0.0f && fx > -1.0f && fx < float(v.W) && fy > -1.0f && fy < float(v.H)) {
           const float x0f = floorf(fx), y0f = floorf(fy);
           const float a = fx - x0f, b = fy - y0f;
           const int x0 = (int)x0f, y0 = (int)y0f;
@@ -202,7 +251,7 @@ __global__ void __launch_bounds__(kBlock) k_dn_reproject(DenoiseView v, FrameVie
               const float4 hq = r.hist_prev[q];
               const float4 nq = r.nz_prev[q];
               if (nq.w < 0.0f || !dn_finite(hq) || r.ids_prev[q].x != gp) continue;
-              float wn = fmax_g(0.0f, dot(xyz(np), xyz(nq)));
+              float wn = fmax_g(0.0f, dot(nrm, xyz(nq)));
               for (uint32_t k = 0; k < v.normal_log2; ++k) wn = wn * wn;
               const float e = fabsf(dist - nq.w) / (v.sigma_z * fmax_g(dist, nq.w));
               const float wz = 1.0f / (1.0f + e * e);
@@ -255,6 +304,7 @@ __global__ void __launch_bounds__(kBlock) k_dn_reproject(DenoiseView v, FrameVie
       }
     }
     r.hist[p] = out;
+    if constexpr (kMotion) r.motion[p] = mv;
   }
   const unsigned long long bal = __ballot(took);
   if (bal != 0ull && lane_id() == 0u) atomicAdd(r.count, (uint32_t)__popcll(bal));
@@ -285,7 +335,11 @@ void launch_atrous_history(const DenoiseView& v, const float4* cin, float4* cout
 }
 void launch_dn_reproject(const DenoiseView& v, const FrameView& f, const ReprojView& r, hipStream_t s) {
   const dim3 grid((unsigned)((v.W + kDnTileW - 1) / kDnTileW), (unsigned)((v.H + kDnTileH - 1) / kDnTileH));
-  hipLaunchKernelGGL(k_dn_reproject, grid, dim3(kBlock), 0, s, v, f, r);
+  hipLaunchKernelGGL(k_dn_reproject<false>, grid, dim3(kBlock), 0, s, v, f, r);
+}
+void launch_dn_reproject_motion(const DenoiseView& v, const FrameView& f, const ReprojView& r, hipStream_t s) {
+  const dim3 grid((unsigned)((v.W + kDnTileW - 1) / kDnTileW), (unsigned)((v.H + kDnTileH - 1) / kDnTileH));
+  hipLaunchKernelGGL(k_dn_reproject<true>, grid, dim3(kBlock), 0, s, v, f, r);
 }
 void launch_dn_resolve(const DenoiseView& v, const float4* c, uint8_t* image, hipStream_t s) {
   hipLaunchKernelGGL(k_dn_resolve, dim3(grid_for((uint64_t)v.W * v.H)), dim3(kBlock), 0, s, v, c, image);

@@ -826,6 +826,8 @@ int build_lbvh(Context& c, const float* h_pos, uint32_t nverts, const uint32_t* 
   // dynamic scenes (sptr_set_dynamic): what a refit needs is kept below; otherwise nothing of it is
   c.rf.valid = c.rf.split = false;
   c.rf.refits = 0;
+  c.rf.snapshots = 0;
+  c.rf.ms_snapshot = 0.0;
   c.rf.num_verts = nverts;
   c.rf.max_h = 0;
   if (!c.dynamic) refit_release(c);

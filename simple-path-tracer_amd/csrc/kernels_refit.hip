@@ -190,9 +190,29 @@ void launch_slots(Context& c, const float* d_pos, const float4* d_sph) {
 
 void refit_release(Context& c) {
   RefitState& r = c.rf;
-  for (DevBuf* b : {&r.idx, &r.box_lo, &r.box_hi, &r.order, &r.hoff, &r.wsrc, &r.in_pos, &r.in_sph}) b->release();
+  for (DevBuf* b : {&r.idx, &r.box_lo, &r.box_hi, &r.order, &r.hoff, &r.wsrc, &r.in_pos, &r.in_sph, &r.snap}) b->release();
   r.hoff_h.clear();
   r.valid = false;
+}
+
+// Two device-to-device copies: 48 B per triangle slot, then 16 B per sphere.
+int refit_snapshot(Context& c) {
+  RefitState& r = c.rf;
+  hipStream_t s = c.stream;
+  for (DevEvent& e : r.snap_ev)
+    if (!e) RF_CHECK(hipEventCreate(e.put()));
+  const size_t tb = (size_t)c.num_tri_refs * 48, sb = (size_t)c.num_sph * 16;
+  RF_CHECK(r.snap.ensure(tb + sb > 0 ? tb + sb : 16));
+  RF_CHECK(hipEventRecord(r.snap_ev[0], s));
+  if (tb) RF_CHECK(hipMemcpyAsync(r.snap.p, c.tris.p, tb, hipMemcpyDeviceToDevice, s));
+  if (sb) RF_CHECK(hipMemcpyAsync(static_cast<char*>(r.snap.p) + tb, c.sph.p, sb, hipMemcpyDeviceToDevice, s));
+  RF_CHECK(hipEventRecord(r.snap_ev[1], s));
+  RF_CHECK(hipStreamSynchronize(s));
+  float ms = 0.0f;
+  RF_CHECK(hipEventElapsedTime(&ms, r.snap_ev[0], r.snap_ev[1]));
+  r.ms_snapshot = ms;
+  ++r.snapshots;
+  return SPTR_OK;
 }
 
 int refit_retain_slots(Context& c, const float* d_pos, const uint32_t* d_idx, const float4* d_sph) {

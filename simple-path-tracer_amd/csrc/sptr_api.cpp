@@ -81,11 +81,21 @@ struct sptr_ctx {
       sptr_camera cam{};
       int W = 0, H = 0;
       uint64_t epoch = 0;
+      uint64_t gen = 0;  // the geometry generation it ran on
     } last, carry;  // the last pass, and the pass the current accumulation takes its history from
     bool hist_ran = false;     // the last render call ran a pass with history on
     bool hist_carried = false; // ... and that pass had a carry to read
     uint32_t hist_slot = 0;    // ... and wrote hist[hist_slot]
     sptr::DevEvent hev[2];     // k_dn_reproject begin / end
+    // sptr_set_history_motion.  geom_gen counts sptr_update_geometry calls; the snapshot
+    // (Context::rf.snap) holds the records of generation snap_gen.  ruv: k_aov's reference / barycentric
+    // plane of the cached planes (aov_uv: it was written with them); motion: k_dn_reproject<true>'s vectors.
+    bool motion_on = false;
+    uint64_t geom_gen = 0, snap_gen = 0;
+    bool snap_valid = false;
+    sptr::DevBuf ruv, motion;
+    bool aov_uv = false;
+    bool motion_used = false;  // the last pass with history on took the motion path
   } dn;
   // sptr_query_rays (the caller's context; a pixel lane holds none): scratch that grows on demand (sort keys
   // and identity indices, their sorted copies, the radix sort's temporaries, the stack-overflow flag, the
@@ -2339,6 +2349,7 @@ int sptr_upload_scene(sptr_ctx* x, const sptr_scene* s) {
   const int rc = upload_scene_one(x, s);
   if (rc != SPTR_OK) return rc;
   x->geom_first_valid = false;
+  x->dn.snap_valid = false;  // (the snapshot's slots were the old scene's)
   if (x->split) x->c.W = 0;  // the pixel buffers describe the even lane: re-laid out for the next call
   x->split = false;
   x->lane_scene = false;
@@ -2404,8 +2415,23 @@ int sptr_update_geometry(sptr_ctx* x, const float* positions, uint32_t num_verts
       d_sph = static_cast<const float*>(c.rf.in_sph.p);
     }
   }
+  // sptr_set_history_motion: the records the last history pass saw, kept before the refit overwrites them.
+  // Only when that pass ran on this generation: after two refits between passes the snapshot still holds
+  // the geometry of the pass a later call takes as its carry.
+  auto& d = x->dn;
+  if (d.motion_on && d.last.valid && d.last.gen == d.geom_gen) {
+    const int rs = refit_snapshot(c);
+    if (rs != SPTR_OK) return rs;
+    d.snap_gen = d.geom_gen;
+    d.snap_valid = true;
+  }
+  const uint64_t epoch_before = c.epoch;
   const int rc = refit_one(c, d_pos, d_sph);  // (returns after c.stream drained: the staging is stable)
+  ++d.geom_gen;
   if (rc != SPTR_OK) return rc;
+  if (d.motion_on)  // the history outlives the refit: its passes follow the epoch, and differ by generation
+    for (sptr_ctx::Denoise::Pass* p : {&d.last, &d.carry})
+      if (p->valid && p->epoch == epoch_before) p->epoch = c.epoch;
   if (x->lane && x->lane_scene) {  // the lane's copy of the scene, on the lane's stream
     Context& cy = x->lane->c;
     if (!cy.rf.valid) return fail(c, SPTR_ERR_INVALID, "update_geometry: the pixel lane's scene is not dynamic");
@@ -2613,25 +2639,28 @@ int sptr_set_denoise(sptr_ctx* x, const sptr_denoise_params* p) {
 }
 
 // The AOV planes of (cam, W, H) on stream s, unless the cached ones were computed for them and for this
-// scene state.  *ran: whether k_aov was launched.
-static int ensure_aov(sptr_ctx* x, const sptr_camera& cam, int W, int H, hipStream_t s, bool timed, bool* ran) {
+// scene state.  *ran: whether k_aov was launched.  uv: the reference / barycentric plane is wanted too
+// (SPTR_AOV_UV, sptr_set_history_motion): cached planes computed without it are computed again, in place.
+static int ensure_aov(sptr_ctx* x, const sptr_camera& cam, int W, int H, hipStream_t s, bool timed, bool* ran, bool uv = false) {
   Context& c = x->c;
   auto& d = x->dn;
   *ran = false;
-  if (d.aov_epoch == c.epoch && d.aov_W == W && d.aov_H == H && std::memcmp(&d.aov_cam, &cam, sizeof(cam)) == 0)
-    return SPTR_OK;
+  const bool same = d.aov_epoch == c.epoch && d.aov_W == W && d.aov_H == H && std::memcmp(&d.aov_cam, &cam, sizeof(cam)) == 0;
+  if (same && (!uv || d.aov_uv)) return SPTR_OK;
   const size_t n = (size_t)W * H;
-  // the side written: never the one that holds the carry's planes (history off: always side 0)
-  const int side = d.carry.valid ? d.carry.side ^ 1 : d.aov_side;
+  // the side written: never the one that holds the carry's planes (history off: always side 0); the same
+  // planes again (for the plane they lack): the side they are in, which gets the values it holds
+  const int side = same ? d.aov_side : d.carry.valid ? d.carry.side ^ 1 : d.aov_side;
   sptr::DevBuf& nzb = side ? d.nz1 : d.nz;
   sptr::DevBuf& idb = side ? d.ids1 : d.ids;
-  if (nzb.bytes < n * 16 || d.albedo.bytes < n * 16 || idb.bytes < n * 8) {
+  if (nzb.bytes < n * 16 || d.albedo.bytes < n * 16 || idb.bytes < n * 8 || (uv && d.ruv.bytes < n * 16)) {
     if (sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;  // a pending pass may still read the old planes
     API_HIP(nzb.ensure(n * 16));
     API_HIP(d.albedo.ensure(n * 16));
     API_HIP(idb.ensure(n * 8));
+    if (uv) API_HIP(d.ruv.ensure(n * 16));
   }
-  if (d.last.valid && d.last.side == side) d.last.valid = false;  // its planes are overwritten below
+  if (!same && d.last.valid && d.last.side == side) d.last.valid = false;  // its planes are overwritten below
   if (!d.flag.p) {
     API_HIP(d.flag.ensure(16));
     API_HIP(hipMemset(d.flag.p, 0, 16));
@@ -2649,6 +2678,7 @@ static int ensure_aov(sptr_ctx* x, const sptr_camera& cam, int W, int H, hipStre
   a.nz = static_cast<float4*>(nzb.p);
   a.albedo = static_cast<float4*>(d.albedo.p);
   a.ids = static_cast<uint2*>(idb.p);
+  a.ruv = uv ? static_cast<float4*>(d.ruv.p) : nullptr;
   a.tri_orig = static_cast<const uint32_t*>(c.tri_orig.p);
   a.geom_first = static_cast<const uint32_t*>(x->geom_first.p);
   a.mats = static_cast<const DevMaterial*>(c.mats.p);
@@ -2663,6 +2693,7 @@ static int ensure_aov(sptr_ctx* x, const sptr_camera& cam, int W, int H, hipStre
   d.aov_W = W;
   d.aov_H = H;
   d.aov_side = side;
+  d.aov_uv = uv;
   ++d.aov_passes;
   *ran = true;
   return SPTR_OK;
@@ -2685,6 +2716,7 @@ static int enqueue_denoise(sptr_ctx* x, const sptr_frame* f, hipStream_t s) {
   }
   const bool history = d.hp.max_history != 0u;
   d.hist_ran = false;
+  bool use_motion = false;
   if (history) {
     // the carry rules: a pass of another size or scene state is no history; a call that starts an
     // accumulation takes the last pass as its carry, one that continues it keeps the carry it has
@@ -2692,6 +2724,16 @@ static int enqueue_denoise(sptr_ctx* x, const sptr_frame* f, hipStream_t s) {
     if (stale(d.last)) d.last.valid = false;
     if (stale(d.carry)) d.carry.valid = false;
     if (f->frame_begin == 1) d.carry = d.last;
+    // a carry of an earlier geometry (sptr_update_geometry since; it is here only with motion on, which kept
+    // its epoch current) is read through the snapshot of that geometry, or not at all
+    use_motion = d.carry.valid && d.carry.gen != d.geom_gen;
+    if (use_motion && !(d.motion_on && d.snap_valid && d.snap_gen == d.carry.gen &&
+                        c.rf.snap.bytes >= (size_t)c.num_tri_refs * 48 + (size_t)c.num_sph * 16))
+      d.carry.valid = use_motion = false;
+    if (d.motion_on && d.motion.bytes < n * 8) {
+      if (sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;
+      API_HIP(d.motion.ensure(n * 8));
+    }
     if (d.hist[0].bytes < n * 16 || d.hist[1].bytes < n * 16 || d.nz1.bytes < n * 16 || d.ids1.bytes < n * 8 ||
         d.nz.bytes < n * 16 || d.ids.bytes < n * 8 || !d.hcount.p) {
       if (sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;
@@ -2701,12 +2743,13 @@ static int enqueue_denoise(sptr_ctx* x, const sptr_frame* f, hipStream_t s) {
       for (sptr::DevBuf* b : {&d.hist[0], &d.hist[1], &d.nz, &d.nz1}) API_HIP(b->ensure(n * 16));
       for (sptr::DevBuf* b : {&d.ids, &d.ids1}) API_HIP(b->ensure(n * 8));
       API_HIP(d.hcount.ensure(16));
+      use_motion = false;
     }
     for (DevEvent& e : d.hev)
       if (!e) API_HIP(hipEventCreate(e.put()));
   }
   bool aov_ran = false;
-  const int rc = ensure_aov(x, f->camera, W, H, s, true, &aov_ran);
+  const int rc = ensure_aov(x, f->camera, W, H, s, true, &aov_ran, history && d.motion_on);
   if (rc != SPTR_OK) return rc;
   d.aov_timed = aov_ran;
   DenoiseView v{};
@@ -2751,6 +2794,17 @@ static int enqueue_denoise(sptr_ctx* x, const sptr_frame* f, hipStream_t s) {
       // a history seen from elsewhere is clipped to the current neighbourhood's colours; a
       // standing camera's estimates the same integrand and is taken whole
       r.clip = std::memcmp(&k, &f->camera, sizeof(k)) != 0 ? kHistoryClip : 0.0f;
+      if (use_motion) {
+        // shadows and reflections belong to the scene state as they belong to the view: always clipped
+        r.clip = kHistoryClip;
+        r.ruv = static_cast<const float4*>(d.ruv.p);
+        r.tris_prev = static_cast<const float4*>(c.rf.snap.p);
+        r.sph_prev = r.tris_prev + (size_t)c.num_tri_refs * 3;
+        r.sph = static_cast<const float4*>(c.sph.p);
+        r.num_tris = c.num_tri_refs;
+        r.num_sph = c.num_sph;
+        r.motion = static_cast<float2*>(d.motion.p);
+      }
     }
     r.hist = static_cast<float4*>(d.hist[slot].p);
     r.max_history = float(d.hp.max_history);
@@ -2763,7 +2817,8 @@ static int enqueue_denoise(sptr_ctx* x, const sptr_frame* f, hipStream_t s) {
     fr.max_depth = 1;
     API_HIP(hipMemsetAsync(d.hcount.p, 0, 4, s));
     API_HIP(hipEventRecord(d.hev[0], s));
-    launch_dn_reproject(v, frame_view(c, fr), r, s);
+    if (use_motion) launch_dn_reproject_motion(v, frame_view(c, fr), r, s);
+    else launch_dn_reproject(v, frame_view(c, fr), r, s);
     API_HIP(hipEventRecord(d.hev[1], s));
     const float4* in = r.hist;
     for (uint32_t i = 0; i < d.p.iterations; ++i) {
@@ -2775,6 +2830,8 @@ static int enqueue_denoise(sptr_ctx* x, const sptr_frame* f, hipStream_t s) {
     d.hist_ran = true;
     d.hist_carried = d.carry.valid;
     d.hist_slot = slot;
+    d.motion_used = use_motion;
+    d.last.gen = d.geom_gen;
     d.last.valid = true;
     d.last.slot = (int)slot;
     d.last.side = d.aov_side;
@@ -2834,14 +2891,16 @@ int sptr_render(sptr_ctx* x, const sptr_frame* f, void* stream, sptr_stats* stat
 int sptr_read_aov(sptr_ctx* x, int kind, void* out) {
   if (!x || !out) return SPTR_ERR_INVALID;
   Context& c = x->c;
-  if (kind < SPTR_AOV_ALBEDO || kind > SPTR_AOV_ID) return fail(c, SPTR_ERR_INVALID, "read_aov: unknown kind");
+  if (kind < SPTR_AOV_ALBEDO || kind > SPTR_AOV_UV) return fail(c, SPTR_ERR_INVALID, "read_aov: unknown kind");
   if (!c.have_scene || x->dn.last_W <= 0) return fail(c, SPTR_ERR_NO_SCENE, "read_aov: nothing rendered");
   if (shading(c).mats_host.empty()) return fail(c, SPTR_ERR_NO_SCENE, "read_aov: no materials set");
   API_HIP(hipSetDevice(c.device));
   if (sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;
   auto& d = x->dn;
   bool ran = false;
-  const int rc = ensure_aov(x, d.last_cam, d.last_W, d.last_H, c.stream, false, &ran);
+  // (cached planes that hold the reference plane serve every kind; new ones get it as the passes ask for it)
+  const int rc = ensure_aov(x, d.last_cam, d.last_W, d.last_H, c.stream, false, &ran,
+                            kind == SPTR_AOV_UV || (d.motion_on && d.hp.max_history != 0u));
   if (rc != SPTR_OK) return rc;
   API_HIP(hipStreamSynchronize(c.stream));
   uint32_t flag = 0;
@@ -2853,11 +2912,14 @@ int sptr_read_aov(sptr_ctx* x, int kind, void* out) {
     return SPTR_OK;
   }
   std::vector<float> tmp(n * 4);
-  API_HIP(hipMemcpy(tmp.data(), kind == SPTR_AOV_ALBEDO ? d.albedo.p : (d.aov_side ? d.nz1.p : d.nz.p), n * 16,
-                    hipMemcpyDeviceToHost));
+  API_HIP(hipMemcpy(tmp.data(), kind == SPTR_AOV_ALBEDO ? d.albedo.p : kind == SPTR_AOV_UV ? d.ruv.p : (d.aov_side ? d.nz1.p : d.nz.p),
+                    n * 16, hipMemcpyDeviceToHost));
   float* o = static_cast<float*>(out);
   for (size_t i = 0; i < n; ++i) {
-    if (kind == SPTR_AOV_DEPTH) {
+    if (kind == SPTR_AOV_UV) {
+      o[i * 2 + 0] = tmp[i * 4 + 1];
+      o[i * 2 + 1] = tmp[i * 4 + 2];
+    } else if (kind == SPTR_AOV_DEPTH) {
       o[i] = tmp[i * 4 + 3];
     } else {
       o[i * 3 + 0] = tmp[i * 4 + 0];
@@ -2962,6 +3024,48 @@ int sptr_history_info(sptr_ctx* x, uint32_t* reprojected, double* ms_reproject, 
   if (reprojected) *reprojected = n;
   if (ms_reproject) *ms_reproject = ms;
   if (carried) *carried = ran && d.hist_carried ? 1u : 0u;
+  return SPTR_OK;
+}
+
+// ---- motion vectors: the history across geometry updates -----------------------------
+int sptr_set_history_motion(sptr_ctx* x, uint32_t on) {
+  if (!x) return SPTR_ERR_INVALID;
+  Context& c = x->c;
+  if (x->is_lane) return fail(c, SPTR_ERR_INVALID, "history motion: not on a lane context");
+  auto& d = x->dn;
+  d.motion_on = on != 0u;
+  // the history held and the snapshot are dropped, as sptr_set_denoise_history drops the history (nothing
+  // is freed here: a pending pass keeps the buffers it was enqueued with)
+  d.last.valid = d.carry.valid = false;
+  d.snap_valid = false;
+  d.hist_ran = false;
+  d.motion_used = false;
+  d.aov_epoch = 0;
+  d.aov_side = 0;
+  return SPTR_OK;
+}
+
+int sptr_read_motion(sptr_ctx* x, float* out) {
+  if (!x || !out) return SPTR_ERR_INVALID;
+  Context& c = x->c;
+  auto& d = x->dn;
+  if (x->is_lane) return fail(c, SPTR_ERR_INVALID, "read_motion: not on a lane context");
+  if (!d.ran || !d.hist_ran || !d.motion_used)
+    return fail(c, SPTR_ERR_INVALID, "read_motion: the last render call ran no pass on the motion path (sptr_set_history_motion)");
+  API_HIP(hipSetDevice(c.device));
+  if (sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;
+  API_HIP(hipMemcpy(out, d.motion.p, (size_t)d.last_W * d.last_H * 8, hipMemcpyDeviceToHost));
+  return SPTR_OK;
+}
+
+int sptr_motion_info(sptr_ctx* x, uint32_t* snapshots, double* ms_snapshot, uint32_t* used) {
+  if (!x) return SPTR_ERR_INVALID;
+  Context& c = x->c;
+  if (x->is_lane) return fail(c, SPTR_ERR_INVALID, "motion_info: not on a lane context");
+  const auto& d = x->dn;
+  if (snapshots) *snapshots = c.rf.snapshots;
+  if (ms_snapshot) *ms_snapshot = c.rf.ms_snapshot;
+  if (used) *used = d.ran && d.hist_ran && d.motion_used ? 1u : 0u;
   return SPTR_OK;
 }
 

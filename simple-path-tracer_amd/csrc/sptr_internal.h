@@ -302,6 +302,10 @@ struct AovView {
   float4* nz;      // normal.xyz (facing the camera), depth t; a miss: 0 0 0 -1
   float4* albedo;  // albedo.xyz, 0; a miss: 0
   uint2* ids;      // geomID, primID; a miss: kNoHit twice
+  // or null (no extra work): the traversal's reference (slot, sphere bit) as bits, the barycentrics u, v as
+  // k_rayquery computes them, 0; a sphere hit: u = v = 0; a miss: kNoHit's bits, 0, 0, 0 (SPTR_AOV_UV and the
+  // history's motion vectors)
+  float4* ruv;
   const uint32_t* tri_orig;    // triangle slot -> index in the uploaded triangle list
   const uint32_t* geom_first;  // geomID -> its first triangle in that list
   const DevMaterial* mats;
@@ -346,6 +350,13 @@ struct ReprojView {
   float max_history;        // M
   float clip;               // gamma of the variance clip of h (0: none, the carry's camera is the call's)
   uint32_t* count;          // pixels that took history (zeroed before the launch)
+  // k_dn_reproject<true> only (sptr_set_history_motion): the carry saw an earlier geometry
+  const float4* ruv;        // the current pass's reference / barycentric plane (AovView::ruv)
+  const float4* tris_prev;  // the snapshot's triangle records, 3 float4 per slot (tri_record's layout) ...
+  const float4* sph_prev;   // ... and spheres
+  const float4* sph;        // the current spheres
+  uint32_t num_tris, num_sph;  // slots of each kind: a reference beyond them takes no history
+  float2* motion;           // out: (fx - x, fy - y); a quiet NaN twice where the projection is not reached
 };
 
 // One lane's path-state streams: ray streams, hit records, radiance, shadow tasks, and
@@ -420,6 +431,12 @@ struct RefitState {
   DevEvent ev[4];          // begin, after the slot pass, after the BVH2 pass, end
   uint32_t refits = 0;     // since the upload
   double ms_wall = 0.0, ms_device = 0.0, ms_stage[3] = {0.0, 0.0, 0.0};  // of the last refit
+  // sptr_set_history_motion: the triangle records (48 B per slot) and then the spheres (16 B each) as they
+  // were before a refit overwrote them (refit_snapshot; allocated at the first snapshot)
+  DevBuf snap;
+  DevEvent snap_ev[2];
+  uint32_t snapshots = 0;  // since the upload
+  double ms_snapshot = 0.0;  // device ms of the last one
 };
 
 struct Context {
@@ -537,6 +554,9 @@ int build_lbvh(Context& c, const float* h_pos, uint32_t nverts, const uint32_t* 
 int refit_retain_slots(Context& c, const float* d_pos, const uint32_t* d_idx, const float4* d_sph);
 void launch_wide_sources(uint32_t ncur, const uint2* cur, uint32_t base, const BvhNode* nodes, uint32_t* wsrc, hipStream_t s);
 int refit_lbvh(Context& c, const float* d_pos, const float4* d_sph);
+// the triangle records and spheres copied into RefitState::snap on c.stream (sptr_set_history_motion: taken
+// before refit_lbvh overwrites them); returns when done
+int refit_snapshot(Context& c);
 void refit_release(Context& c);  // the buffers; the events stay for the next dynamic upload
 
 // kernels_sort.hip: the build's device primitives (temp == nullptr: set temp_bytes only)
@@ -627,6 +647,8 @@ void launch_dn_resolve(const DenoiseView& v, const float4* c, uint8_t* image, hi
 // history on: the integration after launch_dn_mean, and the iterations whose colour sigma is per pixel
 // (Si = sigma_c 2^-i; the pixel's n_eff is the colour image's w)
 void launch_dn_reproject(const DenoiseView& v, const FrameView& f, const ReprojView& r, hipStream_t s);
+// ... through the previous geometry (ReprojView's motion fields set)
+void launch_dn_reproject_motion(const DenoiseView& v, const FrameView& f, const ReprojView& r, hipStream_t s);
 void launch_atrous_history(const DenoiseView& v, const float4* cin, float4* cout, int step, float Si, hipStream_t s);
 // kernels_query.h: one batch of ray queries (sptr_query_rays), and the sort keys of a batch with the
 // identity indices 0..n-1 beside them (the radix sort's values)

@@ -114,6 +114,10 @@ bool HipBackend::syncState() {
     if (sptr_set_denoise_history(ctx_, &settings_.history) != SPTR_OK) return false;
     history_applied_ = settings_.history;
   }
+  if (settings_.motion != motion_applied_) {
+    if (sptr_set_history_motion(ctx_, settings_.motion ? 1u : 0u) != SPTR_OK) return false;
+    motion_applied_ = settings_.motion;
+  }
   return true;
 }
 

@@ -45,6 +45,9 @@ class HipBackend {
     // without a number of one's own), and each restart advances the seed offset (sptr_set_seed_offset) by the
     // frames of the accumulation it ends, so that consecutive restarts draw fresh samples
     sptr_history_params history{};
+    // sptr_set_history_motion, applied with the history settings: update() keeps the history, which the next
+    // pass reads through a snapshot of the geometry it saw (motion vectors)
+    bool motion = false;
     // sptr_set_dynamic, applied before build(): the build keeps what update() needs to refit the BVH in
     // place when only coordinates change
     bool dynamic = false;
@@ -96,6 +99,11 @@ class HipBackend {
   bool historyInfo(uint32_t* reprojected, double* ms_reproject, uint32_t* carried) const {
     return ctx_ && sptr_history_info(ctx_, reprojected, ms_reproject, carried) == SPTR_OK;
   }
+  // sptr_motion_info: snapshots since the last build, device ms of the last one, whether the last render()'s
+  // pass took the motion path
+  bool motionInfo(uint32_t* snapshots, double* ms_snapshot, uint32_t* used) const {
+    return ctx_ && sptr_motion_info(ctx_, snapshots, ms_snapshot, used) == SPTR_OK;
+  }
   // sptr_query_rays with host pointers: n rays of 8 floats (o3, d3, tnear, tfar) against the built scene,
   // traced by the renderer's traversal.  Closest hit fills geom, prim, t, ng (n x 3) and uv (n x 2) as
   // include/sptr_hip.h describes them (a miss: geom = prim = 0xFFFFFFFF, t = +inf); anyHit fills occluded.
@@ -138,6 +146,7 @@ class HipBackend {
   uint32_t lanes_applied_ = 0;  // the pixel-lane setting the context holds
   sptr_denoise_params denoise_applied_{};  // the denoiser parameters the context holds
   sptr_history_params history_applied_{};  // the history parameters the context holds
+  bool motion_applied_ = false;            // the motion setting the context holds
   uint32_t seed_offset_ = 0;    // the seed offset the context holds (history on: advanced at every restart)
   uint32_t acc_frames_ = 0;     // frames of the accumulation the last render() call added to
   sptr_stats flushed_{};        // counters since the last flushStats()

@@ -128,7 +128,7 @@ class RayQuery(C.Structure):
                 ("occluded", C.c_void_p), ("reserved", C.c_uint64 * 4)]
 
 
-SPTR_AOV_ALBEDO, SPTR_AOV_NORMAL, SPTR_AOV_DEPTH, SPTR_AOV_ID = 0, 1, 2, 3
+SPTR_AOV_ALBEDO, SPTR_AOV_NORMAL, SPTR_AOV_DEPTH, SPTR_AOV_ID, SPTR_AOV_UV = 0, 1, 2, 3, 4
 DEFAULT_MAX_HISTORY = 4  # the cap to ask set_denoise_history for without a number of one's own
 
 _lib = None
@@ -144,6 +144,7 @@ EXPORTS = [
     "sptr_sort_pairs_u64", "sptr_scan_u32", "sptr_eval_math",
     "sptr_set_denoise", "sptr_read_aov", "sptr_read_denoised", "sptr_denoise_info",
     "sptr_set_seed_offset", "sptr_set_denoise_history", "sptr_read_history", "sptr_history_info",
+    "sptr_set_history_motion", "sptr_read_motion", "sptr_motion_info",
     "sptr_set_dynamic", "sptr_update_geometry", "sptr_refit_info",
     "sptr_query_rays", "sptr_query_info",
     "sptr_host_builtin_scene", "sptr_host_scene_view", "sptr_host_scene_free", "sptr_host_camera_lookat",
@@ -208,6 +209,9 @@ def lib() -> C.CDLL:
         "sptr_set_denoise_history": (C.c_int, [vp, C.POINTER(HistoryParams)]),
         "sptr_read_history": (C.c_int, [vp, fp]),
         "sptr_history_info": (C.c_int, [vp, up, C.POINTER(C.c_double), up]),
+        "sptr_set_history_motion": (C.c_int, [vp, u32]),
+        "sptr_read_motion": (C.c_int, [vp, fp]),
+        "sptr_motion_info": (C.c_int, [vp, up, C.POINTER(C.c_double), up]),
         "sptr_set_dynamic": (C.c_int, [vp, u32]),
         "sptr_update_geometry": (C.c_int, [vp, vp, u32, vp, u32, u32]),
         "sptr_refit_info": (C.c_int, [vp, up, C.POINTER(C.c_double), C.POINTER(C.c_double), up]),
@@ -594,9 +598,11 @@ class Renderer:
     def read_aov(self, kind: int) -> np.ndarray:
         """First-hit feature buffer of the last render call's camera and size: SPTR_AOV_ALBEDO / _NORMAL
         (H, W, 3) float32, SPTR_AOV_DEPTH (H, W) float32 (-1 on a miss), SPTR_AOV_ID (H, W, 2) uint32
-        (geomID, primID; 0xFFFFFFFF on a miss)."""
+        (geomID, primID; 0xFFFFFFFF on a miss), SPTR_AOV_UV (H, W, 2) float32 (query_rays' barycentrics; 0 on
+        a sphere or a miss)."""
         shape, dt = {SPTR_AOV_ALBEDO: ((3,), np.float32), SPTR_AOV_NORMAL: ((3,), np.float32),
-                     SPTR_AOV_DEPTH: ((), np.float32), SPTR_AOV_ID: ((2,), np.uint32)}[kind]
+                     SPTR_AOV_DEPTH: ((), np.float32), SPTR_AOV_ID: ((2,), np.uint32),
+                     SPTR_AOV_UV: ((2,), np.float32)}[kind]
         out = np.zeros((self.height, self.width) + shape, dt)
         self._check(self._L.sptr_read_aov(self._h, kind, out.ctypes.data_as(C.c_void_p)), "read_aov")
         return out
@@ -636,6 +642,24 @@ class Renderer:
         n, ms, k = C.c_uint32(), C.c_double(), C.c_uint32()
         self._check(self._L.sptr_history_info(self._h, C.byref(n), C.byref(ms), C.byref(k)), "history_info")
         return {"reprojected": n.value, "ms_reproject": ms.value, "carried": bool(k.value)}
+
+    def set_history_motion(self, on: bool = True):
+        """sptr_set_history_motion: update_geometry keeps the denoiser's history, which the next pass reads
+        through a snapshot of the geometry it saw (motion vectors).  Any call drops the history held."""
+        self._check(self._L.sptr_set_history_motion(self._h, 1 if on else 0), "set_history_motion")
+
+    def read_motion(self) -> np.ndarray:
+        """The last motion pass's vectors: (H, W, 2) float32, where the pixel's surface point was in the carry's
+        image relative to the pixel; NaN where the projection is not reached (a miss)."""
+        out = np.zeros((self.height, self.width, 2), np.float32)
+        self._check(self._L.sptr_read_motion(self._h, _f(out)), "read_motion")
+        return out
+
+    def motion_info(self) -> dict:
+        """Snapshots since the upload, device ms of the last one, whether the last pass took the motion path."""
+        n, ms, k = C.c_uint32(), C.c_double(), C.c_uint32()
+        self._check(self._L.sptr_motion_info(self._h, C.byref(n), C.byref(ms), C.byref(k)), "motion_info")
+        return {"snapshots": n.value, "ms_snapshot": ms.value, "used": bool(k.value)}
 
     def tiles_device(self) -> tuple[int, int]:
         p = C.c_void_p()

@@ -5,7 +5,7 @@
 //   sptr_cli [--scene default|default_emitter|test_triangle|sphere_mesh:STACKS:SLICES|gltf:PATH]
 //            [--w 800] [--h 600] [--spp 4] [--depth 6] [--env sky|FILE.hdr] [--out image.ppm]
 //            [--warmup N] [--json] [--integrator wavefront|pathtracer|optix] [--spf 4] [--launch-mode 0-3]
-//            [--lagged] [--denoise N] [--history [M]] [--orbit DEG] [--animate K [--rebuild]] [--query-centre-rays]
+//            [--lagged] [--denoise N] [--history [M]] [--motion] [--orbit DEG] [--animate K [--rebuild]] [--query-centre-rays]
 // --spp N renders N progressive frames of 1 spp each (GLRenderer's m_accumulated_samples loop);
 // --warmup N renders N untimed frames first (then restarts the accumulation by a camera change);
 // --json prints one line with per-frame wall-clock statistics (render + RGB8 read back, as the
@@ -25,6 +25,9 @@
 // place: Settings::dynamic) and the accumulation restarts; the last frame is written.  --rebuild: the same
 // loop through HipBackend::build instead.  The --json line adds refits, the mean ms_refit_wall /
 // ms_refit_device of the updates and the mean ms_build of the rebuild loop's builds.
+// --motion: HipBackend::Settings::motion, meaningful with --animate K --denoise N --history: the updates keep the
+// history, read through a snapshot of the geometry it saw; the --json line's snapshots / ms_snapshot are the
+// snapshots taken and the mean device time of one.
 // --query-centre-rays: after the render, the W x H pixel-centre rays of the camera (the rays of the first-hit
 // AOVs: direction getRayDirection((x + 0.5) / W, (y + 0.5) / H), tnear 0, tfar inf) go through
 // HipBackend::queryRays; the --json line adds "query": {"rays": n, "hits": h, "tri_hits": k}.
@@ -62,7 +65,7 @@ static bool build_scene(const std::string& s, scene::SceneDesc& sd, MaterialMana
 int main(int argc, char** argv) {
   std::string scene_name = "default", env = "sky", out = "image.ppm";
   int w = 800, h = 600, spp = 4, depth = 6, warmup = 0;
-  bool json = false, lagged = false, rebuild = false, query_centre = false;
+  bool json = false, lagged = false, rebuild = false, query_centre = false, motion = false;
   int animate = 0;
   std::string integrator = "wavefront";
   int spf = 4, launch_mode = 0, denoise = 0, history = 0;
@@ -87,12 +90,13 @@ int main(int argc, char** argv) {
     else if (a == "--history") {
       history = int(backends::HipBackend::kDefaultMaxHistory);
       if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') history = std::atoi(next());
-    } else if (a == "--orbit") orbit = std::atof(next());
+    } else if (a == "--motion") motion = true;
+    else if (a == "--orbit") orbit = std::atof(next());
     else if (a == "--animate") animate = std::atoi(next());
     else if (a == "--rebuild") rebuild = true;
     else if (a == "--query-centre-rays") query_centre = true;
     else {
-      std::fprintf(stderr, "usage: %s [--scene S] [--w W] [--h H] [--spp N] [--depth D] [--env sky|F.hdr] [--out F] [--warmup N] [--json] [--lagged] [--denoise N] [--history [M]] [--orbit DEG] [--animate K [--rebuild]] [--query-centre-rays]\n",
+      std::fprintf(stderr, "usage: %s [--scene S] [--w W] [--h H] [--spp N] [--depth D] [--env sky|F.hdr] [--out F] [--warmup N] [--json] [--lagged] [--denoise N] [--history [M]] [--motion] [--orbit DEG] [--animate K [--rebuild]] [--query-centre-rays]\n",
                    argv[0]);
       return 2;
     }
@@ -128,6 +132,7 @@ int main(int argc, char** argv) {
   st.lagged_readback = lagged;
   st.denoise.iterations = uint32_t(std::max(0, denoise));
   st.history.max_history = uint32_t(std::max(0, history));
+  st.motion = motion;
   st.dynamic = animate > 0 && !rebuild;
   be.setSettings(st);
   if (!be.build(sd)) {
@@ -145,8 +150,8 @@ int main(int argc, char** argv) {
   uint32_t aov_passes = 0;
   int dn_frames = 0;
   (void)be.flushStats();  // (the warmup's counters)
-  double ms_refit_wall = 0.0, ms_refit_device = 0.0, ms_build = 0.0;
-  uint32_t refits = 0;
+  double ms_refit_wall = 0.0, ms_refit_device = 0.0, ms_build = 0.0, ms_snapshot = 0.0;
+  uint32_t refits = 0, snapshots = 0;
   int moves = 0;
   const auto t0 = std::chrono::steady_clock::now();
   const int shots = std::max(1, animate), total_frames = shots * spp;
@@ -169,6 +174,12 @@ int main(int argc, char** argv) {
         (void)be.refitInfo(&refits, &mw, &md, nullptr);
         ms_refit_wall += mw;
         ms_refit_device += md;
+        uint32_t sn = 0;
+        double msn = 0.0;
+        if (motion && be.motionInfo(&sn, &msn, nullptr) && sn != snapshots) {
+          snapshots = sn;
+          ms_snapshot += msn;
+        }
       }
     }
     if (orbit != 0.0) {  // the next camera on the orbit about the target
@@ -231,11 +242,11 @@ int main(int argc, char** argv) {
     std::printf("{\"scene\": \"%s\", \"launch_mode\": %d, \"width\": %d, \"height\": %d, \"frames\": %d, \"spp_per_frame\": 1, "
                 "\"depth\": %d, \"ms_per_frame_wall\": %.4f, \"ms_per_frame_p50\": %.4f, \"ms_per_frame_p99\": %.4f, "
                 "\"ms_per_frame_device\": %.4f, \"fps\": %.1f, \"mrays_per_s_wall\": %.1f, "
-                "\"lagged_readback\": %s, \"denoise\": %d, \"ms_aov\": %.4f, \"ms_filter\": %.4f, \"aov_passes\": %u, \"history\": %d, \"reprojected\": %.1f, \"ms_reproject\": %.4f, \"animate\": %d, \"refits\": %u, \"ms_refit_wall\": %.4f, \"ms_refit_device\": %.4f, \"ms_build\": %.4f, \"path\": \"backends::HipBackend::render (sptr_render + %s per frame)\"",
+                "\"lagged_readback\": %s, \"denoise\": %d, \"ms_aov\": %.4f, \"ms_filter\": %.4f, \"aov_passes\": %u, \"history\": %d, \"reprojected\": %.1f, \"ms_reproject\": %.4f, \"motion\": %d, \"snapshots\": %u, \"ms_snapshot\": %.4f, \"animate\": %d, \"refits\": %u, \"ms_refit_wall\": %.4f, \"ms_refit_device\": %.4f, \"ms_build\": %.4f, \"path\": \"backends::HipBackend::render (sptr_render + %s per frame)\"",
                 scene_name.c_str(), launch_mode, w, h, total_frames, depth, wall / total_frames, pct(0.5), pct(0.99), ms / total_frames,
                 wall > 0 ? 1e3 * total_frames / wall : 0.0, wall > 0 ? rays / (wall * 1e3) : 0.0, lagged ? "true" : "false", denoise, dn_frames ? ms_aov / dn_frames : 0.0,
                 dn_frames ? ms_filter / dn_frames : 0.0, aov_passes, history, dn_frames ? reprojected / dn_frames : 0.0,
-                dn_frames ? ms_reproject / dn_frames : 0.0, animate, refits,
+                dn_frames ? ms_reproject / dn_frames : 0.0, motion ? 1 : 0, snapshots, snapshots ? ms_snapshot / snapshots : 0.0, animate, refits,
                 moves && !rebuild ? ms_refit_wall / moves : 0.0, moves && !rebuild ? ms_refit_device / moves : 0.0,
                 moves && rebuild ? ms_build / moves : 0.0,
                 lagged ? "sptr_read_rgb8_lagged" : "sptr_read_rgb8");
