@@ -23,6 +23,7 @@
 #include <cstdlib>
 #include <mutex>
 
+#include "cull_prims.h"
 #include "sptr_internal.h"
 
 // Occupancy hints (min waves per SIMD); 1 = let the register allocator decide.
@@ -1008,6 +1009,45 @@ __device__ __forceinline__ bool traverse_w(const Staged& sc, const SceneView& sv
   return traverse<kAny, kCount>(sc.nodes, sc.prim_ref, sc.tris, sc.sph, sv.root, r, tnear, tfar, ref, vc, ls);
 }
 
+// Leaf entry word of the exact cull (k_cull<true>): kLeafBit | parent node << 18 | side << 17 | first prim_ref
+// position << 4 | (count - 1): child `side` (0 left, 1 right) of the parent is the leaf; 13 bits each for the
+// node and the position.  An LDS-staged scene (<= 48 KB) holds under 768 nodes and under 2500 references (a
+// sphere costs 16 + 4 bytes), so both fit and kNoHit, all ones, is no leaf entry; entry_leaf falls back to the
+// parent node as a plain entry should a value ever not fit.
+constexpr uint32_t kEntryFieldBits = 13, kEntryFieldMask = (1u << kEntryFieldBits) - 1u;
+// traverse_w of a bounce-0 camera ray from the walk root its pixel starts at (primary_root: kNoHit, a node,
+// the scene's own leaf-range root, or a leaf entry); the wide BVH has no entries and starts at its root
+template <bool kW4, bool kCount, int N>
+__device__ __forceinline__ bool traverse_w_from(const Staged& sc, const SceneView& sv, uint32_t root, const Ray& r,
+                                                float& tfar, uint32_t& ref, Visits& vc, LdsStackN<N>& ls) {
+  if constexpr (kW4) {
+    return traverse_wide<false, kCount>(sc.nodes4, sc.prim_ref, sc.tris, sc.sph, sv.root4, r, 0.0f, tfar, ref, vc, ls);
+  } else {
+    if (root & kLeafBit) {  // (kNoHit too: the caller tests it first)
+      // the scene's own root when the scene is one leaf range; else a leaf entry (k_cull<true>, entry_leaf): the
+      // leaf's box, held by its parent, then the entry's sub-range
+      if (root == sv.root) return leaf_test<false, kCount>(root, sc.prim_ref, sc.tris, sc.sph, r, 0.0f, tfar, ref, vc);
+      // The one child's six planes are read by address (16 + 8 bytes), not both boxes and a select.
+      // The entry is decoded here, at each use.  It is a per-pixel value: hoisted out of the callers' sample
+      // loops, the decoded addresses stayed live across them (k_trace_wp: three registers spilled, two reloads
+      // per round).  The empty asm keeps the decode behind it.  To re-verify after a compiler change: build with
+      // -Rpass-analysis=kernel-resource-usage and compare k_trace_wp<true, false, false, false, false, false> and
+      // its kHiOcc form with DESIGN.md section 4 (72 VGPRs, 352 B scratch, no VGPR spill; 64, 368 B, 4 spills).
+      asm volatile("" : "+v"(root));
+      const float4* nd = reinterpret_cast<const float4*>(sc.nodes + ((root >> 18) & kEntryFieldMask));
+      const uint32_t right = (root >> 17) & 1u;
+      const float4 xy = nd[right];                                               // lxy | rxy
+      const float2 z = reinterpret_cast<const float2*>(nd + 2)[right];           // z.xy | z.zw
+      if (kCount) ++vc.nodes;
+      float tent;
+      if (!slab(xy.x, xy.y, xy.z, xy.w, z.x, z.y, r, 0.0f, tfar, tent)) return false;
+      const uint32_t range = kLeafBit | (((root >> 4) & kEntryFieldMask) << kLeafCountBits) | (root & kLeafRangeMask);
+      return leaf_test<false, kCount>(range, sc.prim_ref, sc.tris, sc.sph, r, 0.0f, tfar, ref, vc);
+    }
+    return traverse<false, kCount>(sc.nodes, sc.prim_ref, sc.tris, sc.sph, root, r, 0.0f, tfar, ref, vc, ls);
+  }
+}
+
 // traverse_w with the wide BVH's top levels read from an LDS copy (stage_top; ntop = 0: none) — the
 // path-per-thread kernels of L2/HBM scenes (k_tail, k_strag), whose every ray starts at the root
 template <bool kW4, bool kAny, bool kCount, int N>
@@ -1177,25 +1217,189 @@ __device__ __forceinline__ bool pixel_frustum_misses(const SceneView& sv, const 
   }
   return true;
 }
+// The exact cull of LDS-staged BVH2 scenes (k_cull<true>): the descent goes on below the cut depth of
+// pixel_frustum_misses down to the leaves (f.cull_depth only bounds it for pathological trees: a node
+// that survives at the bound counts as a candidate itself), and a leaf whose box the quad's pyramid
+// may touch is no candidate outright: each primitive of its range is tested against the pyramid
+// (cull_prims.h).  The result is the quad's entry word, where a camera ray of its pixels may start
+// its walk:
+//   no candidate                     kNoHit (the pixels' mask bits are set)
+//   all candidates in one leaf       a leaf entry (entry_leaf): the leaf's parent node and side, whose box the
+//                                    walk tests first, and the smallest sub-range of the leaf holding them
+//   otherwise                        the lowest common ancestor of the candidate leaves and nodes
+// A subtree whose box the pyramid misses holds no hit of any ray of the quad (the invariant the mask
+// rests on, per subtree), so a walk from the root changes neither tfar nor ref there; inside the
+// entry's subtree it visits the same nodes and primitives in the same relative order (near-child
+// order and the leaf loop are local), so ties resolve as before and results are bit-identical.
+// The box tests the entry skips are those of the entry's ancestors and of the entry node itself, and none
+// of them can reject a ray that one of the boxes below accepts: a node's box is the exact min / max of its
+// children's, slab()'s plane distances are monotone in the plane (float subtraction and multiplication
+// are), so the enclosing box has tmin no larger and tmax no smaller, and its tfar at the time was no
+// smaller either.  A leaf's own box has no box below it, so a leaf entry keeps that test: a grazing ray
+// that the sphere test accepts by rounding while the leaf's box rejects it must stay a miss (measured:
+// one such ray among the 133 M camera rays of a C2 step, when leaf entries skipped the box).
+// The ancestor needs no second path: the descent is depth first and keeps its root-to-node path; once
+// a candidate is found, every pop at depth d leaves at most the path's first d nodes in common with
+// it (the pop of a candidate leaf at depth d: exactly its d ancestors).
+constexpr int kCullEntryDepth = 20;  // descent bound of the exact cull (cull_depth_for)
+// The descent's stack and path live in LDS, a column per thread (entry-major, as the traversal stacks), so
+// that no push or pop is a scratch access.  A stack entry packs the child link (18 bits: an LDS-staged scene
+// holds under 8192 nodes and references), its depth and its side.  (Measured: no change against private
+// arrays, k_cull 39.9 -> 38.8 us alone on C2; the kernel's time is the VALU work of its longest waves, the
+// ones whose quads touch primitives, 5.67e6 wave-instructions per launch against the box cull's 1.95e6.)
+struct CullStack {
+  uint32_t st[kCullEntryDepth + 2][kBlock];
+  uint16_t path[kCullEntryDepth + 1][kBlock];
+};
+constexpr uint32_t kCullLeaf = 1u << 17;
+__device__ __forceinline__ uint32_t cull_pack(uint32_t link, uint32_t depth, uint32_t side) {
+  const uint32_t l = (link & kLeafBit) ? (kCullLeaf | (((link & ~kLeafBit) >> kLeafCountBits) << 4) | (link & kLeafRangeMask)) : link;
+  return l | (depth << 18) | (side << 24);
+}
+__device__ __forceinline__ Box child_box(const BvhNode& g, bool right) {
+  return right ? Box{v3(g.rxy.x, g.rxy.z, g.z.z), v3(g.rxy.y, g.rxy.w, g.z.w)}
+               : Box{v3(g.lxy.x, g.lxy.z, g.z.x), v3(g.lxy.y, g.lxy.w, g.z.y)};
+}
+// candidates of one leaf range: their first and last position in prim_ref (lo > hi: none)
+__device__ __forceinline__ void cull_leaf(const Staged& sc, const CullPyramid& py, uint32_t link, uint32_t& lo, uint32_t& hi) {
+  const uint32_t start = (link & ~kLeafBit) >> kLeafCountBits, cnt = (link & kLeafRangeMask) + 1u;
+  lo = kNoHit;
+  hi = 0u;
+  for (uint32_t j = 0; j < cnt; ++j) {
+    const uint32_t pr = sc.prim_ref[start + j];
+    const uint32_t idx = pr & kIndexMask;
+    // The primitive's own box against the side planes first (box_outside, ~40 instructions): most primitives
+    // of a touched leaf lie far from the quad, and the exact tests (a few hundred instructions, with square
+    // roots) then run only for those near it.  The boxes are padded by more than the exact tests' own
+    // inflation and rounding (cull_prims.h), so the prefilter culls nothing they would keep.
+    bool out;
+    if (pr & kSphereBit) {
+      const float4 s = sc.sph[idx];
+      const vec3 c = v3(s.x, s.y, s.z), v = c - py.o;
+      const float rb = fabsf(s.w) + 1.1e-3f * (fabsf(v.x) + fabsf(v.y) + fabsf(v.z)) +
+                       1e-5f * (py.ol + fabsf(c.x) + fabsf(c.y) + fabsf(c.z));
+      out = box_outside(Box{c - v3(rb, rb, rb), c + v3(rb, rb, rb)}, py.n, py.o) || cull_sphere_outside(py, c, s.w);
+    } else {
+      // triangle record: v0, e1 = v0 - v1, e2 = v2 - v0 (tri_hit4)
+      const float4 a = sc.tris[3u * idx], b = sc.tris[3u * idx + 1u], c = sc.tris[3u * idx + 2u];
+      const vec3 v0 = v3(a.x, a.y, a.z), v1 = v0 - v3(a.w, b.x, b.y), v2 = v0 + v3(b.z, b.w, c.x);
+      const vec3 lo3 = v3(fminf(v0.x, fminf(v1.x, v2.x)), fminf(v0.y, fminf(v1.y, v2.y)), fminf(v0.z, fminf(v1.z, v2.z)));
+      const vec3 hi3 = v3(fmaxf(v0.x, fmaxf(v1.x, v2.x)), fmaxf(v0.y, fmaxf(v1.y, v2.y)), fmaxf(v0.z, fmaxf(v1.z, v2.z)));
+      const float pad = 1e-5f * (fabsf(lo3.x) + fabsf(lo3.y) + fabsf(lo3.z) + fabsf(hi3.x) + fabsf(hi3.y) + fabsf(hi3.z) + py.ol);
+      out = box_outside(Box{lo3 - v3(pad, pad, pad), hi3 + v3(pad, pad, pad)}, py.n, py.o) || cull_triangle_outside(py, v0, v1, v2);
+    }
+    if (!out) {
+      lo = min(lo, start + j);
+      hi = start + j;
+    }
+  }
+}
+__device__ __forceinline__ uint32_t entry_leaf(uint32_t parent, uint32_t side, uint32_t lo, uint32_t hi) {
+  if (parent >= kEntryFieldMask || hi > kEntryFieldMask) return parent;  // (does not fit: the parent node, a plain entry)
+  return kLeafBit | (parent << 18) | (side << 17) | (lo << 4) | (hi - lo);
+}
+// sc: the scene as the block staged it in LDS (the descent's node and primitive reads are dependent loads)
+__device__ __forceinline__ uint32_t cull_entry(const Staged& sc, const SceneView& sv, const FrameView& f, int x, int y, int npx,
+                                               CullStack& cs) {
+  if (sv.root == kNoHit) return kNoHit;
+  const float u0 = (float(x) - kCullMarginPx) / float(f.W), u1 = (float(x + npx) + kCullMarginPx) / float(f.W);
+  const float v0 = (float(y) - kCullMarginPx) / float(f.H), v1 = (float(y + npx) + kCullMarginPx) / float(f.H);
+  auto dir = [&](float u, float v) {
+    return f.cam_f + ((u - 0.5f) * 2.0f * f.half_w) * f.cam_r + (-(v - 0.5f) * 2.0f * f.half_h) * f.cam_u;
+  };
+  const CullPyramid py = cull_pyramid(f.cam_pos, dir(u0, v0), dir(u1, v0), dir(u1, v1), dir(u0, v1));
+  uint32_t lo, hi;
+  // a scene that is one leaf range has no box to test first: as in the box cull, nothing is culled and every
+  // camera ray tests the range (tests/test_gpu_bounce_order.py counts on those rays being traced)
+  if ((sv.root & kLeafBit) || sv.num_nodes == 0u) return sv.root;
+  const uint32_t limit = min(f.cull_depth, (uint32_t)kCullEntryDepth);
+  uint32_t* st = &cs.st[0][threadIdx.x];     // entry i at st[i * kBlock]
+  uint16_t* path = &cs.path[0][threadIdx.x];  // likewise
+  int sp = 0;
+  // common: path nodes shared by all candidates so far, anc = the last of them; mind: the smallest depth
+  // popped since the last candidate (the path beyond it has been, or may be, overwritten)
+  uint32_t ncand = 0u, common = kNoHit, mind = kNoHit, anc = sv.root, one_lo = 0u, one_hi = 0u, one_side = 0u;
+  bool one_leaf = false;  // the candidates so far are primitives of one leaf, child one_side of anc: prim_ref[one_lo .. one_hi]
+  auto push_children = [&](uint32_t node, uint32_t depth) {  // the children whose boxes the pyramid may touch
+    const BvhNode g = sc.nodes[node];
+    path[(depth - 1u) * kBlock] = (uint16_t)node;
+    if (!box_outside(child_box(g, true), py.n, f.cam_pos)) st[sp++ * kBlock] = cull_pack(g.link.y, depth, 1u);
+    if (!box_outside(child_box(g, false), py.n, f.cam_pos)) st[sp++ * kBlock] = cull_pack(g.link.x, depth, 0u);
+  };
+  push_children(sv.root, 1u);
+  while (sp > 0) {
+    const uint32_t e = st[--sp * kBlock];
+    const uint32_t link = e & (kCullLeaf - 1u), depth = (e >> 18) & 63u, side = (e >> 24) & 1u;  // its ancestors: path[0 .. depth)
+    mind = min(mind, depth);
+    if (e & kCullLeaf) {
+      cull_leaf(sc, py, kLeafBit | ((link >> 4) << kLeafCountBits) | (link & kLeafRangeMask), lo, hi);
+      if (lo > hi) continue;
+      one_leaf = ncand++ == 0u;
+      common = one_leaf ? depth : min(common, mind);  // (the first candidate's ancestors: path[0 .. depth))
+      anc = path[(common - 1u) * kBlock];
+      mind = kNoHit;
+      one_lo = lo;
+      one_hi = hi;
+      one_side = side;
+    } else if (depth >= limit) {  // a node at the bound: a candidate itself
+      if (ncand++ == 0u) {
+        common = depth + 1u;
+        anc = link;
+      } else {
+        common = min(common, mind);
+        anc = path[(common - 1u) * kBlock];
+      }
+      mind = kNoHit;
+      one_leaf = false;
+    } else {
+      push_children(link, depth + 1u);
+    }
+  }
+  if (ncand == 0u) return kNoHit;
+  if (one_leaf) return entry_leaf(anc, one_side, one_lo, one_hi);
+  return anc;
+}
+// one entry word per 2x2 pixel quad, in k_cull's thread order: tile, then quad row, then quad column
+__device__ __forceinline__ uint32_t entry_index(uint32_t l) {
+  const uint32_t w = l & 1023u;
+  return ((l >> 10) << 8) | ((w >> 6) << 4) | ((w & 31u) >> 1);
+}
 // bit l of mask: pixel l is culled (see above).  plist: the valid pixels that are not culled, from
 // plist[0] (count at plist[P], zeroed before).  One block per local tile: thread (qx, qy) tests the 2x2
 // pixel quad at (2qx, 2qy) of the tile and sets the quad's bits in the tile's 32 LDS row words; then
 // each thread lists the pixels of 4 consecutive local indices, the tile's run at a range one atomic per
 // tile reserves.  (r02: a pyramid per pixel and one atomic per wave, C2 108 us; per pixel and per tile
 // 65-75 us.)
-__global__ void __launch_bounds__(kBlock) k_cull(SceneView sv, FrameView f, uint32_t* mask, uint32_t* plist) {
+// kEntry: the exact cull (cull_entry); the quad's entry word goes to entry[tile * 256 + thread].
+template <bool kEntry>
+__global__ void __launch_bounds__(kBlock) k_cull(SceneView sv, FrameView f, uint32_t* mask, uint32_t* plist, uint32_t* entry) {
   static_assert(kTile == 32 && kBlock == 256, "16 x 16 quads per 32 x 32 tile");
   __shared__ uint32_t s_row[kTile];
   __shared__ uint32_t s_cnt[kBlock / 64u];
   __shared__ uint32_t s_base;
   const uint32_t t0 = blockIdx.x * kTilePixels;  // the tile's first local pixel
   if (threadIdx.x < (uint32_t)kTile) s_row[threadIdx.x] = 0u;
+  extern __shared__ float4 lds[];
+  // the exact cull walks the scene from LDS (sv.lds_bytes of dynamic LDS): its descent is a chain of dependent
+  // reads, and a shard's k_cull, one block per CU, lasts as long as one thread's chain.  With CullStack's 32.5 KB
+  // of static LDS a block holds up to ~81 KB (a scene at kLdsSceneBytes), within gfx950's 160 KB per CU but one
+  // block per CU there; tests/test_gpu_cull_entry.py renders such a scene (test_scene_at_the_lds_limit)
+  [[maybe_unused]] const Staged sc = stage_scene<kEntry>(sv, lds);
   __syncthreads();
   {
     const uint32_t qx = threadIdx.x & 15u, qy = threadIdx.x >> 4;
     int x = 0, y = 0;
     (void)local_pixel(f, t0 + 2u * qy * kTile + 2u * qx, x, y);  // the quad's corner (in or out of the image)
-    if (x < f.W && y < f.H && pixel_frustum_misses(sv, f, x, y, 2)) {
+    bool miss;
+    if constexpr (kEntry) {
+      __shared__ CullStack s_cs;
+      const uint32_t e = (x < f.W && y < f.H) ? cull_entry(sc, sv, f, x, y, 2, s_cs) : kNoHit;  // (a quad outside the image: no pixel reads it)
+      entry[blockIdx.x * kBlock + threadIdx.x] = e;
+      miss = x < f.W && y < f.H && e == kNoHit;
+    } else {
+      miss = x < f.W && y < f.H && pixel_frustum_misses(sv, f, x, y, 2);
+    }
+    if (miss) {
       atomicOr(&s_row[2u * qy], 3u << (2u * qx));
       atomicOr(&s_row[2u * qy + 1u], 3u << (2u * qx));
     }
@@ -1277,6 +1481,16 @@ __device__ __forceinline__ unsigned long long primary_traced(const FrameView& f)
 }
 __device__ __forceinline__ bool pixel_culled(const FrameView& f, uint32_t l) {
   return f.cull != nullptr && ((f.cull[l >> 5] >> (l & 31u)) & 1u) != 0u;
+}
+// Where the camera rays of valid local pixel l start their walk (traverse_w_from); kNoHit: nowhere, the
+// pixel is culled.  kEntries (LDS-staged BVH2 kernels): the quad's entry word when the call has entries
+// (f.entry; null with SPTR_FRAME_NO_CULL and for every other scene), else the scene's root.
+template <bool kLds, bool kW4>
+__device__ __forceinline__ uint32_t primary_root(const SceneView& sv, const FrameView& f, uint32_t l) {
+  if constexpr (kLds && !kW4) {
+    if (f.entry != nullptr) return f.entry[entry_index(l)];
+  }
+  return pixel_culled(f, l) ? kNoHit : (kW4 ? 0u : sv.root);  // (the wide walk starts at its own root: traverse_w_from)
 }
 
 // --------------------------------------------------------------------------------- shading math
@@ -1474,7 +1688,7 @@ __global__ void __launch_bounds__(kBlock, kW4 ? SPTR_TRACE4_WAVES : SPTR_TRACE_P
     int x = 0, y = 0;
     const bool valid = l < f.P && local_pixel(f, l, x, y);
     const uint32_t ps = valid ? (uint32_t)(y * f.W + x) : 0u;
-    const bool culled = valid && pixel_culled(f, l);
+    const uint32_t root = valid ? primary_root<true, kW4>(sv, f, l) : kNoHit;  // read once per pixel; kNoHit: culled
     vec3 a = v3(0.0f, 0.0f, 0.0f);
     if (valid && !f.reset) a = xyz(f.accum[l]);
     bool fold = true;
@@ -1489,10 +1703,10 @@ __global__ void __launch_bounds__(kBlock, kW4 ? SPTR_TRACE4_WAVES : SPTR_TRACE_P
         primary_at(f, idiv, x, y, ps, f.acc0 + smp, pr);
         // SPTR_ABLATE (timing experiments only, wrong images): 2 = primary rays skip traversal,
         // 1 = constant environment, 4 = primary misses add no radiance
-        if (!(ablate(f) & 2u) && !culled) {
+        if (!(ablate(f) & 2u) && root != kNoHit) {
           const Ray r = make_ray(f.cam_pos, pr.d);
           const uint32_t v0 = vc.nodes;
-          hit = traverse_w<kW4, false, kCount>(sc, sv, r, 0.0f, tfar, ref, vc, s_stack);
+          hit = traverse_w_from<kW4, kCount>(sc, sv, root, r, tfar, ref, vc, s_stack);
           if (kCount) hist_ray(s_hist, vc.nodes - v0);
         }
         if (!hit) {
@@ -1541,7 +1755,12 @@ __global__ void __launch_bounds__(kBlock, kW4 ? SPTR_TRACE4_WAVES : SPTR_TRACE_P
 constexpr uint32_t kFoldLanes = 8;  // samples per pixel per round = lanes per pixel group
 // kHiOcc: 8 waves/SIMD for shards whose pixels fill the resident waves only a few times (r04u: the
 // 8-way C2 shard 0.554 -> 0.541 ms, while 2- and 4-way shards lose ~1.5 % at 8 waves)
-template <bool kLds, bool kCount, bool kW4, bool kCube, bool kHiOcc = false, bool kTimed = false>
+// kEntries (false only with kHiOcc): the call may have walk entry words (FrameView::entry).  The 64-register
+// kHiOcc form has no room to hold a pixel's word across its sample loop and reads it again every round; a call
+// without entries (the box cull, SPTR_FRAME_NO_CULL) would pay those reads for nothing (the 4-way C2 shard
+// 0.694-0.698 -> 0.719-0.722 ms with them), so it runs the instantiation without, which is the kernel as it
+// was before the entries: the mask bit once per pixel, walks from the scene's root.
+template <bool kLds, bool kCount, bool kW4, bool kCube, bool kHiOcc = false, bool kTimed = false, bool kEntries = true>
 __global__ void __launch_bounds__(kBlock, kW4 ? SPTR_TRACE4_WAVES : (kHiOcc ? 8 : SPTR_TRACE_WP_WAVES))
     k_trace_wp(SceneView sv, EnvView sh, FrameView fin, WaveView w) {
   if constexpr (kTimed) ktime_begin(w);
@@ -1577,7 +1796,9 @@ __global__ void __launch_bounds__(kBlock, kW4 ? SPTR_TRACE4_WAVES : (kHiOcc ? 8 
     int x = 0, y = 0;
     const bool valid = l < f.P && local_pixel(f, l, x, y);
     const uint32_t ps = valid ? (uint32_t)(y * f.W + x) : 0u;
-    const bool culled = valid && pixel_culled(f, l);
+    static_assert(kEntries || kHiOcc, "only the high-occupancy form has an instantiation without entries");
+    // read once per pixel; kNoHit: culled.  (kHiOcc with entries, 64 registers: once per round, see below)
+    uint32_t root = valid ? primary_root<kLds && kEntries, kW4>(sv, f, l) : kNoHit;
     vec3 a = v3(0.0f, 0.0f, 0.0f);
     if (valid && !f.reset) a = xyz(f.accum[l]);
     bool fold = true;
@@ -1593,10 +1814,18 @@ __global__ void __launch_bounds__(kBlock, kW4 ? SPTR_TRACE4_WAVES : (kHiOcc ? 8 
       if (act) {
         Primary pr;
         primary_at(f, idiv, x, y, ps, f.acc0 + smp, pr);
-        if (!culled) {
+        if constexpr (kHiOcc && kEntries) {
+          // the word is read again each round instead of staying live across the loop: held, it cost this
+          // 64-register form six more spilled registers (10 against the parent's 4; 4 with the re-read)
+          uint32_t lv = l;
+          asm volatile("" : "+v"(lv));
+          root = primary_root<kLds, kW4>(sv, f, lv);
+        }
+        if (root != kNoHit) {
           const Ray r = make_ray(f.cam_pos, pr.d);
           const uint32_t v0 = vc.nodes;
-          hit = traverse_w<kW4, false, kCount>(sc, sv, r, 0.0f, tfar, ref, vc, s_stack);
+          if constexpr (kEntries) hit = traverse_w_from<kW4, kCount>(sc, sv, root, r, tfar, ref, vc, s_stack);
+          else hit = traverse_w<kW4, false, kCount>(sc, sv, r, 0.0f, tfar, ref, vc, s_stack);
           if (kCount) hist_ray(s_hist, vc.nodes - v0);
         }
         if (!hit && sh.debug_mode != 1) rv = v3(0.0f, 0.0f, 0.0f) + v3(1.0f, 1.0f, 1.0f) * env_color<kCube>(sh, renormalized_again(pr.d));
@@ -1689,6 +1918,7 @@ __global__ void __launch_bounds__(kBlock, (kW4 && !kPrimary) ? SPTR_TRACE4_WAVES
     const uint32_t i = base + threadIdx.x;
     bool active = i < n, hit = false, culled = false;
     uint32_t id = 0u, pid = 0u, ref = kNoHit;
+    [[maybe_unused]] uint32_t root = kNoHit;  // bounce 0 of LDS-staged BVH2 scenes
     float tfar = __builtin_huge_valf();
     vec3 o, d;
     if (active) {
@@ -1698,7 +1928,12 @@ __global__ void __launch_bounds__(kBlock, (kW4 && !kPrimary) ? SPTR_TRACE4_WAVES
         if (f.plist) p = primary_item(f, nlist, i);
         id = pid = p;
         active = primary_path(f, idiv, p, pr, l);
-        culled = !f.plist && pixel_culled(f, l);
+        if constexpr (kLds && !kW4) {
+          root = active ? primary_root<kLds, kW4>(sv, f, l) : kNoHit;  // the pixel's walk root (kNoHit: culled)
+          culled = root == kNoHit;
+        } else {
+          culled = !f.plist && pixel_culled(f, l);
+        }
         o = f.cam_pos;
         d = pr.d;
       } else {
@@ -1715,7 +1950,8 @@ __global__ void __launch_bounds__(kBlock, (kW4 && !kPrimary) ? SPTR_TRACE4_WAVES
       // 1 = constant environment, 4 = primary misses write no radiance
       if (!(kPrimary && ((ablate(f) & 2u) || culled))) {
         const uint32_t v0 = vc.nodes;
-        hit = traverse_w<kW4, false, kCount>(sc, sv, r, 0.0f, tfar, ref, vc, s_stack);
+        if constexpr (kPrimary && kLds && !kW4) hit = traverse_w_from<kW4, kCount>(sc, sv, root, r, tfar, ref, vc, s_stack);
+        else hit = traverse_w<kW4, false, kCount>(sc, sv, r, 0.0f, tfar, ref, vc, s_stack);
         if (kCount) hist_ray(s_hist, vc.nodes - v0);
       }
       if (kPrimary && !hit && (ablate(f) & 4u)) {
@@ -4219,22 +4455,23 @@ unsigned launch_trace(const SceneView& sv, const ShadeView& sh, const FrameView&
     const bool hi = L && !W && (uint64_t)f.P < (uint64_t)g7 * (kBlock / 64u) * 8u * kWpHiOccRounds;
     return dispatch(
         [&](auto fl) -> unsigned {
-          return [&]<bool Lc, bool C, bool Wc, bool Cube, bool Hi>(Flags<Lc, C, Wc, Cube, Hi>) {
+          return [&]<bool Lc, bool C, bool Wc, bool Cube, bool Hi, bool Ent>(Flags<Lc, C, Wc, Cube, Hi, Ent>) {
             if constexpr (Hi && (Wc || !Lc)) {
               return 0u;  // not instantiated: the high-occupancy form is for LDS-staged BVH2 scenes
             } else {
+              constexpr bool E = Ent || !Hi;  // (the other forms test f.entry themselves)
               if (w.tslot) {
-                const unsigned g = resident_grid((const void*)&k_trace_wp<Lc, C, Wc, Cube, Hi, true>, lb);
-                SPTR_TIMED_LAUNCH((k_trace_wp<Lc, C, Wc, Cube, Hi, true>), dim3(g), b, lb, s, sv, ev, f, w);
+                const unsigned g = resident_grid((const void*)&k_trace_wp<Lc, C, Wc, Cube, Hi, true, E>, lb);
+                SPTR_TIMED_LAUNCH((k_trace_wp<Lc, C, Wc, Cube, Hi, true, E>), dim3(g), b, lb, s, sv, ev, f, w);
                 return g;
               }
-              const unsigned g = resident_grid((const void*)&k_trace_wp<Lc, C, Wc, Cube, Hi>, lb);
-              SPTR_TIMED_LAUNCH((k_trace_wp<Lc, C, Wc, Cube, Hi>), dim3(g), b, lb, s, sv, ev, f, w);
+              const unsigned g = resident_grid((const void*)&k_trace_wp<Lc, C, Wc, Cube, Hi, false, E>, lb);
+              SPTR_TIMED_LAUNCH((k_trace_wp<Lc, C, Wc, Cube, Hi, false, E>), dim3(g), b, lb, s, sv, ev, f, w);
               return g;
             }
           }(fl);
         },
-        Flags<>{}, L, count, W, cube, hi);
+        Flags<>{}, L, count, W, cube, hi, f.entry != nullptr);
   }
   if (P && L && f.pixel_major == kFoldThread) {
     return dispatch(
@@ -4301,11 +4538,16 @@ unsigned launch_shade(const SceneView& sv, const ShadeView& sh, const FrameView&
       Flags<>{}, depth == 0, fuse);
 }
 
-uint32_t cull_depth_for(uint32_t spp) { return spp >= 16u ? (uint32_t)kCullDepthMax : 4u; }
+bool cull_entries_apply(const SceneView& sv) { return sv.lds_bytes != 0u && sv.width == 2u; }
+uint32_t cull_depth_for(uint32_t spp, bool exact) {
+  if (exact) return (uint32_t)kCullEntryDepth;  // the exact cull descends to the leaves
+  return spp >= 16u ? (uint32_t)kCullDepthMax : 4u;
+}
 
-void launch_cull(const SceneView& sv, const FrameView& f, uint32_t* mask, uint32_t* plist, hipStream_t s) {
+void launch_cull(const SceneView& sv, const FrameView& f, uint32_t* mask, uint32_t* plist, uint32_t* entry, hipStream_t s) {
   if (f.P == 0u) return;
-  hipLaunchKernelGGL(k_cull, dim3(f.P / kTilePixels), dim3(kBlock), 0, s, sv, f, mask, plist);
+  if (entry) hipLaunchKernelGGL(k_cull<true>, dim3(f.P / kTilePixels), dim3(kBlock), sv.lds_bytes, s, sv, f, mask, plist, entry);
+  else hipLaunchKernelGGL(k_cull<false>, dim3(f.P / kTilePixels), dim3(kBlock), 0, s, sv, f, mask, plist, entry);
 }
 
 unsigned launch_bounce(const SceneView& sv, const ShadeView& sh, const FrameView& f, const WaveView& w_in, int depth,

@@ -366,6 +366,7 @@ FrameView frame_view(const Context& c, const sptr_frame& f) {
   v.sky_fold = 0u;
   v.plist = nullptr;
   v.unculled = nullptr;
+  v.entry = nullptr;
   v.integrator = f.integrator;
   v.spf = f.samples_per_frame ? f.samples_per_frame : 4u;
   return v;
@@ -703,6 +704,7 @@ int ensure_pixels(Context& c, int W, int H, int G, int R, hipStream_t s, bool& r
   API_HIP(c.image.ensure((size_t)W * H * 3));
   API_HIP(c.cull.ensure((size_t)c.P / 32u * 4u + 4u));
   API_HIP(c.plist.ensure(((size_t)c.P + 2u) * 4u));
+  API_HIP(c.entry.ensure((size_t)c.P / 4u * 4u + 4u));
   ++c.epoch;
   API_HIP(hipMemsetAsync(c.accum.p, 0, (size_t)c.P * 16, s));
   API_HIP(hipMemsetAsync(c.tiles.p, 0, (size_t)c.P * 4, s));
@@ -806,6 +808,22 @@ bool overlap_enabled(const Context& c) {
 // overflows the host stack (the r03 libamdhip64+0x2d34a8 crash of the two-lane calls;
 // tools/micro/capture_events.hip reproduces it with three streams).  run_call checks every captured
 // graph (check_graph) before instantiating it.
+// Whether this call's cull is the exact one (k_cull<true>: LDS-staged BVH2 scenes), which also fills the entry
+// words.  A cached mask is paid once per camera, so it always is.  A call that recomputes its mask in its own
+// sequence (SPTR_FRAME_RECULL) pays the cull every time, at the head of its launch chain, and the exact cull
+// costs about three times the box cull (C2: 39 against 16 us; on a shard of one block per CU or less 30
+// against 10 us, the time of its longest wave whatever the shard's size), while what it saves in the bounce-0
+// trace grows with the call's samples.  Measured on C2 at 64 spp (profiles/r09_cull_entry_ab.txt): the 8-way
+// shard, one chain of 16.7 M samples, saves 10 us in k_trace_wp and loses 20 in k_cull (0.438-0.442 -> 0.449-0.451
+// ms); the 2-way shard's lanes, 33.4 M samples each, gain (1.262-1.263 -> 1.227-1.234).  Such calls keep the box
+// cull below 2^24 samples, the size from which a call is "large" for the pixel lanes too (lanes_for).
+constexpr uint64_t kExactRecullMinSamples = 1ull << 24;
+bool cull_exact_for(const Context& c, const SceneView& sv, const sptr_frame& f) {
+  if (!cull_entries_apply(sv)) return false;
+  if (f.flags & SPTR_FRAME_RECULL) return (uint64_t)c.P * f.spp >= kExactRecullMinSamples;
+  return true;
+}
+
 uint32_t enqueue_wavefront(Context& c, const sptr_frame& f, uint32_t k, int T, hipStream_t s, StageTimer& tm) {
   const SceneView sv = scene_view(c);
   const ShadeView sh = shade_view(c);
@@ -826,14 +844,17 @@ uint32_t enqueue_wavefront(Context& c, const sptr_frame& f, uint32_t k, int T, h
   // current by refresh_cull ahead of this launch sequence, or, with SPTR_FRAME_RECULL, computed as the
   // sequence's first launch (inside a captured graph, whose key includes the camera and the flag)
   if (!(f.flags & SPTR_FRAME_NO_CULL)) {
-    fv.cull_depth = cull_depth_for(f.spp);
+    const bool exact = cull_exact_for(c, sv, f);
+    fv.cull_depth = cull_depth_for(f.spp, exact);
     fv.cull = static_cast<const uint32_t*>(c.cull.p);
     fv.unculled = static_cast<const uint32_t*>(c.plist.p) + c.P;
+    if (exact) fv.entry = static_cast<const uint32_t*>(c.entry.p);  // computed with the mask
   }
   tm.begin_call();
   if (fv.cull && (f.flags & SPTR_FRAME_RECULL)) {  // the count at plist[P] was zeroed by k_frame_dyn
     tm.begin(8);
-    launch_cull(sv, fv, static_cast<uint32_t*>(c.cull.p), static_cast<uint32_t*>(c.plist.p), s);
+    launch_cull(sv, fv, static_cast<uint32_t*>(c.cull.p), static_cast<uint32_t*>(c.plist.p),
+                fv.entry ? static_cast<uint32_t*>(c.entry.p) : nullptr, s);
     tm.end();
   }
   uint32_t done = 0, waves = 0;
@@ -1049,12 +1070,14 @@ uint32_t enqueue_wavefront(Context& c, const sptr_frame& f, uint32_t k, int T, h
 // from the cached mask's, and on SPTR_FRAME_RECULL).
 int refresh_cull(Context& c, const sptr_frame& f, hipStream_t s, bool timing) {
   if (f.flags & SPTR_FRAME_NO_CULL) return SPTR_OK;
-  const uint32_t depth = cull_depth_for(f.spp);
+  const SceneView sv = scene_view(c);
+  const bool exact = cull_exact_for(c, sv, f);
+  const uint32_t depth = cull_depth_for(f.spp, exact);
   if (f.flags & SPTR_FRAME_RECULL) {  // the call's own launch sequence computes the mask (enqueue_wavefront)
     c.cull_epoch = 0;  // the cached key is set once that sequence is enqueued (sptr_render)
     return SPTR_OK;
   }
-  if (!(f.flags & SPTR_FRAME_RECULL) && c.cull_epoch == c.epoch && c.cull_depth == depth &&
+  if (!(f.flags & SPTR_FRAME_RECULL) && c.cull_epoch == c.epoch && c.cull_depth == depth && c.cull_exact == exact &&
       std::memcmp(&c.cull_cam, &f.camera, sizeof(sptr_camera)) == 0)
     return SPTR_OK;
   FrameView fv = frame_view(c, f);
@@ -1062,13 +1085,15 @@ int refresh_cull(Context& c, const sptr_frame& f, hipStream_t s, bool timing) {
   StageTimer tm{c, timing, true, s};
   tm.begin(8);
   API_HIP(hipMemsetAsync(static_cast<uint32_t*>(c.plist.p) + c.P, 0, 8, s));
-  launch_cull(scene_view(c), fv, static_cast<uint32_t*>(c.cull.p), static_cast<uint32_t*>(c.plist.p), s);
+  launch_cull(sv, fv, static_cast<uint32_t*>(c.cull.p), static_cast<uint32_t*>(c.plist.p),
+              exact ? static_cast<uint32_t*>(c.entry.p) : nullptr, s);
   tm.end();
   API_HIP(hipGetLastError());
   if (tm.err != hipSuccess) return fail(c, SPTR_ERR_HIP, std::string("render: cull events: ") + hipGetErrorString(tm.err));
   c.cull_epoch = c.epoch;
   c.cull_cam = f.camera;
   c.cull_depth = depth;
+  c.cull_exact = exact;
   ++c.pending_culls;
   return SPTR_OK;
 }
@@ -1773,7 +1798,8 @@ static int render_one(sptr_ctx* x, const sptr_frame* f, void* stream, sptr_stats
     if (clear) {  // the sequence just enqueued computes this camera's mask (keyed only once enqueued)
       c.cull_epoch = c.epoch;
       c.cull_cam = f->camera;
-      c.cull_depth = cull_depth_for(f->spp);
+      c.cull_exact = cull_exact_for(c, scene_view(c), *f);
+      c.cull_depth = cull_depth_for(f->spp, c.cull_exact);
       ++c.pending_culls;
     }
     samples = (uint64_t)frame_view(c, *f).valid * f->spp;

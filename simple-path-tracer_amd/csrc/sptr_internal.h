@@ -169,6 +169,9 @@ struct FrameView {
   uint32_t cull_depth;   // BVH2 levels k_cull tests (<= kCullDepthMax)
   const uint32_t* plist; // with sky_fold: the unculled local pixels (count at plist[P]), bounce 0's paths
   const uint32_t* unculled;  // with cull: the number of unculled valid local pixels (k_cull's plist[P])
+  // with cull, LDS-staged BVH2 scenes: per 2x2 pixel quad (tile, quad row, quad column) where the quad's
+  // camera rays start their walk: kNoHit (culled), a node index or a leaf link (k_cull<true>); else null
+  const uint32_t* entry;
 };
 // FrameView::dyn words: {frame_begin, reset, total} of the call (k_frame_dyn).
 constexpr size_t kDynBytes = 2048;
@@ -523,10 +526,12 @@ struct Context {
   DevBuf accum, tiles, image;
   DevBuf cull;   // bounce-0 pixel-frustum cull mask, 1 bit per local pixel (k_cull)
   DevBuf plist;  // the local pixels k_cull did not cull, each tile's run in pixel order; their count at [P]
+  DevBuf entry;  // the exact cull's walk entry word per 2x2 pixel quad (FrameView::entry), computed with the mask
   // what the mask was computed for (state epoch, camera): k_cull reruns only when these change
   uint64_t cull_epoch = 0;
   sptr_camera cull_cam{};
   uint32_t cull_depth = 0;  // depth the cached mask was computed with
+  bool cull_exact = false;  // ... and by the exact cull, which filled `entry` too (else the box cull: `entry` is stale)
   uint32_t last_samples = 0;  // accumulation count after the last render
   // sptr_set_seed_offset: a wavefront call seeds its frames as if its accumulation index were frame_begin +
   // seed_offset (the k_frame_dyn word the seeds read; reset and total follow frame_begin alone)
@@ -609,9 +614,12 @@ uint32_t bounce0_pixel_major(const SceneView& sv, const FrameView& f);
 // resolve: also tone-map the sums into tiles (+ image) in the same launch (the call's last batch)
 void launch_accumulate(const FrameView& f, const WaveView& w, float4* accum, uint32_t* tiles, uint8_t* image,
                        bool resolve, hipStream_t s);
-// BVH2 levels the bounce-0 pixel cull tests for a call of spp samples per pixel
-uint32_t cull_depth_for(uint32_t spp);
-void launch_cull(const SceneView& sv, const FrameView& f, uint32_t* mask, uint32_t* plist, hipStream_t s);
+// BVH2 levels the bounce-0 pixel cull tests for a call of spp samples per pixel of this scene
+uint32_t cull_depth_for(uint32_t spp, bool exact);
+// the scene's cull is the exact one, which also writes walk entry words (LDS-staged BVH2 scenes)
+bool cull_entries_apply(const SceneView& sv);
+// entry: the quads' entry words (the exact cull), or null (the box cull down to f.cull_depth)
+void launch_cull(const SceneView& sv, const FrameView& f, uint32_t* mask, uint32_t* plist, uint32_t* entry, hipStream_t s);
 // capped: at most 4 waves per SIMD (beside the launch chain); else full occupancy
 void launch_sky(const ShadeView& sh, const FrameView& f, bool capped, hipStream_t s);
 // dst local tile i <- a's tile i / 2 (i even) or b's tile i / 2 (i odd): two pixel lanes' tiles in the
