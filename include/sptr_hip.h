@@ -242,6 +242,17 @@ int sptr_set_tail_depth(sptr_ctx* ctx, uint32_t depth);
  * keep their launch sequence whatever the setting).  The image and the counters do not
  * depend on it. */
 int sptr_set_bounce_chain(sptr_ctx* ctx, uint32_t mode);
+/* Sky split (symbols added within ABI 9: no existing struct or entry point changed): in a lane-group bounce 0
+ * of an LDS-staged scene with a cull mask, the bulk of the culled pixels, whose camera rays all miss, is summed
+ * one thread per pixel by a launch of its own, every thread the same number of pixels, and the lane groups
+ * take the unculled pixels and the culled remainder.  mode 0 = automatic (the default): on for batches with at
+ * least 5/4 pixels per bulk thread (the pixel lanes of a 1080p frame and of its 2-way shard); 1 = off; 2 = on
+ * wherever that bounce 0 runs.  bulk_threads: 0 = automatic (three quarters of the launch's resident threads);
+ * any other value is for tests.  The image and the
+ * counters do not depend on either.  sptr_sky_split_info: the bulk thread count of the last wavefront call's
+ * first batch, 0 if it did not split. */
+int sptr_set_sky_split(sptr_ctx* ctx, uint32_t mode, uint32_t bulk_threads);
+int sptr_sky_split_info(sptr_ctx* ctx, uint32_t* bulk_threads);
 /* Maximum primitives per BVH leaf range (1..16; 0 = automatic, the default: 8 for scenes staged in
  * LDS, 1 otherwise); applies to the next sptr_upload_scene. */
 int sptr_set_leaf_size(sptr_ctx* ctx, uint32_t max_prims);

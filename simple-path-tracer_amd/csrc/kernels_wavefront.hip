@@ -24,6 +24,7 @@
 #include <mutex>
 
 #include "cull_prims.h"
+#include "sky_split.h"
 #include "sptr_internal.h"
 
 // Occupancy hints (min waves per SIMD); 1 = let the register allocator decide.
@@ -1365,18 +1366,20 @@ __device__ __forceinline__ uint32_t entry_index(uint32_t l) {
   return ((l >> 10) << 8) | ((w >> 6) << 4) | ((w & 31u) >> 1);
 }
 // bit l of mask: pixel l is culled (see above).  plist: the valid pixels that are not culled, from
-// plist[0] (count at plist[P], zeroed before).  One block per local tile: thread (qx, qy) tests the 2x2
+// plist[0] (count at plist[P], zeroed before), and with list_culled the valid pixels that are culled, from
+// plist[P - 1] down (count at plist[P + 1], zeroed before; sky_split.h).  One block per local tile: thread (qx, qy) tests the 2x2
 // pixel quad at (2qx, 2qy) of the tile and sets the quad's bits in the tile's 32 LDS row words; then
 // each thread lists the pixels of 4 consecutive local indices, the tile's run at a range one atomic per
 // tile reserves.  (r02: a pyramid per pixel and one atomic per wave, C2 108 us; per pixel and per tile
 // 65-75 us.)
 // kEntry: the exact cull (cull_entry); the quad's entry word goes to entry[tile * 256 + thread].
 template <bool kEntry>
-__global__ void __launch_bounds__(kBlock) k_cull(SceneView sv, FrameView f, uint32_t* mask, uint32_t* plist, uint32_t* entry) {
+__global__ void __launch_bounds__(kBlock) k_cull(SceneView sv, FrameView f, uint32_t* mask, uint32_t* plist, uint32_t* entry,
+                                                 uint32_t list_culled) {
   static_assert(kTile == 32 && kBlock == 256, "16 x 16 quads per 32 x 32 tile");
   __shared__ uint32_t s_row[kTile];
   __shared__ uint32_t s_cnt[kBlock / 64u];
-  __shared__ uint32_t s_base;
+  __shared__ uint32_t s_base, s_base_c;
   const uint32_t t0 = blockIdx.x * kTilePixels;  // the tile's first local pixel
   if (threadIdx.x < (uint32_t)kTile) s_row[threadIdx.x] = 0u;
   extern __shared__ float4 lds[];
@@ -1429,9 +1432,15 @@ __global__ void __launch_bounds__(kBlock) k_cull(SceneView sv, FrameView f, uint
   uint32_t w = mbits << col;
   for (int off = 1; off < 8; off <<= 1) w |= __shfl_xor(w, off);
   if ((threadIdx.x & 7u) == 0u) mask[(t0 >> 5) + row] = w;
-  // list the kept pixels: per-thread counts, wave scans, block offsets, one atomic per tile
-  const uint32_t n = (uint32_t)__popc(keep), lane = lane_id();
-  uint32_t incl = n;
+  // list the kept pixels, and from the buffer's back the culled valid ones (sky_split.h): per-thread counts
+  // (kept in the low half, culled in the high half: a tile has at most 1024 of either), wave scans, block
+  // offsets, one atomic per tile and list
+  // (list_culled: only a call whose bounce 0 splits needs the second list; nearly every tile has culled pixels, and
+  // their reservations on one word cost a 4K frame's k_cull 57 -> 334 us)
+  const uint32_t cbits = list_culled ? mbits : 0u;
+  const uint32_t n = (uint32_t)__popc(keep), nc = (uint32_t)__popc(cbits), lane = lane_id();
+  const uint32_t both = n | (nc << 16);
+  uint32_t incl = both;
   for (int off = 1; off < 64; off <<= 1) {
     const uint32_t v = __shfl_up(incl, off);
     if (lane >= (uint32_t)off) incl += v;
@@ -1445,13 +1454,19 @@ __global__ void __launch_bounds__(kBlock) k_cull(SceneView sv, FrameView f, uint
       s_cnt[i] = run;
       run += c;
     }
-    s_base = run ? atomicAdd(&plist[f.P], run) : 0u;
+    const uint32_t run_u = run & 0xFFFFu, run_c = run >> 16;
+    s_base = run_u ? atomicAdd(&plist[f.P], run_u) : 0u;
+    s_base_c = run_c ? atomicAdd(&plist[f.P + 1u], run_c) : 0u;
   }
   __syncthreads();
-  uint32_t o = s_base + s_cnt[threadIdx.x >> 6] + incl - n;
+  const uint32_t excl = s_cnt[threadIdx.x >> 6] + incl - both;
+  uint32_t o = s_base + (excl & 0xFFFFu);
+  uint32_t oc = s_base_c + (excl >> 16);
 #pragma unroll
-  for (uint32_t j = 0; j < 4u; ++j)
+  for (uint32_t j = 0; j < 4u; ++j) {
     if ((keep >> j) & 1u) plist[o++] = t0 + 4u * threadIdx.x + j;
+    if ((cbits >> j) & 1u) plist[sky_split_culled_word(f.P, oc++)] = t0 + 4u * threadIdx.x + j;
+  }
 }
 // Path-major bounce 0 over the unculled pixel list (f.plist: nlist pixels x k samples): compacted
 // item i -> path p.  Items run in groups of kPrimaryGroup listed pixels — neighbours, since k_cull lists
@@ -1760,9 +1775,15 @@ constexpr uint32_t kFoldLanes = 8;  // samples per pixel per round = lanes per p
 // without entries (the box cull, SPTR_FRAME_NO_CULL) would pay those reads for nothing (the 4-way C2 shard
 // 0.694-0.698 -> 0.719-0.722 ms with them), so it runs the instantiation without, which is the kernel as it
 // was before the entries: the mask bit once per pixel, walks from the scene's root.
-template <bool kLds, bool kCount, bool kW4, bool kCube, bool kHiOcc = false, bool kTimed = false, bool kEntries = true>
+// kList (f.split_threads: the culled bulk split off, sky_split.h): the blocks walk the item list, the unculled
+// pixels and then the culled pixels k_sky's list mode leaves over, in place of the local pixels 0 .. P - 1.  A chunk
+// of 32 items is a run of one tile's pixels, so a block's hit records stay tile-coherent.  Pixels in no item (the
+// bulk's, and tile slots outside the image) are k_sky's to write.
+template <bool kLds, bool kCount, bool kW4, bool kCube, bool kHiOcc = false, bool kTimed = false, bool kEntries = true,
+          bool kList = false>
 __global__ void __launch_bounds__(kBlock, kW4 ? SPTR_TRACE4_WAVES : (kHiOcc ? 8 : SPTR_TRACE_WP_WAVES))
     k_trace_wp(SceneView sv, EnvView sh, FrameView fin, WaveView w) {
+  static_assert(!kList || (kLds && !kHiOcc && kEntries), "the item list: LDS-staged scenes at the 7-wave occupancy");
   if constexpr (kTimed) ktime_begin(w);
   const FrameView f = frame_dyn(fin);
   __shared__ KernelStack<kLds> s_stack;
@@ -1789,10 +1810,15 @@ __global__ void __launch_bounds__(kBlock, kW4 ? SPTR_TRACE4_WAVES : (kHiOcc ? 8 
   const uint32_t per = cap * f.k;                          // hit-record segment stride
   const uint32_t seg0 = lb * per;
   const uint32_t rounds = (f.k + kFoldLanes - 1u) / kFoldLanes;
+  static_assert(kPix == kSkySplitChunk, "sky_split.h deals the items in this kernel's chunks");
+  // the item list's counts are read on the device (a replayed graph's cull may have changed them)
+  const SkySplit ss = kList ? sky_split(f.plist[f.P], f.plist[f.P + 1u], f.split_threads) : SkySplit{};
+  const uint32_t work = kList ? ss.items : f.P;  // (items <= P: a block takes at most cap of them, as of the pixels)
   for (uint32_t it = 0;; ++it) {
     const uint32_t base = lb * kPix + it * step;
-    if (base >= f.P) break;
-    const uint32_t l = base + threadIdx.x / kFoldLanes;
+    if (base >= work) break;
+    uint32_t l = base + threadIdx.x / kFoldLanes;
+    if constexpr (kList) l = l < ss.items ? f.plist[sky_split_item_word(ss, f.P, l)] : f.P;  // (f.P: no pixel)
     int x = 0, y = 0;
     const bool valid = l < f.P && local_pixel(f, l, x, y);
     const uint32_t ps = valid ? (uint32_t)(y * f.W + x) : 0u;
@@ -3595,40 +3621,61 @@ __device__ __forceinline__ bool sky_pixel(const FrameView& f, uint32_t l, int& x
 #ifndef SPTR_SKY_VGPR
 #define SPTR_SKY_VGPR 127
 #endif
-template <bool kCube, bool kCapped>
+// kList (f.split_threads = T: the culled bulk of a lane-group bounce 0, sky_split.h): thread t < T sums the m
+// pixels of culled ranks t, t + T, ... from k_cull's culled list, every thread the same number, and writes them
+// as k_trace_wp would: the sum and resume slot k.  The counts are read on the device.  The tile slots outside the
+// image, which are in neither list, get k_trace_wp's value too (zero, resume slot k).
+template <bool kCube, bool kCapped, bool kList = false>
 __global__ void __launch_bounds__(kBlock) k_sky(EnvView sh, FrameView fin) {
 #if SPTR_SKY_VGPR
   if constexpr (kCapped) asm volatile("; k_sky occupancy cap" ::: "v" SPTR_STR(SPTR_SKY_VGPR));
 #endif
   const FrameView f = frame_dyn(fin);
   const ImageDiv idiv = image_div(f);
-  for (uint32_t l = blockIdx.x * blockDim.x + threadIdx.x; l < f.P; l += grid_threads()) {
-    int x, y;
-    // only the culled pixels' words: k_accum sums the others (sky_pixel)
-    if (sky_pixel(f, l, x, y)) {
-      vec3 a = v3(0.0f, 0.0f, 0.0f);
-      if (!f.reset) a = xyz(f.accum[l]);
-      const uint32_t ps = (uint32_t)(y * f.W + x);
-      auto sample = [&](uint32_t smp) {
-        Primary pr;
-        primary_at(f, idiv, x, y, ps, f.acc0 + smp, pr);
-        vec3 rv = v3(0.0f, 0.0f, 0.0f);
-        if (sh.debug_mode != 1) rv = v3(0.0f, 0.0f, 0.0f) + v3(1.0f, 1.0f, 1.0f) * env_color<kCube>(sh, renormalized_again(pr.d));
-        return rv;
-      };
-      // kSkyIlp independent samples (their environment fetches in flight together), then their adds
-      // in sample order
-      constexpr uint32_t kSkyIlp = SPTR_SKY_ILP;
-      uint32_t smp = 0;
-      for (; smp + kSkyIlp <= f.k; smp += kSkyIlp) {
-        vec3 rv[kSkyIlp];
+  // the k samples of local pixel l at (x, y), summed in sample order onto the previous batches' sum
+  auto sum_pixel = [&](uint32_t l, int x, int y) {
+    vec3 a = v3(0.0f, 0.0f, 0.0f);
+    if (!f.reset) a = xyz(f.accum[l]);
+    const uint32_t ps = (uint32_t)(y * f.W + x);
+    auto sample = [&](uint32_t smp) {
+      Primary pr;
+      primary_at(f, idiv, x, y, ps, f.acc0 + smp, pr);
+      vec3 rv = v3(0.0f, 0.0f, 0.0f);
+      if (sh.debug_mode != 1) rv = v3(0.0f, 0.0f, 0.0f) + v3(1.0f, 1.0f, 1.0f) * env_color<kCube>(sh, renormalized_again(pr.d));
+      return rv;
+    };
+    // kSkyIlp independent samples (their environment fetches in flight together), then their adds
+    // in sample order
+    constexpr uint32_t kSkyIlp = SPTR_SKY_ILP;
+    uint32_t smp = 0;
+    for (; smp + kSkyIlp <= f.k; smp += kSkyIlp) {
+      vec3 rv[kSkyIlp];
 #pragma unroll
-        for (uint32_t j = 0; j < kSkyIlp; ++j) rv[j] = sample(smp + j);
+      for (uint32_t j = 0; j < kSkyIlp; ++j) rv[j] = sample(smp + j);
 #pragma unroll
-        for (uint32_t j = 0; j < kSkyIlp; ++j) a = a + rv[j];
-      }
-      for (; smp < f.k; ++smp) a = a + sample(smp);
-      f.accum[l] = make_float4(a.x, a.y, a.z, __uint_as_float(f.k));
+      for (uint32_t j = 0; j < kSkyIlp; ++j) a = a + rv[j];
+    }
+    for (; smp < f.k; ++smp) a = a + sample(smp);
+    f.accum[l] = make_float4(a.x, a.y, a.z, __uint_as_float(f.k));
+  };
+  if constexpr (kList) {
+    const SkySplit ss = sky_split(f.plist[f.P], f.plist[f.P + 1u], f.split_threads);
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    for (uint32_t l = t; l < f.P; l += grid_threads()) {
+      int x, y;
+      if (!local_pixel(f, l, x, y)) f.accum[l] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(f.k));
+    }
+    if (t >= ss.threads) return;
+    for (uint32_t j = 0; j < ss.m; ++j) {
+      const uint32_t l = f.plist[sky_split_culled_word(f.P, sky_split_bulk_rank(ss, t, j))];
+      int x, y;
+      if (l < f.P && local_pixel(f, l, x, y)) sum_pixel(l, x, y);  // (a listed pixel is valid)
+    }
+  } else {
+    for (uint32_t l = blockIdx.x * blockDim.x + threadIdx.x; l < f.P; l += grid_threads()) {
+      int x, y;
+      // only the culled pixels' words: k_accum sums the others (sky_pixel)
+      if (sky_pixel(f, l, x, y)) sum_pixel(l, x, y);
     }
   }
 }
@@ -4449,6 +4496,18 @@ unsigned launch_trace(const SceneView& sv, const ShadeView& sh, const FrameView&
   const bool cube = sh.env.env != nullptr;
   const unsigned lb = trace_lds(sv, L, P, nseg);
   const EnvView ev = sh.env;
+  if (P && L && f.pixel_major == kFoldWave && f.split_threads) {
+    // the item list (sky_split.h) at the 7-wave occupancy: the split is for batches that fill the grid many times
+    return dispatch(
+        [&](auto fl) -> unsigned {
+          return [&]<bool C, bool Wc, bool Cube, bool T>(Flags<C, Wc, Cube, T>) {
+            const unsigned g = resident_grid((const void*)&k_trace_wp<true, C, Wc, Cube, false, T, true, true>, lb);
+            SPTR_TIMED_LAUNCH((k_trace_wp<true, C, Wc, Cube, false, T, true, true>), dim3(g), b, lb, s, sv, ev, f, w);
+            return g;
+          }(fl);
+        },
+        Flags<>{}, count, W, cube, w.tslot != nullptr);
+  }
   if (P && f.pixel_major == kFoldWave) {
     // rounds of 8-pixel wave groups over the resident grid: few rounds (a small shard) -> 8 waves/SIMD
     const unsigned g7 = resident_grid((const void*)&k_trace_wp<true, false, false, false>, lb);
@@ -4544,10 +4603,12 @@ uint32_t cull_depth_for(uint32_t spp, bool exact) {
   return spp >= 16u ? (uint32_t)kCullDepthMax : 4u;
 }
 
-void launch_cull(const SceneView& sv, const FrameView& f, uint32_t* mask, uint32_t* plist, uint32_t* entry, hipStream_t s) {
+void launch_cull(const SceneView& sv, const FrameView& f, uint32_t* mask, uint32_t* plist, uint32_t* entry, bool list_culled,
+                 hipStream_t s) {
   if (f.P == 0u) return;
-  if (entry) hipLaunchKernelGGL(k_cull<true>, dim3(f.P / kTilePixels), dim3(kBlock), sv.lds_bytes, s, sv, f, mask, plist, entry);
-  else hipLaunchKernelGGL(k_cull<false>, dim3(f.P / kTilePixels), dim3(kBlock), 0, s, sv, f, mask, plist, entry);
+  const uint32_t lc = list_culled ? 1u : 0u;
+  if (entry) hipLaunchKernelGGL(k_cull<true>, dim3(f.P / kTilePixels), dim3(kBlock), sv.lds_bytes, s, sv, f, mask, plist, entry, lc);
+  else hipLaunchKernelGGL(k_cull<false>, dim3(f.P / kTilePixels), dim3(kBlock), 0, s, sv, f, mask, plist, entry, lc);
 }
 
 unsigned launch_bounce(const SceneView& sv, const ShadeView& sh, const FrameView& f, const WaveView& w_in, int depth,
@@ -4749,6 +4810,20 @@ void launch_sky(const ShadeView& sh, const FrameView& f, bool capped, hipStream_
   } else {
     if (capped) go(k_sky<false, true>); else go(k_sky<false, false>);
   }
+}
+
+// The culled bulk of a lane-group bounce 0 (k_sky's list mode, sky_split.h): f.split_threads threads, uncapped,
+// in the lane's own chain.
+void launch_sky_list(const ShadeView& sh, const FrameView& f, hipStream_t s) {
+  const unsigned g = std::max(1u, (f.split_threads + kBlock - 1u) / kBlock);
+  if (sh.env.env != nullptr) hipLaunchKernelGGL((k_sky<true, false, true>), dim3(g), dim3(kBlock), 0, s, sh.env, f);
+  else hipLaunchKernelGGL((k_sky<false, false, true>), dim3(g), dim3(kBlock), 0, s, sh.env, f);
+}
+// threads of the list mode's resident grid
+uint32_t sky_list_resident_threads(const ShadeView& sh) {
+  const unsigned g = sh.env.env != nullptr ? resident_grid((const void*)&k_sky<true, false, true>, 0u)
+                                           : resident_grid((const void*)&k_sky<false, false, true>, 0u);
+  return g * kBlock;
 }
 
 __global__ void __launch_bounds__(kBlock) k_interleave_tiles(const uint4* a, uint32_t na, const uint4* b, uint32_t nb,

@@ -188,6 +188,56 @@ bool bounce_chain_on(const Context& c, uint64_t batch_paths) {
   (void)batch_paths;
   return c.bounce_chain == 2u;
 }
+// The culled bulk of a lane-group bounce 0 with a cull mask, summed thread per pixel by k_sky's list mode while
+// k_trace_wp walks the remaining items (sky_split.h; sptr_set_sky_split: 1 never, 2 wherever that bounce 0 runs).
+// Returns the bulk thread count T of the batch, 0 for no split.
+// T: three quarters of the list mode's resident threads.  The launch runs as the batch's last before k_accum (below),
+// beside the other lane's late bounces or alone, so it wants most of the machine's thread slots; a larger T also
+// leaves more culled pixels (up to T - 1) to the lane groups.  Measured on MI355X, C2 (two lanes) and its 2-way
+// shard, ms/step, split off 2.096-2.107 / 1.235: T = 64 K, 128 K, 192 K, 256 K, 384 K, 512 K threads (the resident
+// grid is 512 K) 2.154-2.162, 2.117-2.122, 2.071-2.073, 2.010-2.018, 1.982-1.994, 1.987-1.996 / 1.187, 1.129-1.132,
+// 1.171-1.178, 1.152-1.153, 1.124-1.125, 1.225-1.227 (512 K exceed the shard lane's culled pixels: no bulk).
+// Rule: the culled count is known only on the device, so the batch's pixels stand in for it: on from 5/4 pixels
+// per bulk thread, from where every thread has a pixel if four fifths of the pixels are culled (C2: 88 %).  That
+// takes the lanes of a 1080p frame and of its 2-way shard (1.04 M and 522 K pixels against T = 384 K) and leaves
+// the 4-way shard's (261 K) and everything smaller to the parent's launches.  With fewer culled pixels than T,
+// m = 0: the item list is every valid pixel, the parent's work, and the list launch only marks the tile slots
+// outside the image.  DESIGN.md section 9.3, profiles/r10_sky_split_ab.txt.
+#ifndef SPTR_SKY_SPLIT_TNUM
+#define SPTR_SKY_SPLIT_TNUM 3  // T = resident threads * TNUM / TDIV
+#endif
+#ifndef SPTR_SKY_SPLIT_TDIV
+#define SPTR_SKY_SPLIT_TDIV 4
+#endif
+constexpr uint64_t kSkySplitPixelsNum = 5, kSkySplitPixelsDen = 4;  // pixels per bulk thread from which mode 0 splits
+uint32_t sky_split_threads(const Context& c, const SceneView& sv, const ShadeView& sh, const FrameView& fv) {
+  uint32_t mode = c.sky_split, threads = c.sky_split_threads;
+#ifdef SPTR_EXPERIMENT_KNOBS
+  if (const char* e = getenv("SPTR_SKY_SPLIT"); e && mode == 0u && threads == 0u) {  // "mode[,threads]" (A/B)
+    mode = (uint32_t)atoi(e);
+    if (const char* t = strchr(e, ',')) threads = (uint32_t)atoi(t + 1);
+  }
+#endif
+  if (mode == 1u || fv.cull == nullptr || fv.pixel_major != kFoldWave || sv.lds_bytes == 0u) return 0u;
+  const uint32_t T = threads ? threads
+                             : std::max(1u, sky_list_resident_threads(sh) / (uint32_t)SPTR_SKY_SPLIT_TDIV * (uint32_t)SPTR_SKY_SPLIT_TNUM);
+  if (mode == 2u) return T;
+  return (uint64_t)fv.P * kSkySplitPixelsDen >= kSkySplitPixelsNum * T ? T : 0u;
+}
+// The place of the list-mode launch in the batch's chain: the last launch before k_accum.  It writes only accum
+// words of pixels that are no item of k_trace_wp's, which nothing reads before k_accum, so any place is correct.
+// Ahead of k_trace_wp it delays the lane's whole chain by its own length; at the end it runs beside the other
+// lane's short late-bounce launches.  Measured (as above, ahead of the trace): C2 2.031-2.037, 2.027-2.042,
+// 2.032-2.056, 2.049, 2.051-2.058, 2.059-2.063; 2-way shard 1.190-1.194, 1.179-1.193, 1.183-1.185, 1.203-1.206,
+// 1.183-1.194, 1.225-1.227: ahead, a small T is best and gains 3 %; last, a large T gains 5.6 % / 9 %.
+static bool sky_split_late() {
+#ifdef SPTR_EXPERIMENT_KNOBS
+  static const bool early = getenv("SPTR_SKY_SPLIT_EARLY") != nullptr;  // (A/B)
+  return !early;
+#else
+  return true;
+#endif
+}
 // The fused launches per bounce: k_shade_trace (shade the previous bounce's hits on dense lanes, then trace)
 // for batches of more than kShadeFirstMinPaths paths, k_bounce01 + k_bounce for the others.  In a small batch
 // a launch lasts as long as its longest wave, and k_shade_trace's closing launch (shade, trace, shade) is the
@@ -367,6 +417,7 @@ FrameView frame_view(const Context& c, const sptr_frame& f) {
   v.plist = nullptr;
   v.unculled = nullptr;
   v.entry = nullptr;
+  v.split_threads = 0u;
   v.integrator = f.integrator;
   v.spf = f.samples_per_frame ? f.samples_per_frame : 4u;
   return v;
@@ -854,7 +905,7 @@ uint32_t enqueue_wavefront(Context& c, const sptr_frame& f, uint32_t k, int T, h
   if (fv.cull && (f.flags & SPTR_FRAME_RECULL)) {  // the count at plist[P] was zeroed by k_frame_dyn
     tm.begin(8);
     launch_cull(sv, fv, static_cast<uint32_t*>(c.cull.p), static_cast<uint32_t*>(c.plist.p),
-                fv.entry ? static_cast<uint32_t*>(c.entry.p) : nullptr, s);
+                fv.entry ? static_cast<uint32_t*>(c.entry.p) : nullptr, c.sky_split_last != 0u, s);
     tm.end();
   }
   uint32_t done = 0, waves = 0;
@@ -908,6 +959,12 @@ uint32_t enqueue_wavefront(Context& c, const sptr_frame& f, uint32_t k, int T, h
     // (r04s: handing them to k_sky beside the thread-per-pixel bounce 0 too: C2 3.09-3.20 -> 3.54-3.57 ms)
     fv.sky_fold = (fv.cull != nullptr && fv.pixel_major == kFoldNone) ? 1u : 0u;
     fv.plist = fv.sky_fold ? static_cast<const uint32_t*>(c.plist.p) : nullptr;
+    // the culled bulk of a lane-group bounce 0 summed thread per pixel (k_sky's list mode), the rest as an item list
+    // (only where this call's cull listed the culled pixels: decided for the call's first batch, sptr_render; a
+    // later batch is never the first to take lane groups)
+    const bool listed = (f.flags & SPTR_FRAME_RECULL) ? c.sky_split_last != 0u : c.cull_listed;
+    fv.split_threads = listed ? sky_split_threads(c, sv, sh, fv) : 0u;
+    if (fv.split_threads) fv.plist = static_cast<const uint32_t*>(c.plist.p);
     // fused bounces (k_shade_trace since r08; the figures here are its predecessors k_bounce01 / k_bounce's), in
     // batches of every size since r06: r02 measured them on C2 only where
     // launches are short (8-way shard 0.627 -> 0.590 ms, 2-way 1.887 -> 1.822, but 1 GPU (133 M paths) 3.39
@@ -975,6 +1032,11 @@ uint32_t enqueue_wavefront(Context& c, const sptr_frame& f, uint32_t k, int T, h
       // straggler hand-off of this bounce's trace (scenes beyond an XCD's L2; not the visit-count pass)
       WaveView wt = w;
       wt.strag_lanes = (strag && (uint32_t)d < kStragHandoffBounces) ? c.strag_lanes : 0u;
+      if (d == 0 && fv.split_threads && !sky_split_late()) {  // (A/B: the culled bulk ahead of the lane groups)
+        tm.begin(4);
+        launch_sky_list(sh, fv, s);
+        tm.end();
+      }
       tm.begin(d == 0 ? 5 : 1);
       const uint32_t g_trace = launch_trace(sv, sh, fv, wt, d, count, g_shade, s);
       tm.end();
@@ -1046,6 +1108,11 @@ uint32_t enqueue_wavefront(Context& c, const sptr_frame& f, uint32_t k, int T, h
     join_shadow();
     if (join_sky) check(hipStreamWaitEvent(s, ev.sky, 0), "sky join wait");
     join_sky = false;
+    if (fv.split_threads && sky_split_late()) {  // the culled bulk (sky_split.h), in this chain (sky_split_late)
+      tm.begin(4);
+      launch_sky_list(sh, fv, s);
+      tm.end();
+    }
     tm.begin(4);
     if (done + kk >= f.spp) tm.last_launch();
     launch_accumulate(fv, w, static_cast<float4*>(c.accum.p), static_cast<uint32_t*>(c.tiles.p),
@@ -1077,8 +1144,9 @@ int refresh_cull(Context& c, const sptr_frame& f, hipStream_t s, bool timing) {
     c.cull_epoch = 0;  // the cached key is set once that sequence is enqueued (sptr_render)
     return SPTR_OK;
   }
+  const bool want_list = c.sky_split_last != 0u;  // this call's bounce 0 splits (sptr_render): it needs the culled list
   if (!(f.flags & SPTR_FRAME_RECULL) && c.cull_epoch == c.epoch && c.cull_depth == depth && c.cull_exact == exact &&
-      std::memcmp(&c.cull_cam, &f.camera, sizeof(sptr_camera)) == 0)
+      (c.cull_listed || !want_list) && std::memcmp(&c.cull_cam, &f.camera, sizeof(sptr_camera)) == 0)
     return SPTR_OK;
   FrameView fv = frame_view(c, f);
   fv.cull_depth = depth;
@@ -1086,7 +1154,7 @@ int refresh_cull(Context& c, const sptr_frame& f, hipStream_t s, bool timing) {
   tm.begin(8);
   API_HIP(hipMemsetAsync(static_cast<uint32_t*>(c.plist.p) + c.P, 0, 8, s));
   launch_cull(sv, fv, static_cast<uint32_t*>(c.cull.p), static_cast<uint32_t*>(c.plist.p),
-              exact ? static_cast<uint32_t*>(c.entry.p) : nullptr, s);
+              exact ? static_cast<uint32_t*>(c.entry.p) : nullptr, want_list, s);
   tm.end();
   API_HIP(hipGetLastError());
   if (tm.err != hipSuccess) return fail(c, SPTR_ERR_HIP, std::string("render: cull events: ") + hipGetErrorString(tm.err));
@@ -1094,6 +1162,7 @@ int refresh_cull(Context& c, const sptr_frame& f, hipStream_t s, bool timing) {
   c.cull_cam = f.camera;
   c.cull_depth = depth;
   c.cull_exact = exact;
+  c.cull_listed = want_list;
   ++c.pending_culls;
   return SPTR_OK;
 }
@@ -1535,6 +1604,14 @@ static int set_bounce_chain_one(sptr_ctx* x, uint32_t mode) {
   return SPTR_OK;
 }
 
+static int set_sky_split_one(sptr_ctx* x, uint32_t mode, uint32_t bulk_threads) {
+  if (!x) return SPTR_ERR_INVALID;
+  if (mode > 2u) return fail(x->c, SPTR_ERR_INVALID, "sky split must be 0 (automatic), 1 (off) or 2 (on)");
+  x->c.sky_split = mode;  // (both are part of the launch-graph key: sptr_render)
+  x->c.sky_split_threads = bulk_threads;
+  return SPTR_OK;
+}
+
 static int set_split_refs_one(sptr_ctx* x, uint32_t max_pieces) {
   if (!x) return SPTR_ERR_INVALID;
   if (max_pieces == 0u) max_pieces = 1u;
@@ -1784,6 +1861,15 @@ static int render_one(sptr_ctx* x, const sptr_frame* f, void* stream, sptr_stats
     key.k = k;
     key.tail = (uint32_t)T;
     key.chain = c.bounce_chain;
+    key.sky_split = c.sky_split;
+    key.sky_split_threads = c.sky_split_threads;
+    {  // what enqueue_wavefront decides for the call's first batch (sptr_sky_split_info)
+      FrameView probe = frame_view(c, *f);
+      probe.k = k;
+      probe.pixel_major = bounce0_pixel_major(scene_view(c), probe);
+      if (!(f->flags & SPTR_FRAME_NO_CULL)) probe.cull = static_cast<const uint32_t*>(c.cull.p);
+      c.sky_split_last = sky_split_threads(c, scene_view(c), shade_view(c), probe);
+    }
     if (c.pending == 0) API_HIP(hipMemsetAsync(c.w_tot.p, 0, kTotWords * 8, s));
     rc = refresh_cull(c, *f, s, timing || trace_timing);
     if (rc != SPTR_OK) return rc;
@@ -1799,6 +1885,7 @@ static int render_one(sptr_ctx* x, const sptr_frame* f, void* stream, sptr_stats
       c.cull_epoch = c.epoch;
       c.cull_cam = f->camera;
       c.cull_exact = cull_exact_for(c, scene_view(c), *f);
+      c.cull_listed = c.sky_split_last != 0u;
       c.cull_depth = cull_depth_for(f->spp, c.cull_exact);
       ++c.pending_culls;
     }
@@ -3128,6 +3215,17 @@ int sptr_set_tail_depth(sptr_ctx* x, uint32_t depth) {
 int sptr_set_bounce_chain(sptr_ctx* x, uint32_t mode) {
   const int rc = set_bounce_chain_one(x, mode);
   return rc == SPTR_OK ? lane_forward(x, set_bounce_chain_one(x ? x->lane : nullptr, mode)) : rc;
+}
+
+int sptr_set_sky_split(sptr_ctx* x, uint32_t mode, uint32_t bulk_threads) {
+  const int rc = set_sky_split_one(x, mode, bulk_threads);
+  return rc == SPTR_OK ? lane_forward(x, set_sky_split_one(x ? x->lane : nullptr, mode, bulk_threads)) : rc;
+}
+
+int sptr_sky_split_info(sptr_ctx* x, uint32_t* bulk_threads) {
+  if (!x || !bulk_threads) return SPTR_ERR_INVALID;
+  *bulk_threads = x->c.sky_split_last;
+  return SPTR_OK;
 }
 
 int sptr_set_split_refs(sptr_ctx* x, uint32_t max_pieces) {

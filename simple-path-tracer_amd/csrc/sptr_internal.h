@@ -157,6 +157,9 @@ struct FrameView {
   uint32_t ablate;  // SPTR_ABLATE environment variable: timing experiments only (0 in normal use)
   float4* accum;    // per local pixel: running sample sum (xyz) + resume slot (w bits), see k_accum
   uint32_t reset;   // this batch starts the accumulation (frame_begin == 1, first batch)
+  // lane-group bounce 0 with the culled bulk split off (sky_split.h): the bulk thread count T; plist then holds
+  // both of k_cull's lists.  0: no split.  (In the padding ahead of the next pointer: the struct keeps its size.)
+  uint32_t split_threads;
   const uint32_t* dyn;  // device {frame_begin, reset, total} of the call (k_frame_dyn); see frame_dyn
   uint32_t pixel_major;  // kFold*: bounce 0 folds each pixel's leading misses into accum (bounce0_pixel_major)
   uint32_t integrator;   // sptr_integrator
@@ -173,6 +176,7 @@ struct FrameView {
   // camera rays start their walk: kNoHit (culled), a node index or a leaf link (k_cull<true>); else null
   const uint32_t* entry;
 };
+static_assert(sizeof(FrameView) == 272, "FrameView: split_threads sits in padding, the kernels' arguments keep their layout");
 // FrameView::dyn words: {frame_begin, reset, total} of the call (k_frame_dyn).
 constexpr size_t kDynBytes = 2048;
 
@@ -403,6 +407,7 @@ struct GraphKey {
   sptr_frame frame;
   uint32_t k, tail;
   uint32_t chain, spare;  // sptr_set_bounce_chain's mode (spare: zero, keeps the key free of padding)
+  uint32_t sky_split, sky_split_threads;  // sptr_set_sky_split's mode and bulk thread count
 };
 struct GraphCache {
   bool valid = false;
@@ -489,6 +494,10 @@ struct Context {
   uint64_t wave_paths = 0;  // 0 = default
   uint32_t tail_depth = 0;  // first bounce traced path-per-thread by k_tail (0 = automatic)
   uint32_t bounce_chain = 0;  // sptr_set_bounce_chain: 0 automatic, 1 off, 2 on wherever applicable
+  uint32_t sky_split = 0;     // sptr_set_sky_split: 0 automatic, 1 off, 2 on wherever applicable
+  uint32_t sky_split_threads = 0;  // its bulk thread count (0: automatic)
+  bool cull_listed = false;        // the cached cull also listed the culled pixels (launch_cull list_culled)
+  uint32_t sky_split_last = 0;     // bulk threads of the last wavefront call's first batch, 0: no split (sptr_sky_split_info)
   // scene
   DevBuf nodes, prim_ref, tris, sph, tri_geom, sph_geom, tri_orig, sph_orig, geom_mat;
   DevBuf tri_mat;  // ShadeView::tri_mat (resolve_geom_materials)
@@ -619,9 +628,14 @@ uint32_t cull_depth_for(uint32_t spp, bool exact);
 // the scene's cull is the exact one, which also writes walk entry words (LDS-staged BVH2 scenes)
 bool cull_entries_apply(const SceneView& sv);
 // entry: the quads' entry words (the exact cull), or null (the box cull down to f.cull_depth)
-void launch_cull(const SceneView& sv, const FrameView& f, uint32_t* mask, uint32_t* plist, uint32_t* entry, hipStream_t s);
+// list_culled: also the culled valid pixels, from the back of plist (a call whose bounce 0 splits, sky_split.h)
+void launch_cull(const SceneView& sv, const FrameView& f, uint32_t* mask, uint32_t* plist, uint32_t* entry, bool list_culled,
+                 hipStream_t s);
 // capped: at most 4 waves per SIMD (beside the launch chain); else full occupancy
 void launch_sky(const ShadeView& sh, const FrameView& f, bool capped, hipStream_t s);
+// k_sky's list mode (f.split_threads bulk threads, sky_split.h) and the threads of its resident grid
+void launch_sky_list(const ShadeView& sh, const FrameView& f, hipStream_t s);
+uint32_t sky_list_resident_threads(const ShadeView& sh);
 // dst local tile i <- a's tile i / 2 (i even) or b's tile i / 2 (i odd): two pixel lanes' tiles in the
 // tile order of the shard they split
 void launch_interleave_tiles(const uint32_t* a, uint32_t na, const uint32_t* b, uint32_t nb, uint32_t* dst,

@@ -136,7 +136,7 @@ _lib = None
 # every symbol include/sptr_hip.h declares
 EXPORTS = [
     "sptr_abi_version", "sptr_create", "sptr_destroy", "sptr_last_error", "sptr_set_debug_mode",
-    "sptr_set_wave_paths", "sptr_set_launch_mode", "sptr_set_pixel_lanes", "sptr_pixel_lanes_info", "sptr_graph_info", "sptr_capture_error", "sptr_overlap_probe", "sptr_set_tail_depth", "sptr_set_bounce_chain", "sptr_set_leaf_size", "sptr_set_split_refs", "sptr_set_stragglers", "sptr_set_bvh_width", "sptr_upload_scene", "sptr_set_materials", "sptr_set_lights",
+    "sptr_set_wave_paths", "sptr_set_launch_mode", "sptr_set_pixel_lanes", "sptr_pixel_lanes_info", "sptr_graph_info", "sptr_capture_error", "sptr_overlap_probe", "sptr_set_tail_depth", "sptr_set_bounce_chain", "sptr_set_sky_split", "sptr_sky_split_info", "sptr_set_leaf_size", "sptr_set_split_refs", "sptr_set_stragglers", "sptr_set_bvh_width", "sptr_upload_scene", "sptr_set_materials", "sptr_set_lights",
     "sptr_set_environment", "sptr_scene_info", "sptr_scene_layout_info", "sptr_render", "sptr_collect_stats",
     "sptr_read_rgb8", "sptr_read_rgb8_lagged",
     "sptr_read_accum",
@@ -178,6 +178,8 @@ def lib() -> C.CDLL:
         "sptr_overlap_probe": (C.c_int, [vp, C.POINTER(C.c_double)]),
         "sptr_set_tail_depth": (C.c_int, [vp, u32]),
         "sptr_set_bounce_chain": (C.c_int, [vp, u32]),
+        "sptr_set_sky_split": (C.c_int, [vp, u32, u32]),
+        "sptr_sky_split_info": (C.c_int, [vp, C.POINTER(u32)]),
         "sptr_set_leaf_size": (C.c_int, [vp, u32]),
         "sptr_set_split_refs": (C.c_int, [vp, u32]),
         "sptr_set_stragglers": (C.c_int, [vp, u32]),
@@ -531,6 +533,17 @@ class Renderer:
     def set_bounce_chain(self, mode: int):
         """0 automatic, 1 off (one launch per bounce), 2 on wherever applicable (sptr_set_bounce_chain)."""
         self._check(self._L.sptr_set_bounce_chain(self._h, mode), "set_bounce_chain")
+
+    def set_sky_split(self, mode: int, bulk_threads: int = 0):
+        """0 automatic, 1 off, 2 on wherever a lane-group bounce 0 has a cull mask; bulk_threads 0 = automatic
+        (sptr_set_sky_split)."""
+        self._check(self._L.sptr_set_sky_split(self._h, mode, bulk_threads), "set_sky_split")
+
+    def sky_split_info(self) -> dict:
+        """{"bulk_threads": of the last wavefront call's first batch, 0 if it did not split}."""
+        t = C.c_uint32()
+        self._check(self._L.sptr_sky_split_info(self._h, C.byref(t)), "sky_split_info")
+        return {"bulk_threads": t.value}
 
     def set_leaf_size(self, n: int):
         self._check(self._L.sptr_set_leaf_size(self._h, n), "set_leaf_size")
