@@ -515,6 +515,55 @@ int sptr_update_geometry(sptr_ctx* ctx, const float* positions, uint32_t num_ver
 int sptr_refit_info(const sptr_ctx* ctx, uint32_t* refits, double* ms_wall, double* ms_device,
                     uint32_t* excluded_prims);
 
+/* ---- dynamic scenes: per-geometry transforms applied on the device (symbols added within ABI 9: no
+ *      existing struct or entry point changed) --------------------------------------------------------
+ * Rigid motion needs no new vertices: the caller hands over one matrix per triangle geometry, and the refit's
+ * slot pass transforms a kept copy of the vertices, the rest pose, while it gathers them (DESIGN.md "Dynamic
+ * scenes", transforms).  64 bytes per geometry cross the bus instead of 12 per vertex.
+ *
+ * Values of sptr_set_dynamic.  Any non-zero value keeps the refit tables, as before.  With the bit
+ * SPTR_DYNAMIC_TRANSFORMS the next upload also keeps a device copy of the uploaded positions, the rest pose
+ * (12 B per vertex), and records the cost of its tree (sptr_tree_cost) once, at its end.  Without that bit an
+ * upload allocates, launches and keeps exactly what it did before these entry points existed. */
+enum { SPTR_DYNAMIC_REFIT = 1u, SPTR_DYNAMIC_TRANSFORMS = 2u };
+/* Replaces the rest pose: num_verts * 3 floats, num_verts equal to the upload's; flags takes
+ * SPTR_UPDATE_DEVICE_PTRS.  Nothing visible changes until the next sptr_update_transforms.  A caller uploads the
+ * world-space flattening, so that the tree is built over the scene as it looks, sets the object-space vertices as
+ * the rest pose, and from then on sends the instances' matrices.  Without this call the matrices are relative to
+ * the uploaded pose.  Errors as sptr_update_transforms. */
+int sptr_set_rest_positions(sptr_ctx* ctx, const float* positions, uint32_t num_verts, uint32_t flags);
+/* xforms = num_tri_geoms * 16 floats, one glm-layout mat4 per triangle geometry in geomID order: column-major,
+ * m[col][row], as InstanceData::worldFromObject holds it; or NULL: the triangles keep their records.  spheres as
+ * in sptr_update_geometry, or NULL; not both NULL.  A triangle of geometry g takes each of its three vertices as
+ * glm's M_g * vec4(rest[v], 1) without its w: per component k, m0 = M[0][k] x, m1 = M[1][k] y, m2 = M[2][k] z,
+ * m3 = M[3][k] 1.0f, result (m0 + m1) + (m2 + m3), in float32 without contraction: the bits the host layer's
+ * flattening gives.  Row 3 of the matrix is ignored.  A vertex shared by triangles of two geometries is
+ * transformed per triangle; no world-position buffer is written.  Each call determines the triangles from the
+ * rest pose alone: transforms do not accumulate.  A later sptr_update_geometry(positions) sets world positions
+ * as ever and leaves the rest pose alone.  Everything else is sptr_update_geometry's: it waits for pending
+ * renders, refits on the context's stream and then the pixel lane's copy, bumps the state epoch, takes the
+ * sptr_set_history_motion snapshot first under the same condition, and counts in sptr_refit_info.
+ * SPTR_ERR_NO_SCENE before an upload; SPTR_ERR_INVALID when the scene was not uploaded with
+ * SPTR_DYNAMIC_TRANSFORMS, a count differs from the upload's, both pointers are NULL, a flag is unknown, the
+ * scene uses split references, the context is a lane context, or a host-pointer matrix has an entry that is
+ * not finite.  Matrices given by device pointer (SPTR_UPDATE_DEVICE_PTRS) are not inspected: what a NaN or an
+ * infinity in them does to the boxes is the caller's to avoid. */
+int sptr_update_transforms(sptr_ctx* ctx, const float* xforms, uint32_t num_tri_geoms,
+                           const float* spheres, uint32_t num_spheres, uint32_t flags);
+/* When does an upload pay?  A refit keeps the upload's topology, and boxes that mix two objects grow as the
+ * objects part.  cost = the sum, over the inner nodes of the BVH2 that a walk can reach and over both child
+ * boxes b of each, of w * A(b), with A(b) = 2 (dx dy + dy dz + dz dx) computed in double from the float extents
+ * and w = 1 for an inner child, the leaf range's primitive count for a leaf child; root_area = A of the union
+ * of the root's two child boxes.  Both for the tree as it stands, and as the upload recorded them (0 when the
+ * scene was not uploaded with SPTR_DYNAMIC_TRANSFORMS).  The cost is absolute, not divided by the root area:
+ * a fixed set of camera rays has a fixed line density, and a root that grows because one object left would
+ * make a relative figure improve.  Scenes walked as BVH4 report the BVH2 they were collapsed from (a refit
+ * re-quantises their wide boxes from those boxes).  A scene of one leaf range has no inner node a walk reaches:
+ * cost 0.  The sum has a fixed shape (per-thread sums in node order, a block tree, the blocks in order on the
+ * host), so the same tree gives the same bits on every call.  Waits for pending renders; one launch.  Any
+ * output pointer may be NULL.  SPTR_ERR_NO_SCENE before an upload. */
+int sptr_tree_cost(sptr_ctx* ctx, double* cost, double* root_area, double* cost_at_upload, double* root_area_at_upload);
+
 /* ---- ray queries on caller buffers (symbols added within ABI 9: no existing struct or entry point
  *      changed) ------------------------------------------------------------------------------------------
  * Batched closest-hit / any-hit queries against the uploaded (and possibly refitted) scene, for callers that

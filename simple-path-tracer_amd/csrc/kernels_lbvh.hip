@@ -830,6 +830,8 @@ int build_lbvh(Context& c, const float* h_pos, uint32_t nverts, const uint32_t* 
   c.rf.ms_snapshot = 0.0;
   c.rf.num_verts = nverts;
   c.rf.max_h = 0;
+  c.rf.xf_valid = false;
+  c.rf.cost_upload = c.rf.area_upload = 0.0;
   if (!c.dynamic) refit_release(c);
   if (NP == 0) {
     c.num_nodes = 0;
@@ -1121,9 +1123,17 @@ int build_lbvh(Context& c, const float* h_pos, uint32_t nverts, const uint32_t* 
     const int rr = refit_retain_slots(c, d_pos, d_idx, d_sph);
     if (rr != SPTR_OK) return rr;
     c.rf.valid = true;
+    if (c.dynamic_xf) {  // the rest pose of sptr_update_transforms: the uploaded positions
+      LB_CHECK(c.rf.rest.ensure((size_t)nverts * 12));
+      if (nverts) LB_CHECK(hipMemcpyAsync(c.rf.rest.p, d_pos, (size_t)nverts * 12, hipMemcpyDeviceToDevice, s));
+      c.rf.xf_valid = true;
+    }
   }
+  if (!c.rf.xf_valid) c.rf.rest.release();
   LB_CHECK(hipStreamSynchronize(s));
   c.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  // ... and the finished tree's cost, once: what sptr_tree_cost's later figures are compared with
+  if (c.rf.xf_valid) return refit_tree_cost(c, &c.rf.cost_upload, &c.rf.area_upload);
   return SPTR_OK;
 }
 

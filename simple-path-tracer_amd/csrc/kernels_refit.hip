@@ -12,17 +12,22 @@
 //   k_refit_wide  : every wide node re-quantised (quantize_wide, the function k_wide_emit calls) from
 //                   the BVH2 boxes its children were collapsed from (the source table k_wide_sources
 //                   wrote at upload)
+// k_refit_slots<true> (sptr_update_transforms) is the slot pass reading a kept rest pose and moving each
+// triangle's vertices by its geometry's matrix first; k_tree_cost (sptr_tree_cost) sums the BVH2's child box
+// areas in a fixed shape ("Transforms").
 // No kernel here waits for, or hands data to, another workgroup of its launch: kernel boundaries and
 // __syncthreads() are the only synchronisation.  fminf / fmaxf are exact, so a box does not depend on
 // the order its parts are merged in (the build's k_refit merges in tree order), up to the sign of a zero.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 
 #include "lbvh_shared.h"
 #include "sptr_internal.h"
+#include "xform_point.h"
 
 namespace sptr {
 
@@ -48,7 +53,14 @@ struct SlotIn {
   uint32_t n;                // sorted positions
 };
 
-__global__ void __launch_bounds__(256) k_refit_slots(SlotIn in, float4* tris, float4* sph, float4* box_lo, float4* box_hi) {
+// kXf (sptr_update_transforms): in.pos is the rest pose, and a triangle's three gathered vertices go through
+// its geometry's matrix (xform_point, the host flattening's arithmetic) before the record and the box:
+// tri_geom[slot] = the slot's geomID, xf = 16 floats per triangle geometry (glm layout; 12 are read).  A
+// vertex shared by triangles of two geometries is transformed per triangle; no position is written back.
+// Without kXf the two tables are not read, and the code is the kernel's as it was before the template.
+template <bool kXf>
+__global__ void __launch_bounds__(256) k_refit_slots(SlotIn in, float4* tris, float4* sph, float4* box_lo, float4* box_hi,
+                                                     const uint32_t* tri_geom, const float* xf) {
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < in.n; i += gridDim.x * blockDim.x) {
     const uint32_t ref = in.prim_ref[i], slot = ref & kIndexMask;
     vec3 lo, hi;
@@ -60,9 +72,16 @@ __global__ void __launch_bounds__(256) k_refit_slots(SlotIn in, float4* tris, fl
     } else {
       if (!in.pos) continue;
       const uint32_t a = in.idx[3 * slot], b = in.idx[3 * slot + 1], c = in.idx[3 * slot + 2];
-      const vec3 v0 = v3(in.pos[3 * a], in.pos[3 * a + 1], in.pos[3 * a + 2]);
-      const vec3 v1 = v3(in.pos[3 * b], in.pos[3 * b + 1], in.pos[3 * b + 2]);
-      const vec3 v2 = v3(in.pos[3 * c], in.pos[3 * c + 1], in.pos[3 * c + 2]);
+      vec3 v0 = v3(in.pos[3 * a], in.pos[3 * a + 1], in.pos[3 * a + 2]);
+      vec3 v1 = v3(in.pos[3 * b], in.pos[3 * b + 1], in.pos[3 * b + 2]);
+      vec3 v2 = v3(in.pos[3 * c], in.pos[3 * c + 1], in.pos[3 * c + 2]);
+      if (kXf) {
+        // (slots are in tree order, so most of a wave reads one geometry's matrix: one cache line)
+        const float* m = xf + 16 * (size_t)tri_geom[slot];
+        v0 = xform_point(m, v0);
+        v1 = xform_point(m, v1);
+        v2 = xform_point(m, v2);
+      }
       float4 rec[3];
       tri_record(v0, v1, v2, rec);
       tris[3 * slot + 0] = rec[0];
@@ -178,19 +197,71 @@ unsigned blocks_for(size_t n) {
   return (unsigned)b;
 }
 
-void launch_slots(Context& c, const float* d_pos, const float4* d_sph) {
+// d_xf == null: d_pos holds world positions; else d_pos is the rest pose and d_xf the matrix table
+void launch_slots(Context& c, const float* d_pos, const float4* d_sph, const float* d_xf = nullptr) {
   const uint32_t n = c.num_tri_refs + c.num_sph;
   SlotIn in{d_pos, d_sph, static_cast<const uint32_t*>(c.rf.idx.p), static_cast<const uint32_t*>(c.sph_orig.p),
             static_cast<const uint32_t*>(c.prim_ref.p), n};
-  hipLaunchKernelGGL(k_refit_slots, dim3(blocks_for(n)), dim3(256), 0, c.stream, in, static_cast<float4*>(c.tris.p),
-                     static_cast<float4*>(c.sph.p), static_cast<float4*>(c.rf.box_lo.p), static_cast<float4*>(c.rf.box_hi.p));
+  float4 *tris = static_cast<float4*>(c.tris.p), *sph = static_cast<float4*>(c.sph.p);
+  float4 *blo = static_cast<float4*>(c.rf.box_lo.p), *bhi = static_cast<float4*>(c.rf.box_hi.p);
+  if (d_xf)
+    hipLaunchKernelGGL(k_refit_slots<true>, dim3(blocks_for(n)), dim3(256), 0, c.stream, in, tris, sph, blo, bhi,
+                       static_cast<const uint32_t*>(c.tri_geom.p), d_xf);
+  else
+    hipLaunchKernelGGL(k_refit_slots<false>, dim3(blocks_for(n)), dim3(256), 0, c.stream, in, tris, sph, blo, bhi,
+                       static_cast<const uint32_t*>(nullptr), static_cast<const float*>(nullptr));
 }
+
+// ---- tree cost (sptr_tree_cost) ------------------------------------------------------------------
+// Sum over the BVH2's inner nodes, over both child boxes b, of w * A(b): A = 2 (dx dy + dy dz + dz dx) in
+// double from the float extents, w = 1 for an inner child, the range's primitive count for a leaf child.
+// A node counts when the walk can reach it: more than leaf_max primitives below it (a smaller subtree is
+// its parent's leaf range; link.w, k_karras).  The shape is fixed by the node count alone: thread t of the
+// grid adds its nodes in ascending order, a block folds its 256 sums as a binary tree in LDS and stores one
+// partial, and the host adds the partials in block order; so one tree gives one result, bit for bit, on
+// every call.  No atomics.  partial[gridDim.x] = the area of the union of the root's two child boxes.
+__device__ __forceinline__ double box_area_d(float lx, float hx, float ly, float hy, float lz, float hz) {
+  const double dx = (double)hx - (double)lx, dy = (double)hy - (double)ly, dz = (double)hz - (double)lz;
+  return 2.0 * (dx * dy + dy * dz + dz * dx);
+}
+__device__ __forceinline__ double link_weight(uint32_t link) {
+  return (link & kLeafBit) ? (double)((link & kLeafRangeMask) + 1u) : 1.0;
+}
+__global__ void __launch_bounds__(256) k_tree_cost(uint32_t nn, uint32_t leaf_max, const BvhNode* nodes, double* partial) {
+  __shared__ double s_sum[256];
+  double acc = 0.0;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < nn; i += gridDim.x * blockDim.x) {
+    const uint4 link = nodes[i].link;
+    if (link.w <= leaf_max) continue;
+    const float4 l = nodes[i].lxy, r = nodes[i].rxy, z = nodes[i].z;
+    acc += link_weight(link.x) * box_area_d(l.x, l.y, l.z, l.w, z.x, z.y);
+    acc += link_weight(link.y) * box_area_d(r.x, r.y, r.z, r.w, z.z, z.w);
+  }
+  s_sum[threadIdx.x] = acc;
+  __syncthreads();
+  for (uint32_t st = 128; st > 0; st >>= 1) {
+    if (threadIdx.x < st) s_sum[threadIdx.x] += s_sum[threadIdx.x + st];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    partial[blockIdx.x] = s_sum[0];
+    if (blockIdx.x == 0) {
+      const float4 l = nodes[0].lxy, r = nodes[0].rxy, z = nodes[0].z;
+      partial[gridDim.x] = box_area_d(fminf(l.x, r.x), fmaxf(l.y, r.y), fminf(l.z, r.z), fmaxf(l.w, r.w), fminf(z.x, z.z),
+                                      fmaxf(z.y, z.w));
+    }
+  }
+}
+constexpr unsigned kCostBlocksMax = 1024;
 
 }  // namespace
 
 void refit_release(Context& c) {
   RefitState& r = c.rf;
-  for (DevBuf* b : {&r.idx, &r.box_lo, &r.box_hi, &r.order, &r.hoff, &r.wsrc, &r.in_pos, &r.in_sph, &r.snap}) b->release();
+  for (DevBuf* b : {&r.idx, &r.box_lo, &r.box_hi, &r.order, &r.hoff, &r.wsrc, &r.in_pos, &r.in_sph, &r.snap, &r.rest, &r.in_xf,
+                    &r.cost_part})
+    b->release();
+  r.xf_valid = false;
   r.hoff_h.clear();
   r.valid = false;
 }
@@ -234,7 +305,7 @@ void launch_wide_sources(uint32_t ncur, const uint2* cur, uint32_t base, const B
   hipLaunchKernelGGL(k_wide_sources, dim3(blocks_for(ncur)), dim3(256), 0, s, ncur, cur, base, nodes, wsrc);
 }
 
-int refit_lbvh(Context& c, const float* d_pos, const float4* d_sph) {
+int refit_lbvh(Context& c, const float* d_pos, const float4* d_sph, const float* d_xf) {
   const auto t0 = std::chrono::steady_clock::now();
   RefitState& r = c.rf;
   hipStream_t s = c.stream;
@@ -243,7 +314,7 @@ int refit_lbvh(Context& c, const float* d_pos, const float4* d_sph) {
   BvhNode* nodes = static_cast<BvhNode*>(c.nodes.p);
   const float4 *blo = static_cast<const float4*>(r.box_lo.p), *bhi = static_cast<const float4*>(r.box_hi.p);
   RF_CHECK(hipEventRecord(r.ev[0], s));
-  if (c.num_tri_refs + c.num_sph) launch_slots(c, c.num_tri_refs ? d_pos : nullptr, c.num_sph ? d_sph : nullptr);
+  if (c.num_tri_refs + c.num_sph) launch_slots(c, c.num_tri_refs ? d_pos : nullptr, c.num_sph ? d_sph : nullptr, d_xf);
   RF_CHECK(hipEventRecord(r.ev[1], s));
   if (c.num_nodes) {
     const uint32_t* order = static_cast<const uint32_t*>(r.order.p);
@@ -278,6 +349,36 @@ int refit_lbvh(Context& c, const float* d_pos, const float4* d_sph) {
   if (print)
     std::fprintf(stderr, "refit %u: slots %.4f ms, bvh2 %.4f ms (%u heights), wide %.4f ms, wall %.4f ms\n", r.refits,
                  r.ms_stage[0], r.ms_stage[1], r.max_h, r.ms_stage[2], r.ms_wall);
+  return SPTR_OK;
+}
+
+// One k_tree_cost launch on c.stream and the in-order sum of its partials on the host; returns when done.
+int refit_tree_cost(Context& c, double* cost, double* root_area) {
+  RefitState& r = c.rf;
+  *cost = *root_area = 0.0;
+  if (!c.num_nodes) return SPTR_OK;  // a single primitive: no inner node
+  hipStream_t s = c.stream;
+  for (DevEvent& e : r.cost_ev)
+    if (!e) RF_CHECK(hipEventCreate(e.put()));
+  const unsigned blocks = std::min(blocks_for(c.num_nodes), kCostBlocksMax);
+  RF_CHECK(r.cost_part.ensure((size_t)(kCostBlocksMax + 1) * sizeof(double)));
+  RF_CHECK(hipEventRecord(r.cost_ev[0], s));
+  hipLaunchKernelGGL(k_tree_cost, dim3(blocks), dim3(256), 0, s, c.num_nodes, c.leaf_used, static_cast<const BvhNode*>(c.nodes.p),
+                     static_cast<double*>(r.cost_part.p));
+  RF_CHECK(hipGetLastError());
+  RF_CHECK(hipEventRecord(r.cost_ev[1], s));
+  double part[kCostBlocksMax + 1];
+  RF_CHECK(hipMemcpyAsync(part, r.cost_part.p, (size_t)(blocks + 1) * sizeof(double), hipMemcpyDeviceToHost, s));
+  RF_CHECK(hipStreamSynchronize(s));
+  float ms = 0.0f;
+  RF_CHECK(hipEventElapsedTime(&ms, r.cost_ev[0], r.cost_ev[1]));
+  r.ms_cost = ms;
+  double sum = 0.0;
+  for (unsigned b = 0; b < blocks; ++b) sum += part[b];
+  *cost = sum;
+  *root_area = part[blocks];
+  static const bool print = std::getenv("SPTR_REFIT_STAGES") != nullptr;
+  if (print) std::fprintf(stderr, "tree cost: %.4f ms (%u nodes, %u blocks)\n", r.ms_cost, c.num_nodes, blocks);
   return SPTR_OK;
 }
 

@@ -2487,16 +2487,50 @@ int sptr_upload_scene(sptr_ctx* x, const sptr_scene* s) {
 int sptr_set_dynamic(sptr_ctx* x, uint32_t on) {
   if (!x) return SPTR_ERR_INVALID;
   x->c.dynamic = on != 0u;  // read by the next upload (build_lbvh)
+  x->c.dynamic_xf = (on & SPTR_DYNAMIC_TRANSFORMS) != 0u;
+  // (the lane's copy of the scene is refitted from this context's rest pose and matrices: it keeps neither)
   if (x->lane) x->lane->c.dynamic = x->c.dynamic;
   return SPTR_OK;
 }
 
-// c's scene refitted from device coordinates (either may be null)
-static int refit_one(Context& c, const float* d_pos, const float* d_sph) {
+// c's scene refitted from device coordinates (either may be null); d_xf: refit_lbvh
+static int refit_one(Context& c, const float* d_pos, const float* d_sph, const float* d_xf) {
   if (sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;  // a pending render may still read the old boxes
-  const int rc = refit_lbvh(c, d_pos, reinterpret_cast<const float4*>(d_sph));
+  const int rc = refit_lbvh(c, d_pos, reinterpret_cast<const float4*>(d_sph), d_xf);
   ++c.epoch;  // cull mask, AOV planes and captured graphs were computed for the old coordinates
   return rc;
+}
+
+// The body sptr_update_geometry and sptr_update_transforms share, after their arguments are checked and their
+// host arrays staged on c.stream: the history's snapshot, the refit, the epoch, the pixel lane's copy.
+static int refit_scene(sptr_ctx* x, const char* who, const float* d_pos, const float* d_sph, const float* d_xf,
+                       std::chrono::steady_clock::time_point t0) {
+  Context& c = x->c;
+  // sptr_set_history_motion: the records the last history pass saw, kept before the refit overwrites them.
+  // Only when that pass ran on this generation: after two refits between passes the snapshot still holds
+  // the geometry of the pass a later call takes as its carry.
+  auto& d = x->dn;
+  if (d.motion_on && d.last.valid && d.last.gen == d.geom_gen) {
+    const int rs = refit_snapshot(c);
+    if (rs != SPTR_OK) return rs;
+    d.snap_gen = d.geom_gen;
+    d.snap_valid = true;
+  }
+  const uint64_t epoch_before = c.epoch;
+  const int rc = refit_one(c, d_pos, d_sph, d_xf);  // (returns after c.stream drained: the staging is stable)
+  ++d.geom_gen;
+  if (rc != SPTR_OK) return rc;
+  if (d.motion_on)  // the history outlives the refit: its passes follow the epoch, and differ by generation
+    for (sptr_ctx::Denoise::Pass* p : {&d.last, &d.carry})
+      if (p->valid && p->epoch == epoch_before) p->epoch = c.epoch;
+  if (x->lane && x->lane_scene) {  // the lane's copy of the scene, on the lane's stream
+    Context& cy = x->lane->c;
+    if (!cy.rf.valid) return fail(c, SPTR_ERR_INVALID, std::string(who) + ": the pixel lane's scene is not dynamic");
+    const int r1 = refit_one(cy, d_pos, d_sph, d_xf);
+    if (r1 != SPTR_OK) return lane_forward(x, r1);
+  }
+  c.rf.ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return SPTR_OK;
 }
 
 int sptr_update_geometry(sptr_ctx* x, const float* positions, uint32_t num_verts, const float* spheres,
@@ -2528,30 +2562,88 @@ int sptr_update_geometry(sptr_ctx* x, const float* positions, uint32_t num_verts
       d_sph = static_cast<const float*>(c.rf.in_sph.p);
     }
   }
-  // sptr_set_history_motion: the records the last history pass saw, kept before the refit overwrites them.
-  // Only when that pass ran on this generation: after two refits between passes the snapshot still holds
-  // the geometry of the pass a later call takes as its carry.
-  auto& d = x->dn;
-  if (d.motion_on && d.last.valid && d.last.gen == d.geom_gen) {
-    const int rs = refit_snapshot(c);
-    if (rs != SPTR_OK) return rs;
-    d.snap_gen = d.geom_gen;
-    d.snap_valid = true;
+  return refit_scene(x, "update_geometry", d_pos, d_sph, nullptr, t0);
+}
+
+// The checks sptr_set_rest_positions and sptr_update_transforms share.
+static int transforms_ready(sptr_ctx* x, const char* who) {
+  Context& c = x->c;
+  const std::string w(who);
+  if (x->is_lane) return fail(c, SPTR_ERR_INVALID, w + ": not on a lane context");
+  if (!c.have_scene) return fail(c, SPTR_ERR_NO_SCENE, w + ": no scene uploaded");
+  if (c.rf.split) return fail(c, SPTR_ERR_INVALID, w + ": the scene was built with split references (sptr_set_split_refs)");
+  if (!c.rf.valid || !c.rf.xf_valid)
+    return fail(c, SPTR_ERR_INVALID, w + ": the scene was not uploaded with sptr_set_dynamic(SPTR_DYNAMIC_TRANSFORMS)");
+  return SPTR_OK;
+}
+
+int sptr_set_rest_positions(sptr_ctx* x, const float* positions, uint32_t num_verts, uint32_t flags) {
+  if (!x) return SPTR_ERR_INVALID;
+  Context& c = x->c;
+  const int ready = transforms_ready(x, "set_rest_positions");
+  if (ready != SPTR_OK) return ready;
+  if (num_verts != c.rf.num_verts || (num_verts && !positions))
+    return fail(c, SPTR_ERR_INVALID, "set_rest_positions: the vertex count differs from the uploaded scene's");
+  if (flags & ~(uint32_t)SPTR_UPDATE_DEVICE_PTRS) return fail(c, SPTR_ERR_INVALID, "set_rest_positions: unknown flags");
+  API_HIP(hipSetDevice(c.device));
+  if (sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;
+  if (num_verts) {
+    API_HIP(hipMemcpyAsync(c.rf.rest.p, positions, (size_t)num_verts * 12,
+                           (flags & SPTR_UPDATE_DEVICE_PTRS) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c.stream));
+    API_HIP(hipStreamSynchronize(c.stream));
   }
-  const uint64_t epoch_before = c.epoch;
-  const int rc = refit_one(c, d_pos, d_sph);  // (returns after c.stream drained: the staging is stable)
-  ++d.geom_gen;
-  if (rc != SPTR_OK) return rc;
-  if (d.motion_on)  // the history outlives the refit: its passes follow the epoch, and differ by generation
-    for (sptr_ctx::Denoise::Pass* p : {&d.last, &d.carry})
-      if (p->valid && p->epoch == epoch_before) p->epoch = c.epoch;
-  if (x->lane && x->lane_scene) {  // the lane's copy of the scene, on the lane's stream
-    Context& cy = x->lane->c;
-    if (!cy.rf.valid) return fail(c, SPTR_ERR_INVALID, "update_geometry: the pixel lane's scene is not dynamic");
-    const int r1 = refit_one(cy, d_pos, d_sph);
-    if (r1 != SPTR_OK) return lane_forward(x, r1);
+  return SPTR_OK;
+}
+
+int sptr_update_transforms(sptr_ctx* x, const float* xforms, uint32_t num_tri_geoms, const float* spheres,
+                           uint32_t num_spheres, uint32_t flags) {
+  if (!x) return SPTR_ERR_INVALID;
+  Context& c = x->c;
+  const int ready = transforms_ready(x, "update_transforms");
+  if (ready != SPTR_OK) return ready;
+  if (!xforms && !spheres) return fail(c, SPTR_ERR_INVALID, "update_transforms: neither matrices nor spheres given");
+  // (a scene whose triangles belong to no geometry has no matrix to take: num_tri_geoms 0 is refused with xforms)
+  if ((xforms && (num_tri_geoms != c.num_tri_geoms || num_tri_geoms == 0u)) || (spheres && num_spheres != c.num_sph))
+    return fail(c, SPTR_ERR_INVALID, "update_transforms: counts differ from the uploaded scene's");
+  if (flags & ~(uint32_t)SPTR_UPDATE_DEVICE_PTRS) return fail(c, SPTR_ERR_INVALID, "update_transforms: unknown flags");
+  const bool device = (flags & SPTR_UPDATE_DEVICE_PTRS) != 0u;
+  if (xforms && !device)
+    for (size_t i = 0; i < (size_t)num_tri_geoms * 16; ++i)
+      if (!std::isfinite(xforms[i])) return fail(c, SPTR_ERR_INVALID, "update_transforms: a matrix entry is not finite");
+  const auto t0 = std::chrono::steady_clock::now();
+  API_HIP(hipSetDevice(c.device));
+  if (sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;
+  const float *d_xf = xforms, *d_sph = spheres;
+  if (!device) {
+    if (xforms) {
+      API_HIP(c.rf.in_xf.ensure((size_t)num_tri_geoms * 64));
+      API_HIP(hipMemcpyAsync(c.rf.in_xf.p, xforms, (size_t)num_tri_geoms * 64, hipMemcpyHostToDevice, c.stream));
+      d_xf = static_cast<const float*>(c.rf.in_xf.p);
+    }
+    if (spheres) {
+      API_HIP(c.rf.in_sph.ensure((size_t)num_spheres * 16));
+      API_HIP(hipMemcpyAsync(c.rf.in_sph.p, spheres, (size_t)num_spheres * 16, hipMemcpyHostToDevice, c.stream));
+      d_sph = static_cast<const float*>(c.rf.in_sph.p);
+    }
   }
-  c.rf.ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return refit_scene(x, "update_transforms", d_xf ? static_cast<const float*>(c.rf.rest.p) : nullptr, d_sph, d_xf, t0);
+}
+
+int sptr_tree_cost(sptr_ctx* x, double* cost, double* root_area, double* cost_at_upload, double* root_area_at_upload) {
+  if (!x) return SPTR_ERR_INVALID;
+  Context& c = x->c;
+  if (!c.have_scene) return fail(c, SPTR_ERR_NO_SCENE, "tree_cost: no scene uploaded");
+  API_HIP(hipSetDevice(c.device));
+  if (sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;
+  double cur = 0.0, area = 0.0;
+  if (cost || root_area) {
+    const int rc = refit_tree_cost(c, &cur, &area);
+    if (rc != SPTR_OK) return rc;
+  }
+  if (cost) *cost = cur;
+  if (root_area) *root_area = area;
+  if (cost_at_upload) *cost_at_upload = c.rf.cost_upload;
+  if (root_area_at_upload) *root_area_at_upload = c.rf.area_upload;
   return SPTR_OK;
 }
 

@@ -445,6 +445,15 @@ struct RefitState {
   DevEvent snap_ev[2];
   uint32_t snapshots = 0;  // since the upload
   double ms_snapshot = 0.0;  // device ms of the last one
+  // sptr_set_dynamic's SPTR_DYNAMIC_TRANSFORMS bit (sptr_update_transforms, sptr_tree_cost): the rest pose
+  // (12 B per vertex: the uploaded positions, or sptr_set_rest_positions'), the staging of host-pointer
+  // matrices (64 B per triangle geometry), and the tree cost the upload recorded at its end
+  bool xf_valid = false;   // the current scene keeps a rest pose
+  DevBuf rest, in_xf;
+  DevBuf cost_part;        // k_tree_cost's per-block partials, then the root area
+  DevEvent cost_ev[2];
+  double ms_cost = 0.0;    // device ms of the last k_tree_cost
+  double cost_upload = 0.0, area_upload = 0.0;
 };
 
 struct Context {
@@ -519,6 +528,7 @@ struct Context {
   bool have_scene = false;
   double build_ms = 0.0;
   bool dynamic = false;  // sptr_set_dynamic: the next upload keeps RefitState
+  bool dynamic_xf = false;  // ... its SPTR_DYNAMIC_TRANSFORMS bit: and the rest pose, and records its tree cost
   RefitState rf;
   // shading state
   std::vector<DevMaterial> mats_host;
@@ -564,10 +574,13 @@ int build_lbvh(Context& c, const float* h_pos, uint32_t nverts, const uint32_t* 
 // kernels_refit.hip.  The upload's part (dynamic scenes only): the slot-order index triples and the
 // first slot boxes; the source table of one wide level (cur[j].x = BVH2 node of wide node base + j).
 // refit_lbvh: new device coordinates (either may be null: unchanged) -> triangle records, spheres and
-// every BVH2 and wide box in place, on c.stream; returns when done.
+// every BVH2 and wide box in place, on c.stream; returns when done.  With d_xf (16 floats per triangle
+// geometry, sptr_update_transforms) d_pos is the rest pose and each triangle takes its geometry's matrix.
 int refit_retain_slots(Context& c, const float* d_pos, const uint32_t* d_idx, const float4* d_sph);
 void launch_wide_sources(uint32_t ncur, const uint2* cur, uint32_t base, const BvhNode* nodes, uint32_t* wsrc, hipStream_t s);
-int refit_lbvh(Context& c, const float* d_pos, const float4* d_sph);
+int refit_lbvh(Context& c, const float* d_pos, const float4* d_sph, const float* d_xf = nullptr);
+// the BVH2's cost and root area as it stands (sptr_tree_cost), on c.stream; returns when done
+int refit_tree_cost(Context& c, double* cost, double* root_area);
 // the triangle records and spheres copied into RefitState::snap on c.stream (sptr_set_history_motion: taken
 // before refit_lbvh overwrites them); returns when done
 int refit_snapshot(Context& c);

@@ -39,13 +39,29 @@ void HipBackend::setDebugMode(int mode) {
 
 bool HipBackend::build(const scene::SceneDesc& sd) {
   if (!ensureContext()) return false;
-  return buildFlat(scene::Flatten(sd));
+  return buildScene(sd, scene::Flatten(sd));
+}
+
+// The tree is built over the world-space flattening, the scene as it looks; with Settings::transforms the
+// meshes' own vertices then become the rest pose the instances' matrices move.
+bool HipBackend::buildScene(const scene::SceneDesc& sd, const scene::FlatScene& flat) {
+  built_rest_.clear();
+  if (!buildFlat(flat)) return false;
+  if (settings_.transforms && built_verts_) {
+    scene::FlatScene obj = scene::Flatten(sd, true);
+    // (a scene built with split references keeps no rest pose: update() then sends vertices, and builds again)
+    if (sptr_set_rest_positions(ctx_, obj.positions.data(), uint32_t(obj.positions.size() / 3), 0u) == SPTR_OK)
+      built_rest_ = std::move(obj.positions);
+  }
+  return true;
 }
 
 bool HipBackend::buildFlat(const scene::FlatScene& flat) {
   const sptr_scene v = flat.view();
   built_ = false;
-  if (sptr_set_dynamic(ctx_, settings_.dynamic ? 1u : 0u) != SPTR_OK) return false;
+  const uint32_t dyn = settings_.transforms ? uint32_t(SPTR_DYNAMIC_REFIT | SPTR_DYNAMIC_TRANSFORMS)
+                                            : (settings_.dynamic ? uint32_t(SPTR_DYNAMIC_REFIT) : 0u);
+  if (sptr_set_dynamic(ctx_, dyn) != SPTR_OK) return false;
   const int rc = sptr_upload_scene(ctx_, &v);
   if (rc != SPTR_OK) {
     err_ = std::string("HipBackend::build: ") + sptr_last_error(ctx_);
@@ -56,7 +72,7 @@ bool HipBackend::buildFlat(const scene::FlatScene& flat) {
   built_geom_first_ = flat.tri_geom_first;
   built_verts_ = flat.positions.size() / 3;
   built_spheres_ = flat.spheres.size() / 4;
-  built_dynamic_ = settings_.dynamic;
+  built_dynamic_ = settings_.dynamic || settings_.transforms;
   built_ = true;
   frame_index_ = 0;
   return true;
@@ -64,6 +80,23 @@ bool HipBackend::buildFlat(const scene::FlatScene& flat) {
 
 bool HipBackend::update(const scene::SceneDesc& sd) {
   if (!ensureContext()) return false;
+  sent_transforms_ = false;
+  if (built_ && built_dynamic_ && !built_rest_.empty()) {
+    // the flattening without its transform: equal to the built one, only matrices and spheres can have moved
+    const scene::FlatScene obj = scene::Flatten(sd, true);
+    if (obj.positions == built_rest_ && obj.spheres.size() / 4 == built_spheres_ && obj.indices == built_indices_ &&
+        obj.tri_geom_first == built_geom_first_ && obj.geom_material == geom_material_) {
+      const std::vector<float> xf = scene::InstanceMatrices(sd);
+      const int rc = sptr_update_transforms(ctx_, xf.data(), uint32_t(xf.size() / 16),
+                                            built_spheres_ ? obj.spheres.data() : nullptr, uint32_t(built_spheres_), 0u);
+      if (rc == SPTR_OK) {
+        frame_index_ = 0;
+        sent_transforms_ = true;
+        return true;
+      }
+      // (a matrix that is not finite is refused: the vertices go the ordinary way below)
+    }
+  }
   const scene::FlatScene flat = scene::Flatten(sd);
   const bool same = built_ && built_dynamic_ && flat.positions.size() / 3 == built_verts_ &&
                     flat.spheres.size() / 4 == built_spheres_ && flat.indices == built_indices_ &&
@@ -78,7 +111,7 @@ bool HipBackend::update(const scene::SceneDesc& sd) {
     }
     // (a scene built with split references cannot be refitted: built again below)
   }
-  return buildFlat(flat);
+  return buildScene(sd, flat);
 }
 
 bool HipBackend::syncState() {

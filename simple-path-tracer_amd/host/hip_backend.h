@@ -51,6 +51,10 @@ class HipBackend {
     // sptr_set_dynamic, applied before build(): the build keeps what update() needs to refit the BVH in
     // place when only coordinates change
     bool dynamic = false;
+    // sptr_set_dynamic's SPTR_DYNAMIC_TRANSFORMS bit (implies dynamic), applied before build(): the build also
+    // sets the meshes' object-space vertices as the device's rest pose, and update() sends only the instances'
+    // matrices (and the spheres) when nothing else changed
+    bool transforms = false;
   };
   static constexpr uint32_t kLaggedCollect = 32;
   static constexpr uint32_t kDefaultMaxHistory = 4;  // lowest last-frame RMSE of the caps tried
@@ -64,8 +68,17 @@ class HipBackend {
   // The scene after a change: flattens as build() does; when the counts, the indices, the geometry order
   // and the material map equal the built scene's (and Settings::dynamic was set for that build), the new
   // coordinates are refitted in place (sptr_update_geometry), otherwise the scene is built again.  Either
-  // way the accumulation restarts.
+  // way the accumulation restarts.  With Settings::transforms, when in addition every mesh's vertices equal
+  // the built scene's (only worldFromObject or the spheres differ), the instances' matrices are sent instead of
+  // the vertices (sptr_update_transforms): 64 bytes per instance.
   bool update(const scene::SceneDesc& sceneDesc);
+  // sptr_tree_cost: the BVH2's cost and root area now and as the last build recorded them (0 without
+  // Settings::transforms); compare the first pair with the second to decide when build() would pay
+  bool treeCost(double* cost, double* root_area, double* cost_at_build, double* root_area_at_build) const {
+    return ctx_ && sptr_tree_cost(ctx_, cost, root_area, cost_at_build, root_area_at_build) == SPTR_OK;
+  }
+  // whether the last update() went through sptr_update_transforms
+  bool lastUpdateSentTransforms() const { return sent_transforms_; }
   // sptr_refit_info: refits since the last build, wall / device ms of the last one, excluded primitives
   bool refitInfo(uint32_t* refits, double* ms_wall, double* ms_device, uint32_t* excluded_prims) const {
     return ctx_ && sptr_refit_info(ctx_, refits, ms_wall, ms_device, excluded_prims) == SPTR_OK;
@@ -120,6 +133,7 @@ class HipBackend {
  private:
   bool ensureContext();
   bool buildFlat(const scene::FlatScene& flat);
+  bool buildScene(const scene::SceneDesc& sd, const scene::FlatScene& flat);
   bool syncState();
   bool renderInternal(int width, int height, const Camera& camera, bool async = false);
   void addStats(const sptr_stats& s);
@@ -141,6 +155,10 @@ class HipBackend {
   std::vector<uint32_t> built_indices_, built_geom_first_;
   size_t built_verts_ = 0, built_spheres_ = 0;
   bool built_dynamic_ = false;
+  // the rest pose the device holds (the built scene's object-space vertices in the flattening's order); empty:
+  // none, update() sends vertices
+  std::vector<float> built_rest_;
+  bool sent_transforms_ = false;
   std::string err_;
   int debug_mode_ = 0;
   uint32_t lanes_applied_ = 0;  // the pixel-lane setting the context holds

@@ -4,6 +4,8 @@
 // EmbreeBackend.cpp:32-193; glTF node/mesh walk GLTFLoader.cpp:24-65, 202-382.
 #include "scene_desc.h"
 
+#include "xform_point.h"
+
 #include <cmath>
 #include <cstring>
 #include <fstream>
@@ -48,14 +50,8 @@ mat4 multiply(const mat4& a, const mat4& b) {
   return r;
 }
 
-vec3 transform_point(const mat4& a, vec3 p) {
-  float o[3];
-  for (int k = 0; k < 3; ++k) {
-    const float m0 = a.m[0][k] * p.x, m1 = a.m[1][k] * p.y, m2 = a.m[2][k] * p.z, m3 = a.m[3][k] * 1.0f;
-    o[k] = (m0 + m1) + (m2 + m3);
-  }
-  return vec3{o[0], o[1], o[2]};
-}
+// (the arithmetic is csrc/xform_point.h's, which the device's transform pass calls too)
+vec3 transform_point(const mat4& a, vec3 p) { return sptr::xform_point(&a.m[0][0], p); }
 
 size_t SceneDesc::totalTriangles() const {
   size_t t = 0;
@@ -199,7 +195,17 @@ SceneDesc BuildTestTriangleScene() {
   return s;
 }
 
-FlatScene Flatten(const SceneDesc& s) {
+std::vector<float> InstanceMatrices(const SceneDesc& s) {
+  std::vector<float> out;
+  for (const InstanceData& in : s.instances) {
+    if (in.meshId >= s.meshes.size()) continue;  // (as Flatten: no geomID consumed)
+    const float* m = &in.worldFromObject.m[0][0];
+    out.insert(out.end(), m, m + 16);
+  }
+  return out;
+}
+
+FlatScene Flatten(const SceneDesc& s, bool object_space) {
   FlatScene f;
   f.tri_geom_first.push_back(0);
   for (const InstanceData& in : s.instances) {
@@ -210,7 +216,7 @@ FlatScene Flatten(const SceneDesc& s) {
     if (mat == kNoMaterial) mat = 0;
     const uint32_t base = uint32_t(f.positions.size() / 3);
     for (const vec3& p : m.positions) {
-      const vec3 w = transform_point(in.worldFromObject, p);
+      const vec3 w = object_space ? p : transform_point(in.worldFromObject, p);
       f.positions.insert(f.positions.end(), {w.x, w.y, w.z});
     }
     for (const uvec3& t : m.indices) f.indices.insert(f.indices.end(), {base + t.x, base + t.y, base + t.z});

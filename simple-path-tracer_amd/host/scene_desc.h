@@ -106,6 +106,10 @@ struct FlatScene {
   std::vector<uint32_t> geom_material;
   sptr_scene view() const;
 };
-FlatScene Flatten(const SceneDesc& s);
+// object_space: the same arrays with every instance's vertices left as its mesh holds them (the rest pose of
+// sptr_set_rest_positions, in the flattening's vertex order)
+FlatScene Flatten(const SceneDesc& s, bool object_space = false);
+// worldFromObject of the instances Flatten gives a geometry, in geomID order: 16 floats each, m[col][row]
+std::vector<float> InstanceMatrices(const SceneDesc& s);
 
 }  // namespace scene

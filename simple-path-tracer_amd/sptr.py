@@ -27,6 +27,8 @@ SPTR_FRAME_TIMING_TRACE = 16
 SPTR_FRAME_NO_CULL = 32
 SPTR_FRAME_RECULL = 64
 SPTR_UPDATE_DEVICE_PTRS = 1
+SPTR_DYNAMIC_REFIT = 1
+SPTR_DYNAMIC_TRANSFORMS = 2
 SPTR_QUERY_ANY_HIT = 1
 SPTR_QUERY_DEVICE_PTRS = 2
 SPTR_QUERY_SORT = 4
@@ -146,6 +148,7 @@ EXPORTS = [
     "sptr_set_seed_offset", "sptr_set_denoise_history", "sptr_read_history", "sptr_history_info",
     "sptr_set_history_motion", "sptr_read_motion", "sptr_motion_info",
     "sptr_set_dynamic", "sptr_update_geometry", "sptr_refit_info",
+    "sptr_set_rest_positions", "sptr_update_transforms", "sptr_tree_cost",
     "sptr_query_rays", "sptr_query_info",
     "sptr_host_builtin_scene", "sptr_host_scene_view", "sptr_host_scene_free", "sptr_host_camera_lookat",
     "sptr_host_preset_materials", "sptr_host_default_lights", "sptr_host_equirect_to_faces",
@@ -217,6 +220,9 @@ def lib() -> C.CDLL:
         "sptr_set_dynamic": (C.c_int, [vp, u32]),
         "sptr_update_geometry": (C.c_int, [vp, vp, u32, vp, u32, u32]),
         "sptr_refit_info": (C.c_int, [vp, up, C.POINTER(C.c_double), C.POINTER(C.c_double), up]),
+        "sptr_set_rest_positions": (C.c_int, [vp, vp, u32, u32]),
+        "sptr_update_transforms": (C.c_int, [vp, vp, u32, vp, u32, u32]),
+        "sptr_tree_cost": (C.c_int, [vp] + [C.POINTER(C.c_double)] * 4),
         "sptr_query_rays": (C.c_int, [vp, C.POINTER(RayQuery), vp]),
         "sptr_query_info": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), up, up]),
         "sptr_host_builtin_scene": (C.c_int, [C.c_char_p, u32, u32, C.POINTER(vp)]),
@@ -431,29 +437,59 @@ class Renderer:
         cs = s.to_c()
         self._check(self._L.sptr_upload_scene(self._h, C.byref(cs)), "upload_scene")
 
-    def set_dynamic(self, on: bool = True):
-        """sptr_set_dynamic: the next upload_scene keeps what update_geometry's refit needs."""
-        self._check(self._L.sptr_set_dynamic(self._h, 1 if on else 0), "set_dynamic")
+    def set_dynamic(self, on: bool = True, transforms: bool = False):
+        """sptr_set_dynamic: the next upload_scene keeps what update_geometry's refit needs; with transforms
+        (SPTR_DYNAMIC_TRANSFORMS) also the rest pose update_transforms moves, and it records its tree cost."""
+        v = (SPTR_DYNAMIC_REFIT if on or transforms else 0) | (SPTR_DYNAMIC_TRANSFORMS if transforms else 0)
+        self._check(self._L.sptr_set_dynamic(self._h, v), "set_dynamic")
+
+    @staticmethod
+    def _coord_args(what, arrays, device):
+        """[(array or None, columns)] -> addresses, row counts and the host copies to keep alive."""
+        ptr, cnt, keep = [None] * len(arrays), [0] * len(arrays), []
+        for k, (a, cols) in enumerate(arrays):
+            if a is None:
+                continue
+            if device:
+                if a.numel() % cols or not a.is_contiguous() or a.element_size() != 4:
+                    raise SptrError(f"{what}: device arrays must be contiguous float32")
+                ptr[k], cnt[k] = C.c_void_p(a.data_ptr()), a.numel() // cols
+            else:
+                h = np.ascontiguousarray(a, np.float32).reshape(-1, cols)
+                keep.append(h)
+                ptr[k], cnt[k] = C.c_void_p(h.ctypes.data), len(h)
+        return ptr, cnt, keep
 
     def update_geometry(self, positions=None, spheres=None, device: bool = False):
         """sptr_update_geometry: new coordinates for the uploaded topology, refitted in place.  positions
         (V, 3) and spheres (S, 4) float32, or None for unchanged; with device=True they are contiguous
         float32 tensors on this context's GPU (anything with data_ptr() and numel()).  Restart the
         accumulation (frame_begin=1) afterwards."""
-        ptr, cnt, keep = [None, None], [0, 0], []
-        for k, (a, cols) in enumerate(((positions, 3), (spheres, 4))):
-            if a is None:
-                continue
-            if device:
-                if a.numel() % cols or not a.is_contiguous() or a.element_size() != 4:
-                    raise SptrError("update_geometry: device arrays must be contiguous float32")
-                ptr[k], cnt[k] = C.c_void_p(a.data_ptr()), a.numel() // cols
-            else:
-                h = np.ascontiguousarray(a, np.float32).reshape(-1, cols)
-                keep.append(h)
-                ptr[k], cnt[k] = C.c_void_p(h.ctypes.data), len(h)
+        ptr, cnt, keep = self._coord_args("update_geometry", ((positions, 3), (spheres, 4)), device)
         self._check(self._L.sptr_update_geometry(self._h, ptr[0], cnt[0], ptr[1], cnt[1],
                                                  SPTR_UPDATE_DEVICE_PTRS if device else 0), "update_geometry")
+
+    def set_rest_positions(self, positions, device: bool = False):
+        """sptr_set_rest_positions: the vertices update_transforms moves, (V, 3) float32 (object space, in the
+        upload's vertex order), instead of the uploaded positions."""
+        ptr, cnt, keep = self._coord_args("set_rest_positions", ((positions, 3),), device)
+        self._check(self._L.sptr_set_rest_positions(self._h, ptr[0], cnt[0], SPTR_UPDATE_DEVICE_PTRS if device else 0),
+                    "set_rest_positions")
+
+    def update_transforms(self, xforms=None, spheres=None, device: bool = False):
+        """sptr_update_transforms: one glm-layout mat4 per triangle geometry, (G, 4, 4) float32 with
+        xforms[g][col][row], applied to the rest pose on the device, and / or new spheres (S, 4); None for
+        unchanged.  Needs set_dynamic(transforms=True) before the upload.  Restart the accumulation afterwards."""
+        ptr, cnt, keep = self._coord_args("update_transforms", ((xforms, 16), (spheres, 4)), device)
+        self._check(self._L.sptr_update_transforms(self._h, ptr[0], cnt[0], ptr[1], cnt[1],
+                                                   SPTR_UPDATE_DEVICE_PTRS if device else 0), "update_transforms")
+
+    def tree_cost(self) -> dict:
+        """sptr_tree_cost: the BVH2's cost (sum of weight x child box area) and root area now, and as the upload
+        recorded them (0 without set_dynamic(transforms=True))."""
+        v = [C.c_double() for _ in range(4)]
+        self._check(self._L.sptr_tree_cost(self._h, *[C.byref(d) for d in v]), "tree_cost")
+        return dict(zip(("cost", "root_area", "cost_at_upload", "root_area_at_upload"), (d.value for d in v)))
 
     def refit_info(self) -> dict:
         """Refits since the upload, wall / device ms of the last one, and the triangles left out of the tree

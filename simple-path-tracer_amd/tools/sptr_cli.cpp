@@ -5,7 +5,7 @@
 //   sptr_cli [--scene default|default_emitter|test_triangle|sphere_mesh:STACKS:SLICES|gltf:PATH]
 //            [--w 800] [--h 600] [--spp 4] [--depth 6] [--env sky|FILE.hdr] [--out image.ppm]
 //            [--warmup N] [--json] [--integrator wavefront|pathtracer|optix] [--spf 4] [--launch-mode 0-3]
-//            [--lagged] [--denoise N] [--history [M]] [--motion] [--orbit DEG] [--animate K [--rebuild]] [--query-centre-rays]
+//            [--lagged] [--denoise N] [--history [M]] [--motion] [--orbit DEG] [--animate K [--rebuild] [--rigid]] [--query-centre-rays]
 // --spp N renders N progressive frames of 1 spp each (GLRenderer's m_accumulated_samples loop);
 // --warmup N renders N untimed frames first (then restarts the accumulation by a camera change);
 // --json prints one line with per-frame wall-clock statistics (render + RGB8 read back, as the
@@ -25,6 +25,12 @@
 // place: Settings::dynamic) and the accumulation restarts; the last frame is written.  --rebuild: the same
 // loop through HipBackend::build instead.  The --json line adds refits, the mean ms_refit_wall /
 // ms_refit_device of the updates and the mean ms_build of the rebuild loop's builds.
+// --rigid (with --animate K): every instance also moves rigidly, animation frame k's matrix made from its first
+// one (a turn about +Y and a translation), and the scene is built with Settings::transforms, so that update()
+// sends the matrices and the device moves the kept rest pose (sptr_update_transforms); without --rigid an
+// update sends every vertex.  The --json line reports transform_updates (the updates that went that way) and,
+// for every run, the tree's cost and root area after the last update and as built (sptr_tree_cost; the built
+// figures are 0 unless --rigid kept them).
 // --motion: HipBackend::Settings::motion, meaningful with --animate K --denoise N --history: the updates keep the
 // history, read through a snapshot of the geometry it saw; the --json line's snapshots / ms_snapshot are the
 // snapshots taken and the mean device time of one.
@@ -65,7 +71,7 @@ static bool build_scene(const std::string& s, scene::SceneDesc& sd, MaterialMana
 int main(int argc, char** argv) {
   std::string scene_name = "default", env = "sky", out = "image.ppm";
   int w = 800, h = 600, spp = 4, depth = 6, warmup = 0;
-  bool json = false, lagged = false, rebuild = false, query_centre = false, motion = false;
+  bool json = false, lagged = false, rebuild = false, query_centre = false, motion = false, rigid = false;
   int animate = 0;
   std::string integrator = "wavefront";
   int spf = 4, launch_mode = 0, denoise = 0, history = 0;
@@ -94,9 +100,10 @@ int main(int argc, char** argv) {
     else if (a == "--orbit") orbit = std::atof(next());
     else if (a == "--animate") animate = std::atoi(next());
     else if (a == "--rebuild") rebuild = true;
+    else if (a == "--rigid") rigid = true;
     else if (a == "--query-centre-rays") query_centre = true;
     else {
-      std::fprintf(stderr, "usage: %s [--scene S] [--w W] [--h H] [--spp N] [--depth D] [--env sky|F.hdr] [--out F] [--warmup N] [--json] [--lagged] [--denoise N] [--history [M]] [--motion] [--orbit DEG] [--animate K [--rebuild]] [--query-centre-rays]\n",
+      std::fprintf(stderr, "usage: %s [--scene S] [--w W] [--h H] [--spp N] [--depth D] [--env sky|F.hdr] [--out F] [--warmup N] [--json] [--lagged] [--denoise N] [--history [M]] [--motion] [--orbit DEG] [--animate K [--rebuild] [--rigid]] [--query-centre-rays]\n",
                    argv[0]);
       return 2;
     }
@@ -134,6 +141,7 @@ int main(int argc, char** argv) {
   st.history.max_history = uint32_t(std::max(0, history));
   st.motion = motion;
   st.dynamic = animate > 0 && !rebuild;
+  st.transforms = st.dynamic && rigid;
   be.setSettings(st);
   if (!be.build(sd)) {
     std::fprintf(stderr, "%s\n", be.lastError().c_str());
@@ -153,6 +161,9 @@ int main(int argc, char** argv) {
   double ms_refit_wall = 0.0, ms_refit_device = 0.0, ms_build = 0.0, ms_snapshot = 0.0;
   uint32_t refits = 0, snapshots = 0;
   int moves = 0;
+  std::vector<scene::mat4> instance0;
+  for (const scene::InstanceData& in : sd.instances) instance0.push_back(in.worldFromObject);
+  int sent_transforms = 0;
   const auto t0 = std::chrono::steady_clock::now();
   const int shots = std::max(1, animate), total_frames = shots * spp;
   for (int f = 0; f < total_frames; ++f) {
@@ -161,6 +172,17 @@ int main(int argc, char** argv) {
         const float fi = float(i);
         sd.spheres[i].center = sd.spheres[i].center +
                                vec3{0.06f * std::sin(1.7f * fi), 0.04f * float(i % 3), 0.05f * std::cos(2.3f * fi)};
+      }
+      if (rigid) {  // ... and the instances: animation frame k's matrix from the first one, nothing accumulates
+        const float k = float(f / spp);
+        for (size_t i = 0; i < sd.instances.size(); ++i) {
+          const float fi = float(i), a = 0.12f * k * (fi + 1.0f);
+          scene::mat4 rot = scene::mat4::identity();  // about +Y through the instance's own origin
+          rot.m[0][0] = std::cos(a), rot.m[0][2] = -std::sin(a), rot.m[2][0] = std::sin(a), rot.m[2][2] = std::cos(a);
+          const scene::mat4 move = scene::translate(
+              scene::mat4::identity(), vec3{0.08f * k * std::sin(1.3f * fi + 0.5f), 0.05f * k, 0.06f * k * std::cos(0.7f * fi)});
+          sd.instances[i].worldFromObject = scene::multiply(move, scene::multiply(instance0[i], rot));
+        }
       }
       if (!(rebuild ? be.build(sd) : be.update(sd))) {
         std::fprintf(stderr, "%s\n", be.lastError().c_str());
@@ -174,6 +196,7 @@ int main(int argc, char** argv) {
         (void)be.refitInfo(&refits, &mw, &md, nullptr);
         ms_refit_wall += mw;
         ms_refit_device += md;
+        if (be.lastUpdateSentTransforms()) ++sent_transforms;
         uint32_t sn = 0;
         double msn = 0.0;
         if (motion && be.motionInfo(&sn, &msn, nullptr) && sn != snapshots) {
@@ -250,6 +273,12 @@ int main(int argc, char** argv) {
                 moves && !rebuild ? ms_refit_wall / moves : 0.0, moves && !rebuild ? ms_refit_device / moves : 0.0,
                 moves && rebuild ? ms_build / moves : 0.0,
                 lagged ? "sptr_read_rgb8_lagged" : "sptr_read_rgb8");
+    // the tree after the last update against the tree as built (the latter 0 unless --rigid kept the figures)
+    double tc[4] = {0.0, 0.0, 0.0, 0.0};
+    (void)be.treeCost(&tc[0], &tc[1], &tc[2], &tc[3]);
+    std::printf(", \"rigid\": %d, \"transform_updates\": %d, \"tree_cost\": %.17g, \"root_area\": %.17g, "
+                "\"tree_cost_at_build\": %.17g, \"root_area_at_build\": %.17g",
+                rigid ? 1 : 0, sent_transforms, tc[0], tc[1], tc[2], tc[3]);
     if (query_centre) std::printf(", \"query\": {\"rays\": %zu, \"hits\": %zu, \"tri_hits\": %zu}", q_rays, q_hits, q_tri_hits);
     std::printf("}\n");
   } else {
