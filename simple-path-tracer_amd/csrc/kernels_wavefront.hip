@@ -962,10 +962,14 @@ struct Staged {
   const uint32_t* prim_ref;
   const float4* tris;
   const float4* sph;
+  // primitive slot -> material index (ShadeView::prim_mat): the copy staged beside the scene (pm_lds;
+  // stage_shaded), else the table in global memory; set in the kernels that shade with kShadeFused
+  const uint32_t* pm;
+  bool pm_lds;
 };
 template <bool kLds>
 __device__ __forceinline__ Staged stage_scene(const SceneView& sv, float4* lds) {
-  Staged s{sv.nodes, sv.nodes4, sv.prim_ref, sv.tris, sv.sph};
+  Staged s{sv.nodes, sv.nodes4, sv.prim_ref, sv.tris, sv.sph, nullptr, false};
   if (kLds) {
     const bool w4 = sv.width == (uint32_t)kWide;
     const uint32_t nn = (w4 ? sv.num_nodes4 * (uint32_t)sizeof(WideNode) : sv.num_nodes * (uint32_t)sizeof(BvhNode)) / 16u,
@@ -983,6 +987,25 @@ __device__ __forceinline__ Staged stage_scene(const SceneView& sv, float4* lds) 
     s.tris = lds + nn;
     s.sph = lds + nn + nt;
     s.prim_ref = reinterpret_cast<const uint32_t*>(lds + nn + nt + ns);
+  }
+  return s;
+}
+
+// stage_scene<true> of a fused bounce kernel.  kTable (the kernel shades with kShadeFused): the material table of
+// the primitive slots is copied to LDS behind the scene, sh.pm_lds_bytes of the kernel's dynamic LDS; 0 when it
+// does not fit, and the global table, one independent load, serves.  stage_scene's barrier publishes both.
+template <bool kTable>
+__device__ __forceinline__ Staged stage_shaded(const SceneView& sv, const ShadeView& sh, float4* lds) {
+  const bool tab = kTable && sh.pm_lds_bytes != 0u;
+  float4* dst = lds + sv.lds_bytes / 16u;
+  if (tab) {
+    const float4* g = reinterpret_cast<const float4*>(sh.prim_mat);
+    for (uint32_t i = threadIdx.x; i < sh.pm_lds_bytes / 16u; i += blockDim.x) dst[i] = g[i];
+  }
+  Staged s = stage_scene<true>(sv, lds);
+  if (kTable) {
+    s.pm = tab ? reinterpret_cast<const uint32_t*>(dst) : sh.prim_mat;
+    s.pm_lds = tab;
   }
   return s;
 }
@@ -2297,25 +2320,62 @@ struct Surface {
   vec3 P, n;      // hit point, face-forwarded normal
   DevMaterial m;  // MaterialManager::getMaterialFromHit
 };
-__device__ __forceinline__ Surface surface_at(const SceneView& sv, const ShadeView& sh, const DevMaterial* smat,
-                                              uint32_t nm, vec3 ro, vec3 rd, float t, uint32_t ref) {
+// Loads through a pointer whose address space is stated.  A generic pointer that is an LDS address on one side
+// of a uniform branch and a global one on the other is merged by the compiler into one flat load of a selected
+// address, which waits for both memory counters; stated, each side keeps its own instruction.
+typedef const uint32_t __attribute__((address_space(3))) * LdsWords;
+typedef const uint32_t __attribute__((address_space(1))) * GlobalWords;
+__device__ __forceinline__ uint32_t lds_word(const uint32_t* p) { return *(LdsWords)p; }
+__device__ __forceinline__ uint32_t global_word(const uint32_t* p) { return *(GlobalWords)p; }
+__device__ __forceinline__ DevMaterial lds_material(const DevMaterial* m) {
+  static_assert(sizeof(DevMaterial) == 12 * sizeof(uint32_t), "material words");
+  const uint32_t* w = reinterpret_cast<const uint32_t*>(m);
+  uint32_t v[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) v[i] = lds_word(w + i);
+  DevMaterial out;
+  __builtin_memcpy(&out, v, sizeof(out));
+  return out;
+}
+// Where surface_at reads from.  kShadeGlobal, the code every kernel ran before the slot table: the global
+// arrays, the geomID's material, the material through a select of smat and sh.mats.  kShadeFused, the fused bounce
+// kernels (they always have a table: shade_fuses_shadows): the primitive from sc, the LDS copy; the material
+// index from the slot table (sc.pm), one load that depends on ref alone; with at most 32 materials (uniform) the
+// material by LDS reads.  tri_geom, sph_geom and geom_mat hold no registers there.
+// Three slot-timed instantiations (SPTR_FRAME_TIMING_TRACE) keep kShadeGlobal: at the 80-VGPR bound with the time
+// slot live, kShadeFused spilled two more VGPRs in k_shade_trace<cube, later, timed> (0 -> 2, scratch 728 ->
+// 736 B) and in k_bounce_chain<., timed> (10 -> 12, 5 -> 7); bench.py's timed pass (no cubemap, no chain) runs
+// none of them.  Same values either way.
+enum ShadeFrom { kShadeGlobal = 0, kShadeFused = 1 };
+template <int kFrom>
+__device__ __forceinline__ Surface surface_at(const Staged& sc, const SceneView& sv, const ShadeView& sh,
+                                              const DevMaterial* smat, uint32_t nm, vec3 ro, vec3 rd, float t, uint32_t ref) {
   Surface s;
   s.P = ro + t * rd;
   const uint32_t idx = ref & kIndexMask;
+  const bool sphere = (ref & kSphereBit) != 0u;
+  const float4* sph = kFrom == kShadeGlobal ? sv.sph : sc.sph;
+  const float4* tris = kFrom == kShadeGlobal ? sv.tris : sc.tris;
   vec3 ng;
-  uint32_t mid;
-  if (ref & kSphereBit) {
-    const float4 c = sv.sph[idx];
+  uint32_t mid = 0u;
+  constexpr bool have_mid = kFrom == kShadeFused;
+  if constexpr (have_mid) {
+    const uint32_t pslot = prim_mat_slot(sv.num_tris, sphere, idx);
+    mid = sc.pm_lds ? lds_word(sc.pm + pslot) : global_word(sc.pm + pslot);
+  }
+  if (sphere) {
+    const float4 c = sph[idx];
     ng = v3((s.P.x - c.x) / c.w, (s.P.y - c.y) / c.w, (s.P.z - c.z) / c.w);
-    mid = sh.geom_mat[sv.sph_geom[idx]];
+    if (!have_mid) mid = sh.geom_mat[sv.sph_geom[idx]];
   } else {
-    const float4 c = sv.tris[3 * idx + 2];
+    const float4 c = tris[3 * idx + 2];
     ng = v3(c.y, c.z, c.w);
-    mid = sh.tri_mat ? sh.tri_mat[idx] : sh.geom_mat[sv.tri_geom[idx]];
+    if (!have_mid) mid = sh.tri_mat ? sh.tri_mat[idx] : sh.geom_mat[sv.tri_geom[idx]];
   }
   s.n = safe_normalize(ng);
   if (dot(s.n, rd) > 0.0f) s.n = -s.n;
-  s.m = (mid < nm) ? smat[mid] : sh.mats[mid];
+  if (kFrom != kShadeGlobal && sh.num_mats <= 32u) s.m = lds_material(smat + mid);  // (mid < num_mats: resolve_geom_materials)
+  else s.m = (mid < nm) ? smat[mid] : sh.mats[mid];
   return s;
 }
 
@@ -2468,6 +2528,7 @@ __global__ void __launch_bounds__(kBlock, SPTR_SHADE_WAVES)
     w.work[kWorkTraceQueue + threadIdx.x * 32u] = 0u;                 // k_trace_dyn's, for the next bounce
   }
   const Staged sc = stage_scene<kFuse>(sv, lds);
+  constexpr int kFrom = kShadeGlobal;
   Visits vc;
   uint32_t rays = 0u;
   uint32_t per_in = 0u;
@@ -2517,7 +2578,7 @@ __global__ void __launch_bounds__(kBlock, SPTR_SHADE_WAVES)
         radv = v3(1.0f, 1.0f, 1.0f);
         dirty = true;
       } else {
-        sf = surface_at(sv, sh, smat, nm, ro, rd, __uint_as_float(h.y), h.z);
+        sf = surface_at<kFrom>(sc, sv, sh, smat, nm, ro, rd, __uint_as_float(h.y), h.z);
         const vec3 emission = v3(sf.m.emission[0], sf.m.emission[1], sf.m.emission[2]);
         if (dot(emission, emission) > 0.0f) {
           if (!kPrimary) radv = xyz(w.rad[p]);
@@ -2626,7 +2687,7 @@ __global__ void __launch_bounds__(kBlock, SPTR_SHADE_WAVES)
 // bounce_ray is the per-ray body, shared with k_bounce_chain's later phases: the ray of slot id of rin
 // (valid: this thread holds one), its continuation appended to the block's segment [seg0, ..) of rout
 // through the LDS counter s_cnt.  Every lane of the wave calls it together (block_append ballots).
-template <bool kCube>
+template <bool kCube, int kFrom>
 __device__ __forceinline__ void bounce_ray(const Staged& sc, const SceneView& sv, const ShadeView& sh, const DevMaterial* smat,
                                            uint32_t nm, const WaveView& w, const RayStream& rin, const RayStream& rout,
                                            int depth, bool last, bool valid, uint32_t id, uint32_t seg0, uint32_t* s_cnt,
@@ -2654,7 +2715,7 @@ __device__ __forceinline__ void bounce_ray(const Staged& sc, const SceneView& sv
       radv = v3(1.0f, 1.0f, 1.0f);
       dirty = true;
     } else {
-      const Surface sf = surface_at(sv, sh, smat, nm, ro, rd, tfar, ref);
+      const Surface sf = surface_at<kFrom>(sc, sv, sh, smat, nm, ro, rd, tfar, ref);
       const vec3 emission = v3(sf.m.emission[0], sf.m.emission[1], sf.m.emission[2]);
       if (dot(emission, emission) > 0.0f) {
         radv = xyz(w.rad[p]) + thr * emission;
@@ -2692,13 +2753,14 @@ __global__ void __launch_bounds__(kBlock, SPTR_BOUNCE_WAVES)
   if constexpr (kTimed) ktime_begin(w);
   const FrameView f = frame_dyn(fin);
   extern __shared__ float4 lds[];
-  uint32_t* s_off = reinterpret_cast<uint32_t*>(lds + sv.lds_bytes / 16u);
+  uint32_t* s_off = reinterpret_cast<uint32_t*>(lds + (sv.lds_bytes + sh.pm_lds_bytes) / 16u);
   __shared__ DevMaterial smat[32];
   __shared__ uint32_t s_cnt_n, s_rays;
   __shared__ LdsStack s_stack;
   const uint32_t nm = stage_materials(sh, smat);
   if (threadIdx.x == 0) s_cnt_n = s_rays = 0u;
-  const Staged sc = stage_scene<true>(sv, lds);
+  constexpr int kFrom = kShadeFused;
+  const Staged sc = stage_shaded<kFrom == kShadeFused>(sv, sh, lds);
   uint32_t per_in = 0u;
   const uint32_t n = seg_scan(w.segN, nseg_in, s_off, per_in);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -2715,7 +2777,7 @@ __global__ void __launch_bounds__(kBlock, SPTR_BOUNCE_WAVES)
     const uint32_t i = base + threadIdx.x;
     const bool valid = i < n;
     const uint32_t id = valid ? seg_slot(s_off, nseg_in, per_in, i) : 0u;
-    bounce_ray<kCube>(sc, sv, sh, smat, nm, w, rin, rout, depth, last, valid, id, sd.seg0, &s_cnt_n, vc, s_stack, rays);
+    bounce_ray<kCube, kFrom>(sc, sv, sh, smat, nm, w, rin, rout, depth, last, valid, id, sd.seg0, &s_cnt_n, vc, s_stack, rays);
   }
   for (int off = 32; off > 0; off >>= 1) rays += __shfl_xor(rays, off);
   if (lane_id() == 0u) atomicAdd(&s_rays, rays);
@@ -2744,7 +2806,7 @@ __global__ void __launch_bounds__(kBlock, SPTR_BOUNCE_WAVES)
 // bounce01_path is the per-path body, shared with k_bounce_chain's first phase: the bounce-0 hit record of
 // slot `slot` (valid: this thread holds one), its bounce-2 ray appended to the block's segment [seg0, ..) of
 // rout through the LDS counter s_cnt.  Every lane of the wave calls it together (block_append ballots).
-template <bool kCube>
+template <bool kCube, int kFrom>
 __device__ __forceinline__ void bounce01_path(const Staged& sc, const SceneView& sv, const ShadeView& sh, const DevMaterial* smat,
                                               uint32_t nm, const FrameView& f, const ImageDiv& idiv, const WaveView& w,
                                               const RayStream& rout, bool last1, bool last2, bool valid, uint32_t slot,
@@ -2764,7 +2826,7 @@ __device__ __forceinline__ void bounce01_path(const Staged& sc, const SceneView&
       radv = v3(1.0f, 1.0f, 1.0f);
       active = false;
     } else {
-      const Surface sf = surface_at(sv, sh, smat, nm, f.cam_pos, pr.d, __uint_as_float(h.y), h.z);
+      const Surface sf = surface_at<kFrom>(sc, sv, sh, smat, nm, f.cam_pos, pr.d, __uint_as_float(h.y), h.z);
       const vec3 emission = v3(sf.m.emission[0], sf.m.emission[1], sf.m.emission[2]);
       if (dot(emission, emission) > 0.0f) radv = radv + thr * emission;
       vec3 so, ldir, contrib;
@@ -2788,7 +2850,7 @@ __device__ __forceinline__ void bounce01_path(const Staged& sc, const SceneView&
     if (!traverse_w<false, false, false>(sc, sv, make_ray(ro, rd), 0.0f, tfar, ref, vc, s_stack)) {
       radv = radv + thr * env_color<kCube>(sh.env, renormalized_again(rd));
     } else {
-      const Surface sf = surface_at(sv, sh, smat, nm, ro, rd, tfar, ref);
+      const Surface sf = surface_at<kFrom>(sc, sv, sh, smat, nm, ro, rd, tfar, ref);
       const vec3 emission = v3(sf.m.emission[0], sf.m.emission[1], sf.m.emission[2]);
       if (dot(emission, emission) > 0.0f) radv = radv + thr * emission;
       if (light_faces(sh.lights[0], sf)) lit = light_term(sh.lights[0], sf, -rd, thr, so, ldir, stfar, contrib);
@@ -2821,13 +2883,14 @@ __global__ void __launch_bounds__(kBlock, SPTR_BOUNCE01_WAVES)
   if constexpr (kTimed) ktime_begin(w);
   const FrameView f = frame_dyn(fin);
   extern __shared__ float4 lds[];
-  uint32_t* s_off = reinterpret_cast<uint32_t*>(lds + sv.lds_bytes / 16u);
+  uint32_t* s_off = reinterpret_cast<uint32_t*>(lds + (sv.lds_bytes + sh.pm_lds_bytes) / 16u);
   __shared__ DevMaterial smat[32];
   __shared__ uint32_t s_cnt_n, s_rays, s_traced;
   __shared__ LdsStack s_stack;
   const uint32_t nm = stage_materials(sh, smat);
   if (threadIdx.x == 0) s_cnt_n = s_rays = s_traced = 0u;
-  const Staged sc = stage_scene<true>(sv, lds);
+  constexpr int kFrom = kShadeFused;
+  const Staged sc = stage_shaded<kFrom == kShadeFused>(sv, sh, lds);
   uint32_t per_in = 0u;
   const uint32_t n = seg_scan(w.segH, nseg_in, s_off, per_in);
   const RayStream rout = w.rs[0];
@@ -2840,7 +2903,7 @@ __global__ void __launch_bounds__(kBlock, SPTR_BOUNCE01_WAVES)
     const uint32_t i = base + threadIdx.x;
     const bool valid = i < n;
     const uint32_t slot = valid ? seg_slot(s_off, nseg_in, per_in, i) : 0u;
-    bounce01_path<kCube>(sc, sv, sh, smat, nm, f, idiv, w, rout, last1, last2, valid, slot, sd.seg0, &s_cnt_n, vc, s_stack, rays,
+    bounce01_path<kCube, kFrom>(sc, sv, sh, smat, nm, f, idiv, w, rout, last1, last2, valid, slot, sd.seg0, &s_cnt_n, vc, s_stack, rays,
                          traced);
   }
   for (int off = 32; off > 0; off >>= 1) {
@@ -2901,13 +2964,14 @@ __global__ void __launch_bounds__(kBlock, SPTR_CHAIN_WAVES)
   if constexpr (kTimed) ktime_begin(w);
   const FrameView f = frame_dyn(fin);
   extern __shared__ float4 lds[];
-  uint32_t* s_off = reinterpret_cast<uint32_t*>(lds + sv.lds_bytes / 16u);
+  uint32_t* s_off = reinterpret_cast<uint32_t*>(lds + (sv.lds_bytes + sh.pm_lds_bytes) / 16u);
   __shared__ DevMaterial smat[32];
   __shared__ uint32_t s_cnt[3], s_rays, s_traced;
   __shared__ LdsStack s_stack;
   const uint32_t nm = stage_materials(sh, smat);
   if (threadIdx.x == 0) s_cnt[0] = s_cnt[1] = s_cnt[2] = s_rays = s_traced = 0u;
-  const Staged sc = stage_scene<true>(sv, lds);
+  constexpr int kFrom = kTimed ? kShadeGlobal : kShadeFused;  // (ShadeFrom)
+  const Staged sc = stage_shaded<kFrom == kShadeFused>(sv, sh, lds);
   uint32_t per_in = 0u;
   const uint32_t n = seg_scan(w.segH, nseg_in, s_off, per_in);
   const bool last1 = 1u >= f.max_depth, last2 = 2u >= f.max_depth;
@@ -2921,7 +2985,7 @@ __global__ void __launch_bounds__(kBlock, SPTR_CHAIN_WAVES)
       const uint32_t i = base + threadIdx.x;
       const bool valid = i < n;
       const uint32_t slot = valid ? seg_slot(s_off, nseg_in, per_in, i) : 0u;
-      bounce01_path<kCube>(sc, sv, sh, smat, nm, f, idiv, w, rout, last1, last2, valid, slot, sd.seg0, &s_cnt[1], vc, s_stack,
+      bounce01_path<kCube, kFrom>(sc, sv, sh, smat, nm, f, idiv, w, rout, last1, last2, valid, slot, sd.seg0, &s_cnt[1], vc, s_stack,
                            rays, traced);
     }
   }
@@ -2939,7 +3003,7 @@ __global__ void __launch_bounds__(kBlock, SPTR_CHAIN_WAVES)
     for (uint32_t j = 0u; j < cnt; j += kBlock) {
       const uint32_t id = sd.seg0 + j + threadIdx.x;
       const bool valid = j + threadIdx.x < cnt && id < w.seg_cap;  // (an overflowing append was reported, not written)
-      bounce_ray<kCube>(sc, sv, sh, smat, nm, w, rin, rout, d, last, valid, id, sd.seg0, &s_cnt[d % 3], vc, s_stack, rays);
+      bounce_ray<kCube, kFrom>(sc, sv, sh, smat, nm, w, rin, rout, d, last, valid, id, sd.seg0, &s_cnt[d % 3], vc, s_stack, rays);
     }
   }
   for (int off = 32; off > 0; off >>= 1) {
@@ -2992,6 +3056,13 @@ __global__ void __launch_bounds__(kBlock, SPTR_CHAIN_WAVES)
 // contribution(d - 1) if unoccluded, thr * env(d) on a miss — with the same operands, so rad[], the images
 // and every tally are those of k_trace / k_shade / k_shadow and of bounce01_path / bounce_ray.
 //
+// What a record's shading reads after the record itself comes from LDS (surface_at<kShadeFused>): the primitive from the
+// staged scene, its material index from the slot table staged behind the scene (stage_shaded; from the global
+// table, one load, when it does not fit), the material from smat.  The parent read the global primitive and
+// geomID, then geom_mat, then the material through a flat load: four dependent memory round trips per record
+// ahead of the shading.  Measured: DESIGN.md §4 "Shading from the staged scene", profiles/r11_lds_shading_ab.txt.
+// rad[p] is still read at the first addition: reading it with the record did not separate.
+//
 // Waves per SIMD (C2, two lanes, ms/step, builds alternated on one box, three runs each; this build
 // 2.170-2.174; profiles/r08_bounce_order_ab.txt): no instantiation spills a VGPR at its bound.
 #ifndef SPTR_ST_FIRST_WAVES
@@ -3021,7 +3092,7 @@ __device__ __forceinline__ void shadow_add(const Staged& sc, const SceneView& sv
 // The per-record body: the record of slot `slot` (valid: this thread holds one), its output appended to the
 // block's segment [seg0, ..) of rout through the LDS counter s_cnt.  Every lane of the wave calls it together
 // (block_append ballots).  depth: the bounce traced; last: depth is the path's last bounce.
-template <bool kCube, bool kFirst, bool kClose>
+template <bool kCube, bool kFirst, bool kClose, int kFrom>
 __device__ __forceinline__ void shade_trace(const Staged& sc, const SceneView& sv, const ShadeView& sh, const DevMaterial* smat,
                                             uint32_t nm, const FrameView& f, const ImageDiv& idiv, const WaveView& w,
                                             const RayStream& rin, const RayStream& rout, int depth, bool last, bool valid,
@@ -3058,7 +3129,7 @@ __device__ __forceinline__ void shade_trace(const Staged& sc, const SceneView& s
       radv = v3(1.0f, 1.0f, 1.0f);
       dirty = true;
     } else {
-      const Surface sf = surface_at(sv, sh, smat, nm, ro, rd, t, ref);
+      const Surface sf = surface_at<kFrom>(sc, sv, sh, smat, nm, ro, rd, t, ref);
       const vec3 emission = v3(sf.m.emission[0], sf.m.emission[1], sf.m.emission[2]);
       if (dot(emission, emission) > 0.0f) rad_add(w, p, dirty, radv, thr * emission);
       if (light_faces(sh.lights[0], sf)) lit = light_term(sh.lights[0], sf, -rd, thr, so, ldir, stfar, contrib);
@@ -3091,7 +3162,7 @@ __device__ __forceinline__ void shade_trace(const Staged& sc, const SceneView& s
     vec3 no2, nd2;
     lit = false;
     if (hit) {
-      const Surface sf = surface_at(sv, sh, smat, nm, no, nd, tfar, href);
+      const Surface sf = surface_at<kFrom>(sc, sv, sh, smat, nm, no, nd, tfar, href);
       const vec3 emission = v3(sf.m.emission[0], sf.m.emission[1], sf.m.emission[2]);
       if (dot(emission, emission) > 0.0f) rad_add(w, p, dirty, radv, thr * emission);
       if (light_faces(sh.lights[0], sf)) lit = light_term(sh.lights[0], sf, -nd, thr, so, ldir, stfar, contrib);
@@ -3118,13 +3189,14 @@ __global__ void __launch_bounds__(kBlock, kClose ? SPTR_ST_CLOSE_WAVES : (kFirst
   if constexpr (kTimed) ktime_begin(w);
   const FrameView f = frame_dyn(fin);
   extern __shared__ float4 lds[];
-  uint32_t* s_off = reinterpret_cast<uint32_t*>(lds + sv.lds_bytes / 16u);
+  uint32_t* s_off = reinterpret_cast<uint32_t*>(lds + (sv.lds_bytes + sh.pm_lds_bytes) / 16u);
   __shared__ DevMaterial smat[32];
   __shared__ uint32_t s_cnt_n, s_rays, s_traced;
   __shared__ LdsStack s_stack;
   const uint32_t nm = stage_materials(sh, smat);
   if (threadIdx.x == 0) s_cnt_n = s_rays = s_traced = 0u;
-  const Staged sc = stage_scene<true>(sv, lds);
+  constexpr int kFrom = (kTimed && kCube && !kFirst && !kClose) ? kShadeGlobal : kShadeFused;  // (ShadeFrom)
+  const Staged sc = stage_shaded<kFrom == kShadeFused>(sv, sh, lds);
   const SegTable tin = kFirst ? w.segH : w.segN, tout = kFirst ? w.segN : w.segH;
   uint32_t per_in = 0u;
   const uint32_t n = seg_scan(tin, nseg_in, s_off, per_in);
@@ -3138,7 +3210,7 @@ __global__ void __launch_bounds__(kBlock, kClose ? SPTR_ST_CLOSE_WAVES : (kFirst
     const uint32_t i = base + threadIdx.x;
     const bool valid = i < n;
     const uint32_t slot = valid ? seg_slot(s_off, nseg_in, per_in, i) : 0u;
-    shade_trace<kCube, kFirst, kClose>(sc, sv, sh, smat, nm, f, idiv, w, rin, rout, depth, last, valid, slot, sd.seg0, &s_cnt_n,
+    shade_trace<kCube, kFirst, kClose, kFrom>(sc, sv, sh, smat, nm, f, idiv, w, rin, rout, depth, last, valid, slot, sd.seg0, &s_cnt_n,
                                        vc, s_stack, rays, traced);
   }
   for (int off = 32; off > 0; off >>= 1) {
@@ -3345,6 +3417,7 @@ __global__ void __launch_bounds__(kBlock, kLds ? SPTR_TAIL_WAVES_LDS : SPTR_TAIL
   if (threadIdx.x < 2u) s_rays[threadIdx.x] = 0u;
   if (threadIdx.x == 0u) s_next = 0u;
   const Staged sc = stage_scene<kLds>(sv, lds);
+  constexpr int kFrom = kShadeGlobal;
   // the wide BVH's top levels in LDS (L2/HBM scenes), published by seg_scan's barriers
   const uint32_t ntop = (walk_reads_top(kWalkU) && kW4 && !kLds) ? sv.num_top4 : 0u;
   const uint4* top = ntop ? stage_top(sv, lds + top_lds_offset(sv, kLds, false, nseg_in)) : nullptr;
@@ -3417,7 +3490,7 @@ __global__ void __launch_bounds__(kBlock, kLds ? SPTR_TAIL_WAVES_LDS : SPTR_TAIL
         radv = radv + thr * env_color<kCube>(sh.env, renormalized_again(rd));
         break;
       }
-      const Surface sf = surface_at(sv, sh, smat, nm, ro, rd, tfar, ref);
+      const Surface sf = surface_at<kFrom>(sc, sv, sh, smat, nm, ro, rd, tfar, ref);
       const vec3 emission = v3(sf.m.emission[0], sf.m.emission[1], sf.m.emission[2]);
       if (dot(emission, emission) > 0.0f) radv = radv + thr * emission;
       const vec3 view = -rd;
@@ -3482,6 +3555,7 @@ __global__ void __launch_bounds__(kBlock, SPTR_STRAG_WAVES) k_strag(SceneView sv
   if (threadIdx.x < 2u) s_rays[threadIdx.x] = 0u;
   if (threadIdx.x == 0u) s_next = 0u;
   const Staged sc = stage_scene<false>(sv, nullptr);
+  constexpr int kFrom = kShadeGlobal;
   extern __shared__ float4 lds[];
   const uint32_t ntop = walk_reads_top(kWalkU) ? sv.num_top4 : 0u;
   const uint4* top = ntop ? stage_top(sv, lds) : nullptr;
@@ -3556,7 +3630,7 @@ __global__ void __launch_bounds__(kBlock, SPTR_STRAG_WAVES) k_strag(SceneView sv
         radv = radv + thr * env_color<kCube>(sh.env, renormalized_again(rd));
         break;
       }
-      const Surface sf = surface_at(sv, sh, smat, nm, ro, rd, tfar, ref);
+      const Surface sf = surface_at<kFrom>(sc, sv, sh, smat, nm, ro, rd, tfar, ref);
       const vec3 emission = v3(sf.m.emission[0], sf.m.emission[1], sf.m.emission[2]);
       if (dot(emission, emission) > 0.0f) radv = radv + thr * emission;
       const vec3 view = -rd;
@@ -4580,7 +4654,8 @@ bool shade_fuses_shadows(const SceneView& sv, const ShadeView& sh, bool count) {
 #endif
   // the visit-count pass keeps k_shadow (shadow visit tallies); several lights keep their task
   // records (in light order) in the shadow stream; the in-shade traversal is the LDS BVH2 one
-  return sv.lds_bytes != 0 && sv.width == 2u && sh.num_lights == 1u && !count;
+  // (the fused bounce kernels take a hit's material from the slot table alone: surface_at<kShadeFused>)
+  return sv.lds_bytes != 0 && sv.width == 2u && sh.num_lights == 1u && !count && sh.prim_mat != nullptr;
 }
 
 unsigned launch_shade(const SceneView& sv, const ShadeView& sh, const FrameView& f, const WaveView& w, int depth,
@@ -4614,7 +4689,7 @@ void launch_cull(const SceneView& sv, const FrameView& f, uint32_t* mask, uint32
 unsigned launch_bounce(const SceneView& sv, const ShadeView& sh, const FrameView& f, const WaveView& w_in, int depth,
                        uint32_t nseg, bool shade_first, bool close, hipStream_t s) {
   const WaveView w = with_tslot(w_in);
-  const unsigned lb = sv.lds_bytes + (4u * (nseg + 1u) + 15u) / 16u * 16u;
+  const unsigned lb = sv.lds_bytes + sh.pm_lds_bytes + (4u * (nseg + 1u) + 15u) / 16u * 16u;  // scene, table, s_off
   if (!shade_first)
     return dispatch(
         [&](auto fl) -> unsigned {
@@ -4639,7 +4714,7 @@ unsigned launch_bounce(const SceneView& sv, const ShadeView& sh, const FrameView
 unsigned launch_bounce01(const SceneView& sv, const ShadeView& sh, const FrameView& f, const WaveView& w_in, uint32_t nseg,
                          bool shade_first, bool close, hipStream_t s) {
   const WaveView w = with_tslot(w_in);
-  const unsigned lb = sv.lds_bytes + (4u * (nseg + 1u) + 15u) / 16u * 16u;
+  const unsigned lb = sv.lds_bytes + sh.pm_lds_bytes + (4u * (nseg + 1u) + 15u) / 16u * 16u;  // scene, table, s_off
   if (!shade_first)
     return dispatch(
         [&](auto fl) -> unsigned {
@@ -4664,7 +4739,7 @@ unsigned launch_bounce01(const SceneView& sv, const ShadeView& sh, const FrameVi
 unsigned launch_bounce_chain(const SceneView& sv, const ShadeView& sh, const FrameView& f, const WaveView& w_in, int T,
                              uint32_t nseg, hipStream_t s) {
   const WaveView w = with_tslot(w_in);
-  const unsigned lb = sv.lds_bytes + (4u * (nseg + 1u) + 15u) / 16u * 16u;
+  const unsigned lb = sv.lds_bytes + sh.pm_lds_bytes + (4u * (nseg + 1u) + 15u) / 16u * 16u;  // scene, table, s_off
   return dispatch(
       [&](auto fl) -> unsigned {
         return [&]<bool Cube, bool Tm>(Flags<Cube, Tm>) {
@@ -4862,6 +4937,20 @@ __global__ void __launch_bounds__(kBlock) k_tri_materials(const uint32_t* tri_ge
 }
 void launch_tri_materials(const uint32_t* tri_geom, const uint32_t* geom_mat, uint32_t n, uint32_t* tri_mat, hipStream_t s) {
   if (n) hipLaunchKernelGGL(k_tri_materials, dim3(grid_for(n)), dim3(kBlock), 0, s, tri_geom, geom_mat, n, tri_mat);
+}
+
+__global__ void __launch_bounds__(kBlock) k_prim_materials(const uint32_t* tri_geom, const uint32_t* sph_geom,
+                                                           const uint32_t* geom_mat, uint32_t num_tris, uint32_t num_sph,
+                                                           uint32_t* prim_mat) {
+  const uint32_t n = prim_mat_bytes(num_tris, num_sph) / 4u;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += grid_threads())
+    prim_mat[i] = prim_mat_entry(tri_geom, sph_geom, geom_mat, num_tris, num_sph, i);
+}
+void launch_prim_materials(const uint32_t* tri_geom, const uint32_t* sph_geom, const uint32_t* geom_mat, uint32_t num_tris,
+                           uint32_t num_sph, uint32_t* prim_mat, hipStream_t s) {
+  const uint32_t n = prim_mat_bytes(num_tris, num_sph) / 4u;
+  if (n) hipLaunchKernelGGL(k_prim_materials, dim3(grid_for(n)), dim3(kBlock), 0, s, tri_geom, sph_geom, geom_mat, num_tris,
+                            num_sph, prim_mat);
 }
 
 void launch_unpack(const uint32_t* gathered, int G, uint32_t tiles_per_rank, int W, int H, uint8_t* rgb,

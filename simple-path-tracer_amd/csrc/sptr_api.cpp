@@ -250,9 +250,33 @@ bool shade_first_on(uint64_t batch_paths) { return batch_paths > kShadeFirstMinP
 
 // MaterialManager::getMaterialFromHit (src/MaterialManager.cpp:91-103): the geomID's mapped
 // material when it is in range, else MaterialManager::getMaterialByID(geomID) (:79-89).
+// LDS-staged scenes: the material of every primitive slot of c's scene (ShadeView::prim_mat, prim_mat_table.h),
+// from the geomID -> material table of the context whose shading c renders with.  The slots are c's own: a pixel
+// lane holds its own build of the scene, so it gets its own table, rebuilt whenever the owner's geom_mat changes
+// (sptr_upload_scene, sptr_set_materials).  Without a table (no materials yet, a scene traversed from L2/HBM)
+// the kernels read geom_mat through the slot's geomID, and the bounces are not fused (shade_fuses_shadows).
+int build_prim_materials(Context& c) {
+  const Context& own = shading(c);
+  c.prim_mat_n = 0u;
+  const uint32_t n = prim_mat_entries(c.num_tri_refs, c.num_sph);
+  if (!c.have_scene || n == 0u || own.mats_host.empty() || own.geom_mat.p == nullptr ||
+      own.num_tri_geoms != c.num_tri_geoms || own.num_sph != c.num_sph || scene_view(c).lds_bytes == 0u)
+    return SPTR_OK;
+  API_HIP(hipSetDevice(c.device));
+  API_HIP(c.prim_mat.ensure(prim_mat_bytes(c.num_tri_refs, c.num_sph)));
+  launch_prim_materials(static_cast<const uint32_t*>(c.tri_geom.p), static_cast<const uint32_t*>(c.sph_geom.p),
+                        static_cast<const uint32_t*>(own.geom_mat.p), c.num_tri_refs, c.num_sph,
+                        static_cast<uint32_t*>(c.prim_mat.p), c.stream);
+  API_HIP(hipGetLastError());
+  API_HIP(hipStreamSynchronize(c.stream));
+  c.prim_mat_n = n;
+  return SPTR_OK;
+}
+
 int resolve_geom_materials(Context& c) {
   const uint32_t nm = (uint32_t)c.mats_host.size();
   const uint32_t ng = c.num_tri_geoms + c.num_sph;
+  c.prim_mat_n = 0u;
   if (!c.have_scene || nm == 0) return SPTR_OK;
   std::vector<uint32_t> t(ng ? ng : 1, 0u);
   for (uint32_t g = 0; g < ng; ++g) {
@@ -276,7 +300,7 @@ int resolve_geom_materials(Context& c) {
     API_HIP(hipGetLastError());
     API_HIP(hipStreamSynchronize(c.stream));
   }
-  return SPTR_OK;
+  return build_prim_materials(c);
 }
 
 inline bool host_local_pixel(const Context& c, uint32_t l, int& x, int& y) {
@@ -430,6 +454,10 @@ ShadeView shade_view(const Context& cc) {
   s.num_mats = (uint32_t)c.mats_host.size();
   s.geom_mat = static_cast<const uint32_t*>(c.geom_mat.p);
   s.tri_mat = cc.parent ? nullptr : static_cast<const uint32_t*>(c.tri_mat.p);  // (slots are the owner's)
+  // (the slots are cc's own: build_prim_materials)
+  const bool pm = cc.prim_mat_n != 0u && cc.prim_mat_n == prim_mat_entries(cc.num_tri_refs, cc.num_sph);
+  s.prim_mat = pm ? static_cast<const uint32_t*>(cc.prim_mat.p) : nullptr;
+  s.pm_lds_bytes = pm ? prim_mat_lds_bytes(scene_view(cc).lds_bytes, cc.num_tri_refs, cc.num_sph, kLdsSceneBytes) : 0u;
   s.num_lights = (uint32_t)c.lights_host.size();
   for (uint32_t i = 0; i < s.num_lights; ++i) s.lights[i] = c.lights_host[i];
   s.env.env = static_cast<const float4*>(c.env.p);
@@ -1586,7 +1614,7 @@ static int set_bvh_width_one(sptr_ctx* x, uint32_t width) {
     return fail(x->c, SPTR_ERR_INVALID, "bvh width must be 0 (auto), 2 or " + std::to_string(kWide));
   x->c.bvh_width = width;
   ++x->c.epoch;
-  return SPTR_OK;
+  return build_prim_materials(x->c);  // (the width decides whether the scene is staged: scene_view)
 }
 
 static int set_tail_depth_one(sptr_ctx* x, uint32_t depth) {
@@ -1659,6 +1687,7 @@ static int upload_scene_one(sptr_ctx* x, const sptr_scene* s) {
     for (uint32_t i = s->tri_geom_first[g]; i < s->tri_geom_first[g + 1]; ++i) tg[i] = g;
   }
   c.have_scene = false;
+  c.prim_mat_n = 0u;
   c.num_tri_geoms = s->num_tri_geoms;
   c.geom_first.assign(s->tri_geom_first, s->tri_geom_first + (s->num_tri_geoms ? s->num_tri_geoms + 1 : 0));
   c.geom_material.assign(s->geom_material, s->geom_material + s->num_tri_geoms + s->num_spheres);
@@ -2479,6 +2508,8 @@ int sptr_upload_scene(sptr_ctx* x, const sptr_scene* s) {
     const int r1 = upload_scene_one(x->lane, s);
     if (r1 != SPTR_OK) return lane_forward(x, r1);
     x->lane_scene = true;
+    const int r2 = build_prim_materials(cy);  // (its slots, this context's geom_mat)
+    if (r2 != SPTR_OK) return lane_forward(x, r2);
   }
   return SPTR_OK;
 }
@@ -3338,7 +3369,14 @@ int sptr_set_wave_paths(sptr_ctx* x, uint64_t max_paths) {
 int sptr_set_materials(sptr_ctx* x, const sptr_material* m, uint32_t n) {
   const int rs = lane_shading_sync(x);
   if (rs != SPTR_OK) return rs;
-  return lane_shading_changed(x, set_materials_one(x, m, n));
+  const int rc = lane_shading_changed(x, set_materials_one(x, m, n));
+  if (rc != SPTR_OK || !x->lane) return rc;
+  // the lane's slot table follows this context's geom_mat; without a current copy of the scene it has none
+  if (!x->lane_scene) {
+    x->lane->c.prim_mat_n = 0u;
+    return rc;
+  }
+  return lane_forward(x, build_prim_materials(x->lane->c));
 }
 
 int sptr_set_lights(sptr_ctx* x, const sptr_light* l, uint32_t n) {

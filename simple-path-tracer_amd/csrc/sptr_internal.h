@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "dev_owned.h"
+#include "prim_mat_table.h"
 #include "sptr_hip.h"
 #include "sptr_math.h"
 #include "tile_map.h"
@@ -142,6 +143,12 @@ struct ShadeView {
   DevLight lights[kMaxLights];
   EnvView env;
   int32_t debug_mode;
+  // LDS-staged scenes: primitive slot -> material index, triangle slots first and sphere slot j at num_tris + j
+  // (prim_mat_table.h), padded to whole 16 bytes; null elsewhere.  pm_lds_bytes: its padded size when the fused
+  // bounce kernels stage it behind the scene (their dynamic LDS: scene, table, segment offsets), 0 when they
+  // read it from global memory.  Not part of SceneView::lds_bytes.
+  const uint32_t* prim_mat;
+  uint32_t pm_lds_bytes;
 };
 
 struct FrameView {
@@ -510,6 +517,8 @@ struct Context {
   // scene
   DevBuf nodes, prim_ref, tris, sph, tri_geom, sph_geom, tri_orig, sph_orig, geom_mat;
   DevBuf tri_mat;  // ShadeView::tri_mat (resolve_geom_materials)
+  DevBuf prim_mat;           // ShadeView::prim_mat of this context's slots (build_prim_materials)
+  uint32_t prim_mat_n = 0;   // slots it was built for; 0: none
   uint32_t leaf_size = 0;  // max primitives per BVH leaf range (1..16); 0 = automatic
   uint32_t bvh_width = 0;  // traversal width: 2 (LBVH as built), 4 (collapsed), 0 = automatic
   uint32_t leaf_used = 0;  // leaf size the current BVH was built with
@@ -668,6 +677,9 @@ void launch_unpack(const uint32_t* gathered, int G, uint32_t tiles_per_rank, int
                    hipStream_t s);
 // tri_mat[i] = geom_mat[tri_geom[i]], i < n
 void launch_tri_materials(const uint32_t* tri_geom, const uint32_t* geom_mat, uint32_t n, uint32_t* tri_mat, hipStream_t s);
+// prim_mat[i] = prim_mat_entry(..., i), i < prim_mat_bytes(num_tris, num_sph) / 4 (prim_mat_table.h)
+void launch_prim_materials(const uint32_t* tri_geom, const uint32_t* sph_geom, const uint32_t* geom_mat, uint32_t num_tris,
+                           uint32_t num_sph, uint32_t* prim_mat, hipStream_t s);
 void launch_query(const SceneView& sv, const uint32_t* tri_orig, const uint32_t* sph_orig, const float* rays, uint32_t n,
                   bool anyhit, uint32_t* ref, float* t, float* ng, uint8_t* occ, uint32_t* stack_overflow, hipStream_t s);
 void launch_primary(const FrameView& f, float* dirs, uint32_t* rng, hipStream_t s);
