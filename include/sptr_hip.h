@@ -619,6 +619,64 @@ int sptr_query_rays(sptr_ctx* ctx, const sptr_ray_query* query, void* stream);
  * traversal-stack-overflow flag (a synchronous query checks the flag itself).  Any pointer may be NULL. */
 int sptr_query_info(sptr_ctx* ctx, double* ms_sort, double* ms_trace, uint32_t* sorted, uint32_t* queries);
 
+/* ---- path-traced radiance for caller-supplied rays (symbols added within ABI 9: no existing struct or
+ *      entry point changed) ------------------------------------------------------------------------------
+ * sptr_render renders through the reference's pinhole camera and sptr_query_rays answers what a ray hits; this
+ * entry point takes arbitrary rays and returns what the wavefront integrator sees along them: fisheye,
+ * equirectangular, orthographic and stereo cameras, irradiance and reflection probes, lightmap texels, sensor
+ * models.  It is not a second integrator: a producer writes the rays into the integrator's ray stream, the
+ * chain of trace / shade / shadow stages (and the path-per-thread tail) runs from depth 0 through the
+ * instantiations that bounces >= 1 use, and a consumer sums the paths' radiance (DESIGN.md "Ray rendering").
+ * A ray given the origin, direction and rng state of a camera path returns that path's radiance bit for bit.
+ *
+ * rays: n x 8 floats as sptr_query_rays (o3, d3, and two words that are ignored): the first segment is traced as
+ * a camera ray, tnear 0 and no tfar.  The direction is used as given and must be of unit length; with
+ * SPTR_RAYS_NORMALIZE the library first applies the shading's safe_normalize (v / sqrt(v.v), both correctly
+ * rounded; 0 for a zero vector) — a unit vector is not a fixed point of that function in float32, hence the flag.
+ * Rng state of sample s (0 <= s < samples) of ray i: seeds[i] when seeds is not NULL and samples == 1; otherwise
+ * wang_hash((b ^ (frame_index + s)) ^ 1) with b = seeds ? seeds[i] : i — the state the wavefront raygen gives
+ * pixel seed b in frame frame_index + s, so ray i of a batch without seeds draws what pixel i of that frame
+ * draws (sptr_primary_rays returns those states).
+ * radiance: n x 3 floats, L_i = +0 + L(i, 0) + L(i, 1) + ... in sample order, one add each (the adds the
+ * accumulation of sptr_render makes; divide by samples for the mean).  Stored, or with SPTR_RAYS_ACCUMULATE
+ * radiance[i] = radiance[i] + L_i, one add per component.
+ * The scene, materials, lights, environment, debug mode and refits are followed as a render call follows them;
+ * the semantics are SPTR_INTEGRATOR_WAVEFRONT's.  The image of a render call, its accumulation, its stats, a
+ * captured launch graph, the AOV cache and the denoiser's history are left as they were.
+ *
+ * Pointers: with SPTR_RAYS_DEVICE_PTRS every pointer is a device pointer on the context's device, and the ray
+ * buffer must be 16-byte aligned (SPTR_ERR_INVALID otherwise); without it every pointer is a host pointer, the
+ * library stages the arrays, and the call is synchronous (a non-NULL stream is SPTR_ERR_INVALID).
+ * Streams: the work always runs on the context's stream, since it uses the context's wave buffers, which render
+ * calls use too; a batch runs in chunks of whole rays that fit the capacity those buffers have
+ * (sptr_set_wave_paths lowers it).  stream == NULL: the work follows the pending renders, and the call returns
+ * when the output is written.  A non-NULL stream (a hipStream_t, device pointers only): the context's stream
+ * waits for an event recorded on that stream, and that stream waits for the completion event; no host wait
+ * happens, and the buffers must stay alive until that stream has passed the event.  Render calls that follow
+ * use the context's stream or that one, and the caller synchronises it before any upload, as for queries.
+ * n == 0 returns SPTR_OK with no launch.  SPTR_ERR_INVALID: NULL rays or radiance with n > 0, samples == 0,
+ * max_depth == 0 (or above 32, as for sptr_render), frame_index == 0, frame_index + samples - 1 above 2^32 - 1,
+ * unknown flags, non-zero reserved words, n > 2^28, n * samples > 2^29, a lane context; SPTR_ERR_NO_SCENE before
+ * an upload or before materials are set. */
+enum { SPTR_RAYS_DEVICE_PTRS = 1u, SPTR_RAYS_ACCUMULATE = 2u, SPTR_RAYS_NORMALIZE = 4u };
+typedef struct sptr_ray_render {
+  const float* rays;      /* n x 8 floats as sptr_query_rays: o.xyz, d.xyz, and two words that are ignored */
+  const uint32_t* seeds;  /* n, or NULL */
+  uint32_t n;             /* <= 2^28 */
+  uint32_t samples;       /* paths per ray in this call, >= 1; n * samples <= 2^29 */
+  uint32_t frame_index;   /* accumulation index of sample 0 (a frame's frame_begin), >= 1 */
+  uint32_t max_depth;     /* as sptr_frame.max_depth */
+  uint32_t flags;
+  float* radiance;        /* n x 3 floats */
+  uint32_t reserved[4];   /* 0 */
+} sptr_ray_render;
+int sptr_render_rays(sptr_ctx* ctx, const sptr_ray_render* batch, void* stream);
+/* Waits for the last call's end event: its device time, its closest-hit and any-hit query counts (as
+ * sptr_stats counts them; they are not added to any render call's stats) and the chunks it ran in.  All 0
+ * before the first call; a call with n == 0 leaves the previous call's values.  SPTR_ERR_HIP if the call set the
+ * traversal-stack or stream-overflow flag (a synchronous call checks them itself).  Any pointer may be NULL. */
+int sptr_ray_render_info(sptr_ctx* ctx, double* ms, uint64_t* closest, uint64_t* shadow, uint32_t* chunks);
+
 /* ---- query entry points (tests / tooling) -------------------------------------------------------- */
 /* Closest-hit / any-hit queries on the device BVH: rays = n*8 floats (o3, d3, tnear, tfar).
  * Outputs as rtcIntersect1 reports them: geomID (0xFFFFFFFF on miss), primID, t, unnormalised Ng. */

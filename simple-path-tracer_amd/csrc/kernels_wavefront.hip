@@ -4561,11 +4561,11 @@ static unsigned dispatch(Fn&& fn, Flags<B...>, bool first, Rest... rest) {
 
 
 unsigned launch_trace(const SceneView& sv, const ShadeView& sh, const FrameView& f, const WaveView& w_in, int depth,
-                      bool count, uint32_t nseg, hipStream_t s) {
+                      bool count, uint32_t nseg, hipStream_t s, bool stream_rays) {
   const WaveView w = with_tslot(w_in);
   const dim3 b(kBlock);
   const bool L = sv.lds_bytes != 0;
-  const bool P = depth == 0;
+  const bool P = depth == 0 && !stream_rays;
   const bool W = sv.width == (uint32_t)kWide;
   const bool cube = sh.env.env != nullptr;
   const unsigned lb = trace_lds(sv, L, P, nseg);
@@ -4659,7 +4659,7 @@ bool shade_fuses_shadows(const SceneView& sv, const ShadeView& sh, bool count) {
 }
 
 unsigned launch_shade(const SceneView& sv, const ShadeView& sh, const FrameView& f, const WaveView& w, int depth,
-                      uint32_t nseg, bool fuse, hipStream_t s) {
+                      uint32_t nseg, bool fuse, hipStream_t s, bool stream_rays) {
   const unsigned lb = (fuse ? sv.lds_bytes : 0u) + (4u * (nseg + 1u) + 15u) / 16u * 16u;
   return dispatch(
       [&](auto fl) -> unsigned {
@@ -4669,7 +4669,7 @@ unsigned launch_shade(const SceneView& sv, const ShadeView& sh, const FrameView&
           return g;
         }(fl);
       },
-      Flags<>{}, depth == 0, fuse);
+      Flags<>{}, depth == 0 && !stream_rays, fuse);
 }
 
 bool cull_entries_apply(const SceneView& sv) { return sv.lds_bytes != 0u && sv.width == 2u; }
@@ -4977,5 +4977,7 @@ void launch_primary(const FrameView& f, float* dirs, uint32_t* rng, hipStream_t 
 #include "kernels_denoise.h"
 // batched ray queries on caller buffers (the same traversal, staged or wide as the render kernels')
 #include "kernels_query.h"
+// path-traced radiance for caller-supplied rays: the producer and consumer around the chain's depth-0 entry
+#include "kernels_rays.h"
 
 }  // namespace sptr

@@ -107,6 +107,16 @@ struct sptr_ctx {
     bool sorted = false;
     uint32_t count = 0;
   } rq;
+  // sptr_render_rays (the caller's context; a pixel lane holds none): the call's own totals block (WaveView::tot
+  // of its launches, so that the render totals never see them), the carried sum of a ray whose sample range is
+  // split, the staging of host-pointer calls, and the events of the last call: begin and end on the context's
+  // stream, and the fork recorded on a caller's stream or on the pending renders' stream
+  struct RayRender {
+    sptr::DevBuf tot, carry, stage_rays, stage_seeds, stage_out;
+    sptr::DevEvent ev[3];  // begin, end, fork
+    bool issued = false;
+    uint32_t chunks = 0;
+  } rr;
   // Waits for everything that may still use this context's resources, then lets the lane go; the members
   // free themselves after that (in reverse order of declaration: c, with its streams, last).
   ~sptr_ctx() {
@@ -409,7 +419,10 @@ FrameView frame_view(const Context& c, const sptr_frame& f) {
   v.div_P = make_fastdiv(c.P ? c.P : 1u);
   v.div_ntx = make_fastdiv((uint32_t)v.ntx);
   v.valid = 0;
-  {
+  // (c.W == 0: the pixel buffers await their next layout — an upload or a lane change after a two-lane
+  // accumulation sets it — and the callers that get here before the next render, sptr_primary_rays and
+  // sptr_render_rays, read no pixel; the tile count is stale then and ntx would be 0)
+  if (c.W > 0) {
     const int ntx = (c.W + kTile - 1) / kTile;
     for (uint32_t lt = 0; lt < c.local_tiles; ++lt) {
       const uint32_t t = lt * (uint32_t)c.G + (uint32_t)c.R;
@@ -2382,6 +2395,202 @@ int sptr_query_info(sptr_ctx* x, double* ms_sort, double* ms_trace, uint32_t* so
   if (sorted) *sorted = rq.issued && rq.sorted ? 1u : 0u;
   if (queries) *queries = rq.count;
   return rq.issued ? query_check_flag(x) : SPTR_OK;
+}
+
+// ---- path-traced radiance for caller-supplied rays ---------------------------------------------------
+constexpr uint32_t kRaysMaxRays = 1u << 28;
+constexpr uint64_t kRaysMaxPaths = 1ull << 29;
+constexpr uint32_t kRaysFlags = SPTR_RAYS_DEVICE_PTRS | SPTR_RAYS_ACCUMULATE | SPTR_RAYS_NORMALIZE;
+// wave capacity the ray path allocates when the context has none yet (about 0.8 GB with one light; a context
+// that has rendered has its own, and the ray path takes that)
+constexpr uint64_t kRaysOwnPaths = 1ull << 22;
+
+// Paths per chunk that the wave buffers the context already has can hold on the current scene and lights,
+// 0 if they cannot serve the ray path as they are.  A chunk of np paths needs np records in every stream, the
+// segment slack ensure_wave adds, and hit records for the trace's segments (twice the static shares where the
+// trace takes its rays from the per-XCD queues).
+static uint64_t rays_wave_capacity(Context& c) {
+  const WaveBufs& b = c.wb;
+  const uint32_t L = std::max<uint32_t>(1u, (uint32_t)shading(c).lights_host.size()), ts = task_stride(c);
+  if (!b.seg.p || !b.rad.p || b.cap == 0 || (uint64_t)b.L * b.ts < (uint64_t)L * ts) return 0;
+  const uint64_t slack = (uint64_t)kMaxSegs * kBlock;
+  const uint64_t hrecs = b.hrec.bytes / (kHitBytes * hrec_mult(scene_view(c)));
+  if (hrecs <= slack) return 0;
+  return std::min<uint64_t>(b.cap, hrecs - slack);
+}
+
+// after the last call completed: the flags its launches may have set in the call's totals block
+static int ray_render_check(sptr_ctx* x, unsigned long long* tot_out) {
+  Context& c = x->c;
+  unsigned long long tot[kTotWords];
+  API_HIP(hipMemcpy(tot, x->rr.tot.p, sizeof(tot), hipMemcpyDeviceToHost));
+  if (tot_out) std::memcpy(tot_out, tot, sizeof(tot));
+  if (tot[kTotOverflow]) return fail(c, SPTR_ERR_HIP, "render_rays: segmented stream overflow (internal error)");
+  if (tot[kTotStackOverflow]) return fail(c, SPTR_ERR_HIP, "render_rays: BVH traversal stack overflow (internal error)");
+  return SPTR_OK;
+}
+
+// One validated batch with device pointers, enqueued on the context's stream in chunks of at most cap paths.
+// Per chunk: k_rays_inject, then the serial separate-stage chain from depth 0 — trace(d), shade(d) with its
+// shadow ray in place where shade_fuses_shadows says so, else shadow(d) — with k_tail from the tail depth the
+// batch-size rule gives a batch of the chunk's paths, then k_rays_gather.  No cull, no k_sky, no side streams,
+// no captured graph, no straggler hand-off, no fused bounce launches, no deferred misses, no shadow carry.
+static int enqueue_ray_render(sptr_ctx* x, const sptr_ray_render& q, uint64_t cap) {
+  Context& c = x->c;
+  auto& rr = x->rr;
+  const hipStream_t s = c.stream;
+  const SceneView sv = scene_view(c);
+  const ShadeView sh = shade_view(c);
+  WaveView w = wave_view(c);
+  w.tot = static_cast<unsigned long long*>(rr.tot.p);
+  sptr_frame f{};
+  f.width = f.height = 1;
+  f.frame_begin = q.frame_index;
+  f.spp = 1;
+  f.max_depth = q.max_depth;
+  const FrameView fv = frame_view(c, f);  // (dyn null: absolute values; the stages of bounces >= 1 read max_depth only)
+  const bool fuse = shade_fuses_shadows(sv, sh, false);
+  RayBatchView b{};
+  b.rays = reinterpret_cast<const float4*>(q.rays);
+  b.seeds = q.seeds;
+  b.samples = q.samples;
+  b.frame_index = q.frame_index;
+  b.normalize = (q.flags & SPTR_RAYS_NORMALIZE) ? 1u : 0u;
+  b.accumulate = (q.flags & SPTR_RAYS_ACCUMULATE) ? 1u : 0u;
+  b.radiance = q.radiance;
+  b.carry = static_cast<float4*>(rr.carry.p);
+  const int D = (int)q.max_depth;
+  const uint64_t chunks = ray_chunk_count(q.n, q.samples, cap);
+  for (uint64_t ci = 0; ci < chunks; ++ci) {
+    const RayChunk ck = ray_chunk_at(q.n, q.samples, cap, ci);
+    const uint64_t np = (uint64_t)ck.nrays * ck.ns;
+    const int T = std::max(1, (int)(c.tail_depth ? c.tail_depth : auto_tail_depth(np, sv)));
+    uint32_t g_shade = launch_rays_inject(b, ck, w, s);
+    for (int d = 0; d < D; ++d) {
+      if (d >= T) {
+        launch_tail(sv, sh, fv, w, d, g_shade, s);
+        break;
+      }
+      const uint32_t g_trace = launch_trace(sv, sh, fv, w, d, false, g_shade, s, true);
+      g_shade = launch_shade(sv, sh, fv, w, d, g_trace, fuse, s, true);
+      if (!fuse) launch_shadow(sv, sh, w, d, false, g_shade, s);
+    }
+    launch_rays_gather(b, ck, w, s);
+    API_HIP(hipGetLastError());
+  }
+  rr.chunks = (uint32_t)chunks;
+  return SPTR_OK;
+}
+
+int sptr_render_rays(sptr_ctx* x, const sptr_ray_render* q, void* stream) {
+  if (!x || !q) return SPTR_ERR_INVALID;
+  Context& c = x->c;
+  auto& rr = x->rr;
+  if (x->is_lane) return fail(c, SPTR_ERR_INVALID, "render_rays: not on a lane context");
+  const bool dev = (q->flags & SPTR_RAYS_DEVICE_PTRS) != 0u;
+  if (q->flags & ~kRaysFlags) return fail(c, SPTR_ERR_INVALID, "render_rays: unknown flags");
+  for (uint32_t r : q->reserved)
+    if (r) return fail(c, SPTR_ERR_INVALID, "render_rays: reserved words must be 0");
+  if (q->n > kRaysMaxRays) return fail(c, SPTR_ERR_INVALID, "render_rays: more than 2^28 rays");
+  if (q->samples == 0u || q->max_depth == 0u || q->max_depth > (uint32_t)kMaxDepth || q->frame_index == 0u)
+    return fail(c, SPTR_ERR_INVALID, "render_rays: bad batch parameters");
+  if ((uint64_t)q->frame_index + q->samples - 1u > 0xFFFFFFFFull)
+    return fail(c, SPTR_ERR_INVALID, "render_rays: frame_index + samples - 1 overflows 32 bits");
+  if ((uint64_t)q->n * q->samples > kRaysMaxPaths) return fail(c, SPTR_ERR_INVALID, "render_rays: more than 2^29 paths");
+  if (q->n && (!q->rays || !q->radiance)) return fail(c, SPTR_ERR_INVALID, "render_rays: no rays or no radiance buffer");
+  if (!dev && stream) return fail(c, SPTR_ERR_INVALID, "render_rays: host pointers cannot be enqueued on a stream");
+  if (dev && (reinterpret_cast<uintptr_t>(q->rays) & 15u))
+    return fail(c, SPTR_ERR_INVALID, "render_rays: the device ray buffer must be 16-byte aligned");
+  if (!c.have_scene) return fail(c, SPTR_ERR_NO_SCENE, "render_rays: no scene");
+  if (shading(c).mats_host.empty()) return fail(c, SPTR_ERR_NO_SCENE, "render_rays: no materials set");
+  if (q->n == 0u) return SPTR_OK;
+  API_HIP(hipSetDevice(c.device));
+  const hipStream_t cs = stream ? static_cast<hipStream_t>(stream) : nullptr;
+  for (DevEvent& e : rr.ev)
+    if (!e) API_HIP(hipEventCreate(e.put()));
+  // pending renders on another stream than the context's: waited for on the host (stream == NULL), or followed
+  // through an event (a caller's stream; renders pending on that stream itself are followed through its fork)
+  if (c.pending && c.pending_stream != c.stream && c.pending_stream != cs) {
+    if (!cs) {
+      if (sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;
+    } else {
+      API_HIP(hipEventRecord(rr.ev[2], c.pending_stream));
+      API_HIP(hipStreamWaitEvent(c.stream, rr.ev[2], 0));
+    }
+  }
+  // The wave buffers the context has are taken as they are: the ray path never grows or reallocates them while
+  // they can serve it.  A context without any (or whose buffers do not fit the current lights or scene) gets a
+  // capacity through ensure_wave, which waits for pending renders and bumps the state epoch, as any growth does.
+  uint64_t cap = rays_wave_capacity(c);
+  if (cap == 0) {
+    const uint64_t want = c.wb.cap ? c.wb.cap : std::min<uint64_t>(kRaysOwnPaths, (uint64_t)q->n * q->samples);
+    const int rc = ensure_wave(c, want, (uint32_t)shading(c).lights_host.size(), task_stride(c), 1u, hrec_mult(scene_view(c)));
+    if (rc != SPTR_OK) return rc;
+    cap = rays_wave_capacity(c);
+    if (cap == 0) return fail(c, SPTR_ERR_HIP, "render_rays: no wave capacity (internal error)");
+  }
+  if (c.wave_paths) cap = std::min<uint64_t>(cap, c.wave_paths);
+  if (!rr.tot.p) API_HIP(rr.tot.ensure(kTotWords * 8));
+  if (!rr.carry.p) API_HIP(rr.carry.ensure(256));
+  sptr_ray_render d = *q;
+  const size_t n = q->n;
+  if (!dev) {  // host pointers: rays, seeds and (to accumulate) the radiance in, the radiance out
+    API_HIP(rr.stage_rays.ensure(n * 32));
+    API_HIP(rr.stage_out.ensure(n * 12));
+    API_HIP(hipMemcpyAsync(rr.stage_rays.p, q->rays, n * 32, hipMemcpyHostToDevice, c.stream));
+    if (q->seeds) {
+      API_HIP(rr.stage_seeds.ensure(n * 4));
+      API_HIP(hipMemcpyAsync(rr.stage_seeds.p, q->seeds, n * 4, hipMemcpyHostToDevice, c.stream));
+      d.seeds = static_cast<const uint32_t*>(rr.stage_seeds.p);
+    }
+    if (q->flags & SPTR_RAYS_ACCUMULATE)
+      API_HIP(hipMemcpyAsync(rr.stage_out.p, q->radiance, n * 12, hipMemcpyHostToDevice, c.stream));
+    d.rays = static_cast<const float*>(rr.stage_rays.p);
+    d.radiance = static_cast<float*>(rr.stage_out.p);
+  }
+  if (cs) {  // the rays' producer on the caller's stream
+    API_HIP(hipEventRecord(rr.ev[2], cs));
+    API_HIP(hipStreamWaitEvent(c.stream, rr.ev[2], 0));
+  }
+  API_HIP(hipMemsetAsync(rr.tot.p, 0, kTotWords * 8, c.stream));
+  API_HIP(hipEventRecord(rr.ev[0], c.stream));
+  const int rc = enqueue_ray_render(x, d, cap);
+  // (the end event also after a failed launch: what was enqueued may still run)
+  const hipError_t ee = hipEventRecord(rr.ev[1], c.stream);
+  rr.issued = ee == hipSuccess;
+  if (rc != SPTR_OK) return rc;
+  API_HIP(ee);
+  if (cs) {
+    API_HIP(hipStreamWaitEvent(cs, rr.ev[1], 0));
+    return SPTR_OK;
+  }
+  API_HIP(hipStreamSynchronize(c.stream));
+  const int rf = ray_render_check(x, nullptr);
+  if (rf != SPTR_OK) return rf;
+  if (!dev) API_HIP(hipMemcpy(q->radiance, d.radiance, n * 12, hipMemcpyDeviceToHost));
+  return SPTR_OK;
+}
+
+int sptr_ray_render_info(sptr_ctx* x, double* ms, uint64_t* closest, uint64_t* shadow, uint32_t* chunks) {
+  if (!x) return SPTR_ERR_INVALID;
+  Context& c = x->c;
+  auto& rr = x->rr;
+  double ms_v = 0.0;
+  unsigned long long tot[kTotWords] = {};
+  int rc = SPTR_OK;
+  if (rr.issued) {
+    API_HIP(hipSetDevice(c.device));
+    API_HIP(hipEventSynchronize(rr.ev[1]));
+    float t = 0.0f;
+    API_HIP(hipEventElapsedTime(&t, rr.ev[0], rr.ev[1]));
+    ms_v = t;
+    rc = ray_render_check(x, tot);
+  }
+  if (ms) *ms = ms_v;
+  if (closest) *closest = tot[kTotClosest];
+  if (shadow) *shadow = tot[kTotShadow];
+  if (chunks) *chunks = rr.issued ? rr.chunks : 0u;
+  return rc;
 }
 
 int sptr_primary_rays(sptr_ctx* x, const sptr_camera* cam, int32_t W, int32_t H, uint32_t acc, float* dirs,

@@ -21,6 +21,7 @@
 
 #include "dev_owned.h"
 #include "prim_mat_table.h"
+#include "ray_batch.h"
 #include "sptr_hip.h"
 #include "sptr_math.h"
 #include "tile_map.h"
@@ -341,6 +342,16 @@ struct RayQueryView {
   const uint32_t* geom_first;
   uint32_t* stack_overflow;    // sticky flag
 };
+// One call of sptr_render_rays (k_rays_inject, k_rays_gather): device pointers, indexed by ray; its chunks are
+// RayChunks (ray_batch.h).
+struct RayBatchView {
+  const float4* rays;     // two per ray: o.xyz d.x | d.yz and two ignored words
+  const uint32_t* seeds;  // per ray, or null
+  uint32_t samples, frame_index;
+  uint32_t normalize, accumulate;  // SPTR_RAYS_NORMALIZE, SPTR_RAYS_ACCUMULATE
+  float* radiance;        // n x 3
+  float4* carry;          // the running sum of a ray whose sample range is split over chunks
+};
 // The denoiser's per-pass constants (k_dn_mean, k_atrous, k_dn_resolve), image space.
 struct DenoiseView {
   int32_t W, H;
@@ -603,13 +614,15 @@ hipError_t radix_sort_pairs_u64(void* temp, size_t& temp_bytes, const uint64_t* 
 // kernels_wavefront.hip
 SceneView scene_view(const Context& c);
 // Stage launchers return their (resident) grid size: the segment count their consumer scans.
+// stream_rays: depth 0 reads its rays from the ray stream too (the non-primary instantiation; sptr_render_rays,
+// whose producer k_rays_inject wrote them), instead of computing the camera ray of the path id
 unsigned launch_trace(const SceneView& sv, const ShadeView& sh, const FrameView& f, const WaveView& w, int depth, bool count,
-                  uint32_t nseg_in, hipStream_t s);
+                  uint32_t nseg_in, hipStream_t s, bool stream_rays = false);
 // k_shade traces the shadow ray in place (LDS-staged one-light scenes outside the visit-count pass)
 bool shade_fuses_shadows(const SceneView& sv, const ShadeView& sh, bool count);
 bool shadow_overlaps(const SceneView& sv, const WaveView& w);
 unsigned launch_shade(const SceneView& sv, const ShadeView& sh, const FrameView& f, const WaveView& w, int depth,
-                      uint32_t nseg, bool fuse, hipStream_t s);
+                      uint32_t nseg, bool fuse, hipStream_t s, bool stream_rays = false);
 // The fused bounce launches (k_shade_trace): each shades the hits of bounce depth - 1 and traces bounce depth.
 // close: the last wavefront bounce, which also shades its own hits and writes plain continuation rays (for
 // k_tail) or, at the last bounce of the path, nothing.  !shade_first (small batches, sptr_api.cpp shade_first_on):
@@ -701,6 +714,11 @@ void launch_atrous_history(const DenoiseView& v, const float4* cin, float4* cout
 // identity indices 0..n-1 beside them (the radix sort's values)
 void launch_rayquery(const SceneView& sv, const RayQueryView& q, bool anyhit, hipStream_t s);
 void launch_ray_keys(const SceneView& sv, const float4* rays, uint32_t n, uint64_t* keys, uint32_t* index, hipStream_t s);
+// kernels_rays.h: one chunk of sptr_render_rays.  The producer writes the chunk's paths into rs[0] / w.segN and
+// returns the segments it published (the nseg of the depth-0 trace); the consumer sums rad[] into the caller's
+// buffer and folds the chunk's per-block tallies into w.tot
+unsigned launch_rays_inject(const RayBatchView& b, const RayChunk& ck, const WaveView& w, hipStream_t s);
+void launch_rays_gather(const RayBatchView& b, const RayChunk& ck, const WaveView& w, hipStream_t s);
 // one wave spinning for `ticks` of the device wall clock (sptr_overlap_probe)
 void launch_spin(uint64_t ticks, hipStream_t s);
 

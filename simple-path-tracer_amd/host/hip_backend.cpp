@@ -325,4 +325,31 @@ bool HipBackend::queryRays(const float* rays, uint32_t n, bool anyHit, HitBuffer
   return true;
 }
 
+bool HipBackend::renderRays(const float* rays, const uint32_t* seeds, uint32_t n, uint32_t samples, uint32_t frame_index,
+                            float* radiance, bool accumulate, bool normalize, RayRenderInfo* info) {
+  if (!ctx_ || !built_) {
+    err_ = "HipBackend::renderRays: build() has not succeeded";
+    return false;
+  }
+  if (!syncState()) {
+    err_ = std::string("HipBackend: state upload failed: ") + sptr_last_error(ctx_);
+    return false;
+  }
+  sptr_ray_render q{};
+  q.rays = rays;
+  q.seeds = seeds;
+  q.n = n;
+  q.samples = samples;
+  q.frame_index = frame_index;
+  q.max_depth = settings_.max_depth;
+  q.flags = (accumulate ? SPTR_RAYS_ACCUMULATE : 0u) | (normalize ? SPTR_RAYS_NORMALIZE : 0u);
+  q.radiance = radiance;
+  if (sptr_render_rays(ctx_, &q, nullptr) != SPTR_OK ||
+      (info && sptr_ray_render_info(ctx_, &info->ms, &info->closest, &info->shadow, &info->chunks) != SPTR_OK)) {
+    err_ = std::string("HipBackend::renderRays: ") + sptr_last_error(ctx_);
+    return false;
+  }
+  return true;
+}
+
 }  // namespace backends

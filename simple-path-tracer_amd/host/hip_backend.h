@@ -126,6 +126,19 @@ class HipBackend {
     std::vector<uint8_t> occluded;
   };
   bool queryRays(const float* rays, uint32_t n, bool anyHit, HitBuffers& out);
+  // sptr_render_rays with host pointers: the wavefront integrator's radiance along n caller-supplied rays of 8
+  // floats (o3, unit d3, two ignored words) against the built scene and the current materials, lights and
+  // environment, Settings::max_depth bounces deep.  radiance (n x 3) takes, per ray, the sum of `samples` paths
+  // seeded as include/sptr_hip.h describes (seeds: n words or null), or has it added with `accumulate`;
+  // `normalize` applies the shading's safe_normalize to the directions first.  The image, the accumulation and
+  // the stats of render() are left alone.  info (may be null): sptr_ray_render_info of the call.
+  struct RayRenderInfo {
+    double ms = 0.0;
+    uint64_t closest = 0, shadow = 0;
+    uint32_t chunks = 0;
+  };
+  bool renderRays(const float* rays, const uint32_t* seeds, uint32_t n, uint32_t samples, uint32_t frame_index,
+                  float* radiance, bool accumulate = false, bool normalize = false, RayRenderInfo* info = nullptr);
   uint32_t frameIndex() const { return frame_index_; }
   const std::string& lastError() const { return err_; }
   const std::vector<uint32_t>& getGeomMaterialMapping() const { return geom_material_; }

@@ -130,6 +130,14 @@ class RayQuery(C.Structure):
                 ("occluded", C.c_void_p), ("reserved", C.c_uint64 * 4)]
 
 
+class RayRender(C.Structure):
+    """sptr_ray_render: pointers as addresses (host or device, by SPTR_RAYS_DEVICE_PTRS)."""
+    _fields_ = [("rays", C.c_void_p), ("seeds", C.c_void_p), ("n", C.c_uint32), ("samples", C.c_uint32),
+                ("frame_index", C.c_uint32), ("max_depth", C.c_uint32), ("flags", C.c_uint32),
+                ("radiance", C.c_void_p), ("reserved", C.c_uint32 * 4)]
+
+
+SPTR_RAYS_DEVICE_PTRS, SPTR_RAYS_ACCUMULATE, SPTR_RAYS_NORMALIZE = 1, 2, 4
 SPTR_AOV_ALBEDO, SPTR_AOV_NORMAL, SPTR_AOV_DEPTH, SPTR_AOV_ID, SPTR_AOV_UV = 0, 1, 2, 3, 4
 DEFAULT_MAX_HISTORY = 4  # the cap to ask set_denoise_history for without a number of one's own (DESIGN.md §6f)
 
@@ -149,7 +157,7 @@ EXPORTS = [
     "sptr_set_history_motion", "sptr_read_motion", "sptr_motion_info",
     "sptr_set_dynamic", "sptr_update_geometry", "sptr_refit_info",
     "sptr_set_rest_positions", "sptr_update_transforms", "sptr_tree_cost",
-    "sptr_query_rays", "sptr_query_info",
+    "sptr_query_rays", "sptr_query_info", "sptr_render_rays", "sptr_ray_render_info",
     "sptr_host_builtin_scene", "sptr_host_scene_view", "sptr_host_scene_free", "sptr_host_camera_lookat",
     "sptr_host_preset_materials", "sptr_host_default_lights", "sptr_host_equirect_to_faces",
     "sptr_host_pack_tiles", "sptr_host_unpack_tiles", "sptr_host_load_hdr", "sptr_host_free",
@@ -225,6 +233,8 @@ def lib() -> C.CDLL:
         "sptr_tree_cost": (C.c_int, [vp] + [C.POINTER(C.c_double)] * 4),
         "sptr_query_rays": (C.c_int, [vp, C.POINTER(RayQuery), vp]),
         "sptr_query_info": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), up, up]),
+        "sptr_render_rays": (C.c_int, [vp, C.POINTER(RayRender), vp]),
+        "sptr_ray_render_info": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(u64), C.POINTER(u64), up]),
         "sptr_host_builtin_scene": (C.c_int, [C.c_char_p, u32, u32, C.POINTER(vp)]),
         "sptr_host_scene_view": (C.c_int, [vp, C.POINTER(Scene)]),
         "sptr_host_scene_free": (None, [vp]),
@@ -825,6 +835,77 @@ class Renderer:
         so, n = C.c_uint32(), C.c_uint32()
         self._check(self._L.sptr_query_info(self._h, C.byref(s), C.byref(t), C.byref(so), C.byref(n)), "query_info")
         return {"ms_sort": s.value, "ms_trace": t.value, "sorted": so.value, "queries": n.value}
+
+    def render_rays(self, rays, seeds=None, samples: int = 1, frame_index: int = 1, max_depth: int = 6,
+                    accumulate: bool = False, normalize: bool = False, out=None, stream: int | None = None):
+        """sptr_render_rays: the wavefront integrator's radiance along n caller-supplied rays of 8 floats (o3, unit
+        d3, two ignored words): (n, 3) float32, per ray the sum of `samples` paths (divide for the mean).
+
+        A numpy (n, 8) array takes the host path and returns a numpy array.  A contiguous float32 tensor on this
+        context's GPU (16-byte aligned) takes the device path and returns a torch tensor on that device; seeds and
+        out are then tensors there too.  seeds: n uint32 (numpy) or a 4-byte integer tensor, or None; the rng
+        state of sample s of ray i is seeds[i] itself when samples == 1, else the wavefront raygen's state for
+        pixel seed seeds[i] (or i without seeds) in frame frame_index + s (include/sptr_hip.h).
+        accumulate adds to out (which must then be given) instead of storing; normalize applies the shading's
+        safe_normalize to the directions first.  out: a preallocated contiguous (n, 3) float32 array / tensor.
+        stream: a hipStream_t handle (device path only): the context's stream waits for that stream, and that
+        stream for the result; nothing waits on the host.  Without it a device-path call waits for torch's
+        current stream first and returns when the result is written."""
+        device = hasattr(rays, "data_ptr")
+        if device:
+            import torch
+
+            if rays.element_size() != 4 or not rays.is_floating_point() or not rays.is_contiguous() or rays.numel() % 8:
+                raise SptrError("render_rays: device rays must be a contiguous float32 tensor of n x 8")
+            n = rays.numel() // 8
+            if seeds is not None and (not hasattr(seeds, "data_ptr") or seeds.element_size() != 4 or seeds.is_floating_point()
+                                      or not seeds.is_contiguous() or seeds.numel() != n or seeds.device != rays.device):
+                raise SptrError(f"render_rays: device seeds must be a contiguous 4-byte integer tensor of {n} on the rays' device")
+            if out is None:
+                out = torch.empty((n, 3), dtype=torch.float32, device=rays.device)
+            elif not (hasattr(out, "data_ptr") and out.is_contiguous() and out.numel() == n * 3
+                      and out.dtype == torch.float32 and out.device == rays.device):
+                raise SptrError(f"render_rays: out must be a contiguous float32 tensor of {n} x 3 on the rays' device")
+
+            def addr(a):
+                return a.data_ptr()
+        else:
+            if stream is not None:
+                raise SptrError("render_rays: a stream needs device tensors")
+            rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+            n = len(rays)
+            if seeds is not None:
+                seeds = np.ascontiguousarray(seeds, np.uint32).ravel()
+                if len(seeds) != n:
+                    raise SptrError(f"render_rays: seeds must hold {n} words")
+            if out is None:
+                out = np.zeros((n, 3), np.float32)
+            elif not (isinstance(out, np.ndarray) and out.flags.c_contiguous and out.size == n * 3 and out.dtype == np.float32):
+                raise SptrError(f"render_rays: out must be a contiguous float32 array of {n} x 3")
+
+            def addr(a):
+                return a.ctypes.data
+        q = RayRender()
+        q.rays = addr(rays) if n else None
+        q.seeds = addr(seeds) if (seeds is not None and n) else None
+        q.n = n
+        q.samples = samples
+        q.frame_index = frame_index
+        q.max_depth = max_depth
+        q.flags = ((SPTR_RAYS_DEVICE_PTRS if device else 0) | (SPTR_RAYS_ACCUMULATE if accumulate else 0)
+                   | (SPTR_RAYS_NORMALIZE if normalize else 0))
+        q.radiance = addr(out) if n else None
+        if device and stream is None and n:
+            torch.cuda.current_stream(rays.device).synchronize()  # the rays' (and the output's) producers
+        self._check(self._L.sptr_render_rays(self._h, C.byref(q), C.c_void_p(stream) if stream else None), "render_rays")
+        return out
+
+    def ray_render_info(self) -> dict:
+        """sptr_ray_render_info: waits for the last render_rays call; its device ms, its closest-hit and any-hit
+        query counts and the chunks it ran in."""
+        ms, c, s, k = C.c_double(), C.c_uint64(), C.c_uint64(), C.c_uint32()
+        self._check(self._L.sptr_ray_render_info(self._h, C.byref(ms), C.byref(c), C.byref(s), C.byref(k)), "ray_render_info")
+        return {"ms": ms.value, "closest": c.value, "shadow": s.value, "chunks": k.value}
 
     def primary_rays(self, cam: Camera, width: int, height: int, acc: int):
         dirs = np.zeros((height, width, 3), np.float32)

@@ -37,6 +37,14 @@
 // --query-centre-rays: after the render, the W x H pixel-centre rays of the camera (the rays of the first-hit
 // AOVs: direction getRayDirection((x + 0.5) / W, (y + 0.5) / H), tnear 0, tfar inf) go through
 // HipBackend::queryRays; the --json line adds "query": {"rays": n, "hits": h, "tri_hits": k}.
+// --panorama W H: instead of the frames, an equirectangular panorama of W x H pixels from the camera position
+// through HipBackend::renderRays (sptr_render_rays): row y has polar angle theta = pi (y + 0.5) / H from +Y and
+// column x azimuth phi = 2 pi (x + 0.5) / W, both evaluated in float32 as written (float(pi) times the float
+// sum, then the division); their sines and cosines are those of the float32 angle taken in double and rounded
+// to float32; the direction is (sin theta cos phi, cos theta, sin theta sin phi) in float32.  --spp N gives every
+// ray N samples (frame indices 1 .. N), --depth the bounces.  --out takes the linear image, the mean radiance, as
+// a little-endian PFM (rows top to bottom in the file: scale -1, first row y = 0); the --json line is
+// {"panorama": [W, H], "samples", "depth", "ms", "closest", "shadow", "chunks"} (sptr_ray_render_info).
 #include <algorithm>
 #include <cmath>
 #include <chrono>
@@ -72,6 +80,7 @@ int main(int argc, char** argv) {
   std::string scene_name = "default", env = "sky", out = "image.ppm";
   int w = 800, h = 600, spp = 4, depth = 6, warmup = 0;
   bool json = false, lagged = false, rebuild = false, query_centre = false, motion = false, rigid = false;
+  int pano_w = 0, pano_h = 0;
   int animate = 0;
   std::string integrator = "wavefront";
   int spf = 4, launch_mode = 0, denoise = 0, history = 0;
@@ -102,8 +111,16 @@ int main(int argc, char** argv) {
     else if (a == "--rebuild") rebuild = true;
     else if (a == "--rigid") rigid = true;
     else if (a == "--query-centre-rays") query_centre = true;
+    else if (a == "--panorama") {
+      pano_w = std::atoi(next());
+      pano_h = std::atoi(next());
+      if (pano_w <= 0 || pano_h <= 0) {
+        std::fprintf(stderr, "--panorama W H: positive sizes\n");
+        return 2;
+      }
+    }
     else {
-      std::fprintf(stderr, "usage: %s [--scene S] [--w W] [--h H] [--spp N] [--depth D] [--env sky|F.hdr] [--out F] [--warmup N] [--json] [--lagged] [--denoise N] [--history [M]] [--motion] [--orbit DEG] [--animate K [--rebuild] [--rigid]] [--query-centre-rays]\n",
+      std::fprintf(stderr, "usage: %s [--scene S] [--w W] [--h H] [--spp N] [--depth D] [--env sky|F.hdr] [--out F] [--warmup N] [--json] [--lagged] [--denoise N] [--history [M]] [--motion] [--orbit DEG] [--animate K [--rebuild] [--rigid]] [--query-centre-rays] [--panorama W H]\n",
                    argv[0]);
       return 2;
     }
@@ -146,6 +163,44 @@ int main(int argc, char** argv) {
   if (!be.build(sd)) {
     std::fprintf(stderr, "%s\n", be.lastError().c_str());
     return 1;
+  }
+  if (pano_w > 0) {
+    const size_t n = size_t(pano_w) * size_t(pano_h);
+    std::vector<float> rays(n * 8, 0.0f), rad(n * 3, 0.0f);
+    const sptr_camera dc = cam.toDevice();
+    const float pi = 3.14159265358979323846f;
+    for (int y = 0; y < pano_h; ++y) {
+      const float th = pi * (float(y) + 0.5f) / float(pano_h);
+      const float st_ = float(std::sin(double(th))), ct = float(std::cos(double(th)));
+      for (int x = 0; x < pano_w; ++x) {
+        const float ph = 2.0f * pi * (float(x) + 0.5f) / float(pano_w);
+        const float sp = float(std::sin(double(ph))), cp = float(std::cos(double(ph)));
+        float* r = &rays[(size_t(y) * pano_w + x) * 8];
+        r[0] = dc.pos[0], r[1] = dc.pos[1], r[2] = dc.pos[2];
+        r[3] = st_ * cp, r[4] = ct, r[5] = st_ * sp;
+      }
+    }
+    backends::HipBackend::RayRenderInfo ri;
+    const uint32_t samples = uint32_t(std::max(1, spp));
+    if (!be.renderRays(rays.data(), nullptr, uint32_t(n), samples, 1u, rad.data(), false, false, &ri)) {
+      std::fprintf(stderr, "%s\n", be.lastError().c_str());
+      return 1;
+    }
+    for (float& v : rad) v /= float(samples);
+    if (json)
+      std::printf("{\"panorama\": [%d, %d], \"scene\": \"%s\", \"samples\": %u, \"depth\": %d, \"ms\": %.4f, \"closest\": %llu, "
+                  "\"shadow\": %llu, \"chunks\": %u}\n",
+                  pano_w, pano_h, scene_name.c_str(), samples, depth, ri.ms, (unsigned long long)ri.closest,
+                  (unsigned long long)ri.shadow, ri.chunks);
+    else
+      std::printf("scene=%s panorama %dx%d samples=%u depth=%d: %.2f ms device\n", scene_name.c_str(), pano_w, pano_h, samples,
+                  depth, ri.ms);
+    FILE* fp = std::fopen(out.c_str(), "wb");
+    if (!fp) return 1;
+    std::fprintf(fp, "PF\n%d %d\n-1.0\n", pano_w, pano_h);
+    std::fwrite(rad.data(), sizeof(float), rad.size(), fp);
+    std::fclose(fp);
+    return 0;
   }
   std::vector<unsigned char> img(size_t(w) * h * 3);
   if (warmup > 0) {
