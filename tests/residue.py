@@ -19,6 +19,18 @@ MAX_DIFF_1080P, MAX_DIFF_4K, MAX_REL_L1_FULL = 64, 256, 1e-5
 _SINCOS = {}
 
 
+def log_parity(name, rec):
+    """Measured fractions, printed and (SPTR_PARITY_LOG=<dir>) written as JSON for profiles/."""
+    import json
+
+    print(name, json.dumps(rec))
+    d = os.environ.get("SPTR_PARITY_LOG")
+    if d:
+        os.makedirs(d, exist_ok=True)
+        with open(os.path.join(d, f"{name}.json"), "w") as f:
+            json.dump(rec, f, indent=1)
+
+
 def device_sincos(renderer):
     """The GPU's (sin, cos) of the cosine sample's phi for all 2^24 values of r1 (cached, 128 MB)."""
     if "tab" not in _SINCOS:

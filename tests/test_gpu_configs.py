@@ -193,16 +193,7 @@ def _c5_fan_rows(flat, geom, prim):
     return (geom == mesh) & ((row == 0) | (row == wl.p0 - 1))
 
 
-def _log_parity(name, rec):
-    """Measured fractions, printed and (SPTR_PARITY_LOG=<dir>) written as JSON for profiles/."""
-    import json
-
-    print(name, json.dumps(rec))
-    d = os.environ.get("SPTR_PARITY_LOG")
-    if d:
-        os.makedirs(d, exist_ok=True)
-        with open(os.path.join(d, f"{name}.json"), "w") as f:
-            json.dump(rec, f, indent=1)
+_log_parity = residue.log_parity
 
 
 def test_c5_deep_bvh_first_hits(renderer, c5_scene):
