@@ -256,6 +256,22 @@ int sptr_sky_split_info(sptr_ctx* ctx, uint32_t* bulk_threads);
 /* Maximum primitives per BVH leaf range (1..16; 0 = automatic, the default: 8 for scenes staged in
  * LDS, 1 otherwise); applies to the next sptr_upload_scene. */
 int sptr_set_leaf_size(sptr_ctx* ctx, uint32_t max_prims);
+/* Order of the BVH2 of a scene staged in LDS with leaf ranges (leaf size > 1, no split references).
+ * 0 = automatic (the default): the references are ordered by a sweep-SAH tree built on the host at upload,
+ * which separates spheres from triangles and takes fewer primitive tests per ray than the Morton-order
+ * tree; 1 = Morton order.  Applies to the next sptr_upload_scene.  Hits do not depend on it, except which
+ * of two exactly tying primitives is reported.  Every other scene is in Morton order either way.
+ * sptr_tree_info, about the last upload: order = 0 SAH / 1 Morton; fallback = why Morton (0 = SAH in use,
+ * 1 = asked for, 2 = the scene is not of the kind above, 3 = a SAH path longer than 63 bits, 4 = SAH tree
+ * deeper than the Morton tree and than the walk's LDS stack, 5 = modelled cost not below the Morton
+ * tree's); depth and num_leaves of the tree in use, cost_sah / cost_morton = the builder's modelled cost of
+ * either tree (all four 0 when fallback is 1 or 2). */
+int sptr_set_tree_order(sptr_ctx* ctx, uint32_t mode);
+typedef struct sptr_tree_order_info {
+  uint32_t order, fallback, depth, num_leaves;
+  double cost_sah, cost_morton;
+} sptr_tree_order_info;
+int sptr_tree_info(const sptr_ctx* ctx, sptr_tree_order_info* out);
 /* Split references (early split clipping) for scenes traversed from L2/HBM: a triangle whose box is
  * much larger than the triangle (a sliver lying across the axes) is referenced up to max_pieces times,
  * each reference bounding one piece of it, so that rays near a fan of slivers stop testing every

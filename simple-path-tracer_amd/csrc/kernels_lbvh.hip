@@ -9,6 +9,8 @@
 //                   (early split clipping); every other primitive keeps one reference with its own box
 //   k_ref_bounds  : centroid bounds of the references (ordered-int atomics)
 //   k_morton      : 63-bit Morton code (21 bits/axis) of a reference's box centroid, value = reference id
+//   (host)        : scenes staged in LDS with leaf ranges: the keys become the references' paths in a
+//                   sweep-SAH tree (sah_order.h), so that the steps below build that tree; with leaf indices
 //   radix sort    : radix_sort_pairs_u64 on the codes (kernels_sort.hip, hand-written LSD, stable)
 //   k_leaves      : scatter triangles (v0, e1, e2, Ng precomputed as Embree's TriangleM does) and
 //                   spheres into sorted slots, one slot per reference (a split triangle's references
@@ -35,10 +37,13 @@
 #include <algorithm>
 #include <cfloat>
 #include <chrono>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <vector>
 
 #include "lbvh_shared.h"
+#include "sah_order.h"
 #include "sptr_internal.h"
 
 // treelet size (leaves) of the SAH restructuring of L2/HBM scenes' LBVH (r03u/v A/B); a restructured
@@ -351,8 +356,11 @@ __device__ __forceinline__ uint32_t range_link(uint32_t lo, uint32_t cnt) {
 
 // Karras 2012 hierarchy.  Child links become range leaves when the child subtree covers at most
 // leaf_max primitives; `kids` keeps the binary-tree child ids (leaf i -> kLeafBit | i) for refit.
-__global__ void k_karras(int N, const uint64_t* keys, uint32_t leaf_max, BvhNode* nodes, uint2* kids,
-                         uint32_t* leaf_parent) {
+// leaf_idx (SAH order, sah_order.h; else null): a child subtree is a range leaf iff its first and last
+// primitive carry the same leaf index (such a range never holds more than leaf_max).
+constexpr uint32_t kSmallReachable = 1u << 31;  // link.w: the walk reaches the node although it holds <= leaf_max
+__global__ void k_karras(int N, const uint64_t* keys, uint32_t leaf_max, const uint32_t* leaf_idx, BvhNode* nodes,
+                         uint2* kids, uint32_t* leaf_parent) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < N - 1; i += gridDim.x * blockDim.x) {
     const int d = (delta(keys, N, i, i + 1) - delta(keys, N, i, i - 1)) >= 0 ? 1 : -1;
     const int dmin = delta(keys, N, i, i - d);
@@ -387,9 +395,14 @@ __global__ void k_karras(int N, const uint64_t* keys, uint32_t leaf_max, BvhNode
       nodes[gamma + 1].link.z = (uint32_t)i;
     }
     const uint32_t nl = (uint32_t)(gamma - lo + 1), nr = (uint32_t)(hi - gamma);
-    nodes[i].link.x = nl <= leaf_max ? range_link((uint32_t)lo, nl) : kl;
-    nodes[i].link.y = nr <= leaf_max ? range_link((uint32_t)(gamma + 1), nr) : kr;
-    nodes[i].link.w = (uint32_t)(hi - lo + 1);  // primitives under node i (reachability test)
+    const bool ll = leaf_idx ? leaf_idx[lo] == leaf_idx[gamma] : nl <= leaf_max;
+    const bool rl = leaf_idx ? leaf_idx[gamma + 1] == leaf_idx[hi] : nr <= leaf_max;
+    nodes[i].link.x = ll ? range_link((uint32_t)lo, nl) : kl;
+    nodes[i].link.y = rl ? range_link((uint32_t)(gamma + 1), nr) : kr;
+    // primitives under node i (reachability test: k_tree_cost skips a node with at most leaf_max, which
+    // lies inside its parent's leaf range, unless the SAH order made it a node of the walk)
+    const uint32_t cnt = (uint32_t)(hi - lo + 1);
+    nodes[i].link.w = cnt | ((leaf_idx && cnt <= leaf_max && leaf_idx[lo] != leaf_idx[hi]) ? kSmallReachable : 0u);
     kids[i] = make_uint2(kl, kr);
   }
 }
@@ -929,6 +942,82 @@ int build_lbvh(Context& c, const float* h_pos, uint32_t nverts, const uint32_t* 
   hipLaunchKernelGGL(k_ref_bounds, dim3(blocks_for(NR)), dim3(256), 0, s, NR, blo, bhi, cb);
   hipLaunchKernelGGL(k_morton, dim3(blocks_for(NR)), dim3(256), 0, s, in, NR, blo, bhi, rprim, cb, keys, vals, dmax);
   LB_CHECK(hipGetLastError());
+  // automatic leaf size (measured, profiles/r01*, r02g_leaf.txt): ranges of 8 for scenes small enough
+  // to be staged in LDS (fewer, divergence-free node steps), single primitives for meshes traversed
+  // from L2/HBM (with the greedy wide collapse: C5 14.9 -> 13.9, C3 5.04 -> 4.87 ms/step vs 2)
+  auto leaf_max_for = [&](uint32_t n) {
+    const uint32_t auto_leaf = ((uint64_t)(n > 1 ? n - 1 : 0) * 64 + (uint64_t)ntri_refs * 48 + (uint64_t)nsph * 16 +
+                                ((uint64_t)n + 3) / 4 * 16) <= kLdsSceneBytes ? 8u : 1u;
+    return std::max(1u, std::min(c.leaf_size ? c.leaf_size : auto_leaf, kMaxLeafSize));
+  };
+  // SAH order (sah_order.h) for the scenes staged in LDS: the references' keys become their paths in a
+  // sweep-SAH tree built here on the host (a few hundred references at most), so that the sort and k_karras
+  // below build that tree instead of the Morton-order one; leaf_idx tells k_karras its leaf ranges.
+  // Degenerate references keep their keys (bit 63: sorted last, outside the tree); the paths use the other
+  // 63 bits.  Falls back to the Morton keys when the SAH tree is no better by its own model or deeper than
+  // both the Morton tree and the LDS part of the walk's stack (sah_order_choose).
+  uint32_t* leaf_idx = nullptr;
+  uint32_t tree_order = c.tree_order;
+  SahCosts sah_k;
+  if (const char* e = getenv("SPTR_TREE_ORDER"); e && tree_order == 0u) {  // "mode[,cn,ct,cs]" (A/B)
+    float cn = 0.0f, ct = 0.0f, cs = 0.0f;
+    unsigned m = 0u;
+    const int got = sscanf(e, "%u,%f,%f,%f", &m, &cn, &ct, &cs);
+    if (got >= 1) tree_order = m == 1u ? 1u : 0u;
+    if (got == 4 && cn > 0.0f && ct > 0.0f && cs > 0.0f) sah_k = SahCosts{cn, ct, cs};
+  }
+  c.tree_info = Context::TreeInfo{};
+  c.tree_info.fallback = tree_order == 1u ? kSahOff : kSahNotStaged;
+  if (tree_order != 1u && small && max_pieces == 1u && NR >= 2u) {
+    std::vector<float4> hlo(NR), hhi(NR);
+    std::vector<uint64_t> hkey(NR);
+    std::vector<uint32_t> hprim(NR);
+    LB_CHECK(hipMemcpyAsync(hlo.data(), blo, (size_t)NR * 16, hipMemcpyDeviceToHost, s));
+    LB_CHECK(hipMemcpyAsync(hhi.data(), bhi, (size_t)NR * 16, hipMemcpyDeviceToHost, s));
+    LB_CHECK(hipMemcpyAsync(hkey.data(), keys, (size_t)NR * 8, hipMemcpyDeviceToHost, s));
+    LB_CHECK(hipMemcpyAsync(hprim.data(), rprim, (size_t)NR * 4, hipMemcpyDeviceToHost, s));
+    LB_CHECK(hipStreamSynchronize(s));
+    std::vector<uint32_t> live;  // the references the tree is built over
+    for (uint32_t i = 0; i < NR; ++i)
+      if (!(hkey[i] >> 63)) live.push_back(i);
+    if (live.empty())  // every primitive degenerate: the tree is built over all of them (below)
+      for (uint32_t i = 0; i < NR; ++i) live.push_back(i);
+    const uint32_t n = (uint32_t)live.size(), lm = leaf_max_for(n);
+    if (n >= 2u && lm > 1u) {
+      std::vector<SahBox> box(n);
+      std::vector<uint8_t> is_tri(n);
+      std::vector<uint64_t> mkey(n);
+      for (uint32_t j = 0; j < n; ++j) {
+        const float4 a = hlo[live[j]], b = hhi[live[j]];
+        box[j] = SahBox{{a.x, a.y, a.z}, {b.x, b.y, b.z}};
+        is_tri[j] = hprim[live[j]] < ntris ? 1 : 0;
+        mkey[j] = hkey[live[j]];
+      }
+      const bool all_deg = n == NR && (hkey[0] >> 63);
+      // kSahStackFree: kLdsStack of kernels_wavefront.hip, the stack entries of a staged scene's walk held in LDS
+      constexpr uint32_t kSahStackFree = 12;
+      const SahChoice ch = sah_order_choose(box.data(), is_tri.data(), mkey.data(), n, lm, sah_k, 63u, kSahStackFree);
+      c.tree_info.fallback = ch.fallback;
+      c.tree_info.cost_sah = ch.sah.tree.cost;
+      c.tree_info.cost_morton = ch.morton.cost;
+      c.tree_info.depth = ch.morton.depth;
+      c.tree_info.leaves = ch.morton.leaves;
+      if (ch.fallback == kSahNone) {
+        c.tree_info.order = 0u;
+        c.tree_info.depth = ch.sah.tree.depth;
+        c.tree_info.leaves = ch.sah.tree.leaves;
+        std::vector<uint32_t> hleaf(NR, ~0u);
+        for (uint32_t j = 0; j < n; ++j) {
+          hkey[live[j]] = (ch.sah.key[j] >> 1) | (all_deg ? (1ull << 63) : 0ull);
+          hleaf[j] = ch.sah.leaf[ch.sah.order[j]];  // sorted position j holds reference order[j]
+        }
+        LB_CHECK(tmp.alloc(&leaf_idx, NR));
+        LB_CHECK(hipMemcpyAsync(keys, hkey.data(), (size_t)NR * 8, hipMemcpyHostToDevice, s));
+        LB_CHECK(hipMemcpyAsync(leaf_idx, hleaf.data(), (size_t)NR * 4, hipMemcpyHostToDevice, s));
+        LB_CHECK(hipStreamSynchronize(s));  // the host vectors go out of scope
+      }
+    }
+  }
   size_t tbytes = 0;
   LB_CHECK(radix_sort_pairs_u64(nullptr, tbytes, keys, keys_s, vals, vals_s, NR, s));
   void* tstore = nullptr;
@@ -955,12 +1044,7 @@ int build_lbvh(Context& c, const float* h_pos, uint32_t nverts, const uint32_t* 
   const uint32_t N = ndeg < NR ? NR - ndeg : NR;
   c.excluded_prims = NR - N;
   c.num_nodes = N > 1 ? N - 1 : 0;
-  // automatic leaf size (measured, profiles/r01*, r02g_leaf.txt): ranges of 8 for scenes small enough
-  // to be staged in LDS (fewer, divergence-free node steps), single primitives for meshes traversed
-  // from L2/HBM (with the greedy wide collapse: C5 14.9 -> 13.9, C3 5.04 -> 4.87 ms/step vs 2)
-  const uint32_t auto_leaf = ((uint64_t)(N > 1 ? N - 1 : 0) * 64 + (uint64_t)ntri_refs * 48 + (uint64_t)nsph * 16 +
-                              ((uint64_t)N + 3) / 4 * 16) <= kLdsSceneBytes ? 8u : 1u;
-  const uint32_t leaf_max = std::max(1u, std::min(c.leaf_size ? c.leaf_size : auto_leaf, kMaxLeafSize));
+  const uint32_t leaf_max = leaf_max_for(N);
   c.leaf_used = leaf_max;
   if (N == 1) {
     c.root = kLeafBit | 0u;  // range [0, 1)
@@ -975,7 +1059,7 @@ int build_lbvh(Context& c, const float* h_pos, uint32_t nverts, const uint32_t* 
     uint32_t dep = 0;
     {
       LB_CHECK(hipMemsetAsync(rflags, 0, (size_t)N * 4, s));
-      hipLaunchKernelGGL(k_karras, dim3(blocks_for(N)), dim3(256), 0, s, (int)N, keys_s, leaf_max, nodes, kids,
+      hipLaunchKernelGGL(k_karras, dim3(blocks_for(N)), dim3(256), 0, s, (int)N, keys_s, leaf_max, leaf_idx, nodes, kids,
                          leaf_parent);
       hipLaunchKernelGGL(k_refit, dim3(blocks_for(N)), dim3(256), 0, s, (int)N, vals_s, blo, bhi, kids, leaf_parent,
                          nodes, rflags, dmax);
@@ -1061,7 +1145,8 @@ int build_lbvh(Context& c, const float* h_pos, uint32_t nverts, const uint32_t* 
       LB_CHECK(hipGetLastError());
       LB_CHECK(hipStreamSynchronize(s));  // bh is read by the copy above
     }
-    c.root = N <= leaf_max ? (kLeafBit | (N - 1u)) : 0u;  // whole scene in one leaf range, or node 0
+    // whole scene in one leaf range, or node 0
+    c.root = (leaf_idx ? c.tree_info.leaves == 1u : N <= leaf_max) ? (kLeafBit | (N - 1u)) : 0u;
     c.bvh_depth = dep;
     // a BVH2 node at depth d holds at most d pushed entries and pushes one more; a wide node (BVH2
     // depth kWideLevels*dw) holds at most (kWide-1)*dw and pushes up to kWide-1 more; internal nodes

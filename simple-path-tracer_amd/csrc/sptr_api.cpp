@@ -1621,6 +1621,14 @@ static int set_leaf_size_one(sptr_ctx* x, uint32_t n) {
   return SPTR_OK;
 }
 
+static int set_tree_order_one(sptr_ctx* x, uint32_t mode) {
+  if (!x) return SPTR_ERR_INVALID;
+  if (mode > 1u) return fail(x->c, SPTR_ERR_INVALID, "tree order must be 0 (automatic) or 1 (Morton)");
+  x->c.tree_order = mode;
+  ++x->c.epoch;
+  return SPTR_OK;
+}
+
 static int set_bvh_width_one(sptr_ctx* x, uint32_t width) {
   if (!x) return SPTR_ERR_INVALID;
   if (width != 0 && width != 2 && width != (uint32_t)kWide)
@@ -3532,6 +3540,23 @@ int sptr_set_debug_mode(sptr_ctx* x, int mode) { return lane_shading_changed(x, 
 int sptr_set_leaf_size(sptr_ctx* x, uint32_t n) {
   const int rc = set_leaf_size_one(x, n);
   return rc == SPTR_OK ? lane_forward(x, set_leaf_size_one(x ? x->lane : nullptr, n)) : rc;
+}
+
+int sptr_set_tree_order(sptr_ctx* x, uint32_t mode) {
+  const int rc = set_tree_order_one(x, mode);
+  return rc == SPTR_OK ? lane_forward(x, set_tree_order_one(x ? x->lane : nullptr, mode)) : rc;
+}
+
+int sptr_tree_info(const sptr_ctx* x, sptr_tree_order_info* out) {
+  if (!x || !out) return SPTR_ERR_INVALID;
+  const Context::TreeInfo& t = x->c.tree_info;
+  out->order = t.order;
+  out->fallback = t.fallback;
+  out->depth = t.depth;
+  out->num_leaves = t.leaves;
+  out->cost_sah = t.cost_sah;
+  out->cost_morton = t.cost_morton;
+  return SPTR_OK;
 }
 
 int sptr_set_bvh_width(sptr_ctx* x, uint32_t width) {

@@ -534,6 +534,11 @@ struct Context {
   uint32_t bvh_width = 0;  // traversal width: 2 (LBVH as built), 4 (collapsed), 0 = automatic
   uint32_t leaf_used = 0;  // leaf size the current BVH was built with
   uint32_t treelet_passes = SPTR_TREELET_PASSES;  // SAH treelet passes over L2/HBM scenes' LBVH (kernels_lbvh.hip)
+  uint32_t tree_order = 0;  // sptr_set_tree_order: 0 = automatic (SAH order for LDS-staged scenes, sah_order.h), 1 = Morton
+  struct TreeInfo {  // the last upload's tree (sptr_tree_info)
+    uint32_t order = 1, fallback = 2, depth = 0, leaves = 0;
+    double cost_sah = 0.0, cost_morton = 0.0;
+  } tree_info;
   uint32_t num_nodes = 0, num_tris = 0, num_sph = 0, root = 0, bvh_depth = 0;
   uint32_t num_tri_refs = 0;     // triangle references = triangle slots (split references, kernels_lbvh.hip)
   uint32_t split_pieces = 1;     // most references per split triangle (sptr_set_split_refs; 1 = no splits, the default)

@@ -113,6 +113,11 @@ class SceneLayout(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class TreeOrderInfo(C.Structure):
+    _fields_ = [("order", C.c_uint32), ("fallback", C.c_uint32), ("depth", C.c_uint32), ("num_leaves", C.c_uint32),
+                ("cost_sah", C.c_double), ("cost_morton", C.c_double)]
+
+
 class DenoiseParams(C.Structure):
     _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_depth", C.c_float),
                 ("sigma_albedo", C.c_float), ("normal_log2_power", C.c_uint32), ("reserved", C.c_uint32 * 3)]
@@ -146,7 +151,7 @@ _lib = None
 # every symbol include/sptr_hip.h declares
 EXPORTS = [
     "sptr_abi_version", "sptr_create", "sptr_destroy", "sptr_last_error", "sptr_set_debug_mode",
-    "sptr_set_wave_paths", "sptr_set_launch_mode", "sptr_set_pixel_lanes", "sptr_pixel_lanes_info", "sptr_graph_info", "sptr_capture_error", "sptr_overlap_probe", "sptr_set_tail_depth", "sptr_set_bounce_chain", "sptr_set_sky_split", "sptr_sky_split_info", "sptr_set_leaf_size", "sptr_set_split_refs", "sptr_set_stragglers", "sptr_set_bvh_width", "sptr_upload_scene", "sptr_set_materials", "sptr_set_lights",
+    "sptr_set_wave_paths", "sptr_set_launch_mode", "sptr_set_pixel_lanes", "sptr_pixel_lanes_info", "sptr_graph_info", "sptr_capture_error", "sptr_overlap_probe", "sptr_set_tail_depth", "sptr_set_bounce_chain", "sptr_set_sky_split", "sptr_sky_split_info", "sptr_set_leaf_size", "sptr_set_tree_order", "sptr_tree_info", "sptr_set_split_refs", "sptr_set_stragglers", "sptr_set_bvh_width", "sptr_upload_scene", "sptr_set_materials", "sptr_set_lights",
     "sptr_set_environment", "sptr_scene_info", "sptr_scene_layout_info", "sptr_render", "sptr_collect_stats",
     "sptr_read_rgb8", "sptr_read_rgb8_lagged",
     "sptr_read_accum",
@@ -192,6 +197,8 @@ def lib() -> C.CDLL:
         "sptr_set_sky_split": (C.c_int, [vp, u32, u32]),
         "sptr_sky_split_info": (C.c_int, [vp, C.POINTER(u32)]),
         "sptr_set_leaf_size": (C.c_int, [vp, u32]),
+        "sptr_set_tree_order": (C.c_int, [vp, u32]),
+        "sptr_tree_info": (C.c_int, [vp, C.POINTER(TreeOrderInfo)]),
         "sptr_set_split_refs": (C.c_int, [vp, u32]),
         "sptr_set_stragglers": (C.c_int, [vp, u32]),
         "sptr_set_bvh_width": (C.c_int, [vp, u32]),
@@ -593,6 +600,17 @@ class Renderer:
 
     def set_leaf_size(self, n: int):
         self._check(self._L.sptr_set_leaf_size(self._h, n), "set_leaf_size")
+
+    def set_tree_order(self, mode: int):
+        """sptr_set_tree_order: 0 automatic (SAH order for LDS-staged scenes), 1 Morton; next upload."""
+        self._check(self._L.sptr_set_tree_order(self._h, mode), "set_tree_order")
+
+    def tree_info(self) -> dict:
+        """sptr_tree_info: {"order": 0 SAH / 1 Morton, "fallback": why Morton (0: SAH in use), "depth",
+        "num_leaves", "cost_sah", "cost_morton"} of the last upload."""
+        t = TreeOrderInfo()
+        self._check(self._L.sptr_tree_info(self._h, C.byref(t)), "tree_info")
+        return {k: getattr(t, k) for k, _ in TreeOrderInfo._fields_}
 
     def set_split_refs(self, max_pieces: int):
         """sptr_set_split_refs: most references per split triangle (0 = default 1: none); next upload."""
