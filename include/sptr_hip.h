@@ -693,6 +693,68 @@ int sptr_render_rays(sptr_ctx* ctx, const sptr_ray_render* batch, void* stream);
  * traversal-stack or stream-overflow flag (a synchronous call checks them itself).  Any pointer may be NULL. */
 int sptr_ray_render_info(sptr_ctx* ctx, double* ms, uint64_t* closest, uint64_t* shadow, uint32_t* chunks);
 
+/* ---- adaptive sampling (symbols added within ABI 9: no existing struct or entry point changed) ------------
+ * sptr_render takes spp samples at every pixel; this entry point keeps sampling only the pixels that have not
+ * converged.  It is not a second integrator: a selection compacts the unconverged ("active") local pixels into
+ * a list, a producer writes their next camera rays into the integrator's ray stream, the chain sptr_render_rays
+ * uses runs them from depth 0, and a consumer folds the radiance into the per-pixel state.
+ *
+ * State per local pixel: S, the RGB sum of all its samples (the context's accumulation buffer: sptr_read_accum
+ * returns it); E, the RGB sum of its samples with an even index; n, the samples taken (sptr_read_sample_counts).
+ * Sample i (1-based) of a pixel is the sample frame i of sptr_render takes there (with sptr_set_seed_offset's
+ * offset as a render call applies it); S = S + L_i is one add per component in index order from +0, E likewise
+ * for even i.
+ * Error of a pixel, in float32, every operation correctly rounded and none contracted:
+ *   nf = float(n), hf = float(n / 2); I = S / nf, A = E / hf (per component);
+ *   err = ((|I.r - A.r| + |I.g - A.g|) + |I.b - A.b|) / sqrt(max((I.r + I.g) + I.b, 1e-4f))
+ * A pixel is active iff n < max_samples && !(n >= min_samples && err < threshold); a NaN err keeps it active.
+ * Passes: every active pixel with n == 0 takes min_samples samples, any other min(step, max_samples - n); then
+ * the selection runs again, until no pixel is active.  The selection is a pure function of the state and the
+ * parameters, so a call with max 16 continued with max 32 equals one call with max 32, and with threshold 0 the
+ * result is sptr_render's accumulation of max_samples frames, bit for bit.
+ *
+ * frame: width, height, camera, max_depth, shard_rank and shard_count as sptr_render reads them; frame_begin
+ * must be 1, spp is ignored, the integrator must be SPTR_INTEGRATOR_WAVEFRONT, and the only flag accepted is
+ * SPTR_FRAME_NO_RESOLVE.  Without it the call ends with a resolve of every pixel by its own n into the tiles
+ * and the RGB8 image (sptr_read_rgb8, sptr_tiles_device and a multi-GPU gather work as after sptr_render).
+ * Without SPTR_ADAPTIVE_CONTINUE the call starts a new accumulation (S = E = 0, n = 0); with it the call goes
+ * on from the state the context's last adaptive call left, under the new parameters: the size, camera, depth,
+ * shard and state epoch (scene, materials, lights, environment, settings) must be unchanged and no render call
+ * may have run in between, else SPTR_ERR_INVALID.
+ * The call is synchronous: after each selection the host reads the selection's result words (the list length
+ * among them) to size the next pass, and it returns when the image is written.  It follows the scene,
+ * materials, lights, environment, debug mode and refits as a render call does; its rays are counted in info
+ * only, never in a later call's sptr_stats.  Afterwards a sptr_render with frame_begin != 1 is SPTR_ERR_INVALID
+ * (the accumulation holds unequal counts), one with frame_begin == 1 behaves as ever.
+ * SPTR_ERR_INVALID: the denoiser is on, a lane context, a parameter outside its bounds, an unknown flag, a
+ * non-zero reserved word, frame parameters sptr_render would reject; SPTR_ERR_NO_SCENE as for sptr_render;
+ * SPTR_ERR_HIP if a launch set the traversal-stack or stream-overflow flag or a guard word of the state was
+ * overwritten (internal errors). */
+enum { SPTR_ADAPTIVE_CONTINUE = 1u };
+typedef struct sptr_adaptive_params {
+  float threshold;       /* >= 0, finite */
+  uint32_t min_samples;  /* >= 2 */
+  uint32_t max_samples;  /* >= min_samples, <= 65536 */
+  uint32_t step;         /* >= 1 */
+  uint32_t flags;
+  uint32_t reserved[3];  /* 0 */
+} sptr_adaptive_params;
+typedef struct sptr_adaptive_info {
+  uint64_t samples;          /* taken by this call = sum of the increase of n */
+  uint64_t rays_closest, rays_shadow;
+  uint32_t passes, chunks;
+  uint32_t active_first, active_last;   /* list lengths of the first and last pass */
+  uint32_t min_count, max_count;        /* over valid local pixels, after the call */
+  double ms;                            /* device time, first launch to last */
+  uint32_t reserved[4];
+} sptr_adaptive_info;
+/* info may be NULL. */
+int sptr_render_adaptive(sptr_ctx* ctx, const sptr_frame* frame, const sptr_adaptive_params* params,
+                         sptr_adaptive_info* info);
+/* counts: width * height words of the last adaptive call's image, row-major; pixels of other shards 0.
+ * SPTR_ERR_INVALID when the context holds no adaptive state. */
+int sptr_read_sample_counts(sptr_ctx* ctx, uint32_t* counts);
+
 /* ---- query entry points (tests / tooling) -------------------------------------------------------- */
 /* Closest-hit / any-hit queries on the device BVH: rays = n*8 floats (o3, d3, tnear, tfar).
  * Outputs as rtcIntersect1 reports them: geomID (0xFFFFFFFF on miss), primID, t, unnormalised Ng. */

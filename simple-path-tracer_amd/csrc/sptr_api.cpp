@@ -117,6 +117,21 @@ struct sptr_ctx {
     bool issued = false;
     uint32_t chunks = 0;
   } rr;
+  // sptr_render_adaptive (the caller's context; a pixel lane holds none): the state beside the accumulation, the
+  // list and the selection's words in one block with guard runs (AdaptiveBufs), the call's own totals block, and
+  // what a call with SPTR_ADAPTIVE_CONTINUE must find unchanged.  The state is valid while Context::last_samples
+  // holds kAdaptiveMark: every render call and every new pixel layout overwrites that.
+  struct Adaptive {
+    sptr::DevBuf state, tot;
+    sptr::AdaptiveBufs bufs{};
+    uint32_t P = 0;  // the local pixels `state` is laid out for
+    sptr::DevEvent ev[2];
+    bool valid = false;
+    sptr_camera cam{};
+    int W = 0, H = 0, G = 0, R = 0;
+    uint32_t max_depth = 0;
+    uint64_t epoch = 0;
+  } ad;
   // Waits for everything that may still use this context's resources, then lets the lane go; the members
   // free themselves after that (in reverse order of declaration: c, with its streams, last).
   ~sptr_ctx() {
@@ -2599,6 +2614,265 @@ int sptr_ray_render_info(sptr_ctx* x, double* ms, uint64_t* closest, uint64_t* s
   if (shadow) *shadow = tot[kTotShadow];
   if (chunks) *chunks = rr.issued ? rr.chunks : 0u;
   return rc;
+}
+
+// ---- adaptive sampling ------------------------------------------------------------------
+// Context::last_samples after an adaptive call: no frame_begin continues it (frame_begin + 0 == 0 is rejected)
+constexpr uint32_t kAdaptiveMark = 0xFFFFFFFFu;
+constexpr uint32_t kAdaptiveMaxSamples = 65536u;
+
+// the state block for P local pixels: guard | E | guard | n | guard | list | guard | block words | result
+static int ensure_adaptive(sptr_ctx* x, uint32_t P) {
+  Context& c = x->c;
+  auto& ad = x->ad;
+  if (ad.state.p && ad.P == P) return SPTR_OK;
+  const size_t g = kAdaptiveGuardWords;
+  size_t off[4], w = 0;
+  off[0] = w, w += g;
+  const size_t wE = w;
+  w += (size_t)P * 4;
+  off[1] = w, w += g;
+  const size_t wn = w;
+  w += P;
+  off[2] = w, w += g;
+  const size_t wl = w;
+  w += P;
+  off[3] = w, w += g;
+  const size_t wb = w;
+  w += (size_t)kMaxSegs * kAdaptiveStatWords;
+  const size_t wr = w;
+  w += kAdaptiveResWords;
+  ad.valid = false;
+  API_HIP(ad.state.ensure(w * 4));
+  uint32_t* base = static_cast<uint32_t*>(ad.state.p);
+  API_HIP(hipMemset(base, 0, w * 4));
+  const std::vector<uint32_t> guard(g, kAdaptiveGuardValue);
+  for (int k = 0; k < 4; ++k) {
+    API_HIP(hipMemcpy(base + off[k], guard.data(), g * 4, hipMemcpyHostToDevice));
+    ad.bufs.guard_off[k] = (uint32_t)off[k];
+  }
+  ad.bufs.base = base;
+  ad.bufs.E = reinterpret_cast<float4*>(base + wE);  // (16-byte aligned: the guard run is 64 B)
+  ad.bufs.n = base + wn;
+  ad.bufs.list = base + wl;
+  ad.bufs.bstat = base + wb;
+  ad.bufs.result = base + wr;
+  ad.P = P;
+  return SPTR_OK;
+}
+
+// One group of a pass: the first `count` list entries take `take` samples each, in chunks of at most cap paths.
+// Per chunk: k_adapt_inject, the chain of enqueue_ray_render, k_adapt_gather.
+static int enqueue_adaptive_group(sptr_ctx* x, const FrameView& fv, const FrameView& fchain, uint32_t count, uint32_t take,
+                                  uint64_t cap, uint32_t& chunks_out) {
+  Context& c = x->c;
+  const hipStream_t s = c.stream;
+  const SceneView sv = scene_view(c);
+  const ShadeView sh = shade_view(c);
+  WaveView w = wave_view(c);
+  w.tot = static_cast<unsigned long long*>(x->ad.tot.p);
+  const bool fuse = shade_fuses_shadows(sv, sh, false);
+  const int D = (int)fv.max_depth;
+  const uint64_t chunks = ray_chunk_count(count, take, cap);
+  for (uint64_t ci = 0; ci < chunks; ++ci) {
+    const RayChunk ck = ray_chunk_at(count, take, cap, ci);
+    const uint64_t np = (uint64_t)ck.nrays * ck.ns;
+    const int T = std::max(1, (int)(c.tail_depth ? c.tail_depth : auto_tail_depth(np, sv)));
+    uint32_t g_shade = launch_adapt_inject(x->ad.bufs, ck, c.seed_offset, fv, w, s);
+    for (int d = 0; d < D; ++d) {
+      if (d >= T) {
+        launch_tail(sv, sh, fchain, w, d, g_shade, s);
+        break;
+      }
+      const uint32_t g_trace = launch_trace(sv, sh, fchain, w, d, false, g_shade, s, true);
+      g_shade = launch_shade(sv, sh, fchain, w, d, g_trace, fuse, s, true);
+      if (!fuse) launch_shadow(sv, sh, w, d, false, g_shade, s);
+    }
+    launch_adapt_gather(x->ad.bufs, ck, fv, w, s);
+    API_HIP(hipGetLastError());
+  }
+  chunks_out += (uint32_t)chunks;
+  return SPTR_OK;
+}
+
+int sptr_render_adaptive(sptr_ctx* x, const sptr_frame* f, const sptr_adaptive_params* p, sptr_adaptive_info* info) {
+  if (!x || !f || !p) return SPTR_ERR_INVALID;
+  Context& c = x->c;
+  auto& ad = x->ad;
+  if (info) std::memset(info, 0, sizeof(*info));
+  if (x->is_lane) return fail(c, SPTR_ERR_INVALID, "render_adaptive: not on a lane context");
+  API_HIP(hipSetDevice(c.device));
+  if (!c.have_scene) return fail(c, SPTR_ERR_NO_SCENE, "render_adaptive: no scene uploaded");
+  if (shading(c).mats_host.empty()) return fail(c, SPTR_ERR_NO_SCENE, "render_adaptive: no materials set");
+  if (x->dn.p.iterations != 0u) return fail(c, SPTR_ERR_INVALID, "render_adaptive: the denoiser is on (sptr_set_denoise)");
+  if (p->flags & ~(uint32_t)SPTR_ADAPTIVE_CONTINUE) return fail(c, SPTR_ERR_INVALID, "render_adaptive: unknown flags");
+  for (uint32_t r : p->reserved)
+    if (r) return fail(c, SPTR_ERR_INVALID, "render_adaptive: reserved words must be 0");
+  if (!(p->threshold >= 0.0f) || !std::isfinite(p->threshold) || p->min_samples < 2u || p->max_samples < p->min_samples ||
+      p->max_samples > kAdaptiveMaxSamples || p->step < 1u)
+    return fail(c, SPTR_ERR_INVALID, "render_adaptive: parameters out of bounds");
+  if (f->width <= 0 || f->height <= 0 || f->max_depth == 0 || f->max_depth > (uint32_t)kMaxDepth || f->frame_begin != 1u)
+    return fail(c, SPTR_ERR_INVALID, "render_adaptive: bad frame parameters (frame_begin must be 1)");
+  if (f->integrator != SPTR_INTEGRATOR_WAVEFRONT)
+    return fail(c, SPTR_ERR_INVALID, "render_adaptive: SPTR_INTEGRATOR_WAVEFRONT only");
+  if (f->flags & ~(uint32_t)SPTR_FRAME_NO_RESOLVE)
+    return fail(c, SPTR_ERR_INVALID, "render_adaptive: the only frame flag accepted is SPTR_FRAME_NO_RESOLVE");
+  const int G = f->shard_count > 0 ? f->shard_count : 1, R = f->shard_count > 0 ? f->shard_rank : 0;
+  if (R < 0 || R >= G) return fail(c, SPTR_ERR_INVALID, "render_adaptive: shard_rank out of range");
+  const int ntiles = ((f->width + kTile - 1) / kTile) * ((f->height + kTile - 1) / kTile);
+  if (R >= ntiles) return fail(c, SPTR_ERR_INVALID, "render_adaptive: more shards than tiles");
+  if ((uint64_t)f->width * f->height > (1ull << 28)) return fail(c, SPTR_ERR_INVALID, "render_adaptive: image too large");
+  if ((uint64_t)c.seed_offset + p->max_samples > 0xFFFFFFFFull)
+    return fail(c, SPTR_ERR_INVALID, "render_adaptive: seed offset + max_samples overflows 32 bits");
+  const bool cont = (p->flags & SPTR_ADAPTIVE_CONTINUE) != 0u;
+  if (cont) {
+    const bool same = ad.valid && !x->split && c.last_samples == kAdaptiveMark && ad.W == f->width && ad.H == f->height &&
+                      ad.G == G && ad.R == R && c.W == f->width && c.H == f->height && c.G == G && c.R == R &&
+                      ad.max_depth == f->max_depth && ad.epoch == c.epoch && std::memcmp(&ad.cam, &f->camera, sizeof(sptr_camera)) == 0;
+    if (!same)
+      return fail(c, SPTR_ERR_INVALID, "render_adaptive: SPTR_ADAPTIVE_CONTINUE needs the last adaptive call's size, camera, depth, shard and state");
+  }
+  // synchronous: everything pending on the context ends first
+  if (sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;
+  if (x->split) {  // leaving a two-lane accumulation, as a one-lane render call does
+    if (sync_pending(x->lane->c) != SPTR_OK) return SPTR_ERR_HIP;
+    x->split = false;
+    c.W = 0;
+  }
+  const hipStream_t s = c.stream;
+  bool resized = false;
+  int rc = ensure_pixels(c, f->width, f->height, G, R, s, resized);
+  if (rc != SPTR_OK) return rc;
+  // wave capacity as sptr_render_rays takes it: the buffers the context has, or a capacity of the ray path's own
+  uint64_t cap = rays_wave_capacity(c);
+  if (cap == 0) {
+    const uint64_t want = c.wb.cap ? c.wb.cap : std::min<uint64_t>(kRaysOwnPaths, (uint64_t)c.P * p->min_samples);
+    rc = ensure_wave(c, want, (uint32_t)shading(c).lights_host.size(), task_stride(c), 1u, hrec_mult(scene_view(c)));
+    if (rc != SPTR_OK) return rc;
+    cap = rays_wave_capacity(c);
+    if (cap == 0) return fail(c, SPTR_ERR_HIP, "render_adaptive: no wave capacity (internal error)");
+  }
+  if (c.wave_paths) cap = std::min<uint64_t>(cap, c.wave_paths);
+  if (cont && ad.epoch != c.epoch) return fail(c, SPTR_ERR_INVALID, "render_adaptive: the state changed since the last adaptive call");
+  rc = ensure_adaptive(x, c.P);
+  if (rc != SPTR_OK) return rc;
+  if (!ad.tot.p) API_HIP(ad.tot.ensure(kTotWords * 8));
+  for (DevEvent& e : ad.ev)
+    if (!e) API_HIP(hipEventCreate(e.put()));
+  ad.valid = false;
+  c.last_samples = kAdaptiveMark;
+  x->dn.ran = false;
+  x->dn.last_cam = f->camera;
+  x->dn.last_W = f->width;
+  x->dn.last_H = f->height;
+
+  const FrameView fv = frame_view(c, *f);
+  sptr_frame fc{};  // the chain's frame, as enqueue_ray_render builds it (its stages read max_depth only)
+  fc.width = fc.height = 1;
+  fc.frame_begin = 1;
+  fc.spp = 1;
+  fc.max_depth = f->max_depth;
+  const FrameView fchain = frame_view(c, fc);
+  const AdaptiveRule rule{p->threshold, p->min_samples, p->max_samples, p->step};
+
+  API_HIP(hipMemsetAsync(ad.tot.p, 0, kTotWords * 8, s));
+  API_HIP(hipEventRecord(ad.ev[0], s));
+  if (!cont) {
+    API_HIP(hipMemsetAsync(c.accum.p, 0, (size_t)c.P * 16, s));
+    API_HIP(hipMemsetAsync(ad.bufs.E, 0, (size_t)c.P * 16, s));
+    API_HIP(hipMemsetAsync(ad.bufs.n, 0, (size_t)c.P * 4, s));
+  }
+  sptr_adaptive_info out{};
+  uint32_t res[kAdaptiveResWords] = {};
+  auto select = [&](uint32_t key) -> int {
+    launch_adapt_select(ad.bufs, rule, key, fv, s);
+    API_HIP(hipGetLastError());
+    API_HIP(hipStreamSynchronize(s));
+    API_HIP(hipMemcpy(res, ad.bufs.result, sizeof(res), hipMemcpyDeviceToHost));
+    if (res[kAdaptiveResGuardBad]) return fail(c, SPTR_ERR_HIP, "render_adaptive: a guard word of the state was overwritten (internal error)");
+    return SPTR_OK;
+  };
+  // the key most pixels of the next pass will have: a new accumulation's first pass is all fresh pixels, and
+  // after it every active pixel of a call that is no continuation holds the same n
+  uint32_t guess = cont ? std::min<uint32_t>(p->step, p->max_samples) : kAdaptiveKeyFresh;
+  uint32_t n_uniform = 0;  // (calls that are no continuation: the n of every active pixel)
+  for (;;) {
+    rc = select(guess);
+    if (rc != SPTR_OK) return rc;
+    if (res[kAdaptiveResActive] == 0u) break;
+    uint32_t key = guess;
+    if (res[kAdaptiveResKeyBelow] != 0xFFFFFFFFu || res[kAdaptiveResGroup] == 0u) {  // a smaller key comes first
+      key = std::min(res[kAdaptiveResKeyBelow], res[kAdaptiveResKeyAbove]);
+      const uint32_t active = res[kAdaptiveResActive];
+      rc = select(key);
+      if (rc != SPTR_OK) return rc;
+      if (res[kAdaptiveResActive] != active || res[kAdaptiveResGroup] == 0u || res[kAdaptiveResKeyBelow] != 0xFFFFFFFFu)
+        return fail(c, SPTR_ERR_HIP, "render_adaptive: selection not reproducible (internal error)");
+    }
+    ++out.passes;
+    out.active_last = res[kAdaptiveResActive];
+    if (out.passes == 1u) out.active_first = out.active_last;
+    for (;;) {  // the pass's groups in ascending key
+      const uint32_t count = res[kAdaptiveResGroup];
+      const uint32_t take = key == kAdaptiveKeyFresh ? p->min_samples : key;
+      rc = enqueue_adaptive_group(x, fv, fchain, count, take, cap, out.chunks);
+      if (rc != SPTR_OK) return rc;
+      out.samples += (uint64_t)count * take;
+      const uint32_t next = res[kAdaptiveResKeyAbove];
+      if (next == 0xFFFFFFFFu) break;
+      key = next;
+      rc = select(key);
+      if (rc != SPTR_OK) return rc;
+      if (res[kAdaptiveResGroup] == 0u) return fail(c, SPTR_ERR_HIP, "render_adaptive: empty group (internal error)");
+    }
+    n_uniform = n_uniform == 0u ? p->min_samples : n_uniform + std::min(p->step, p->max_samples - n_uniform);
+    guess = cont ? std::min<uint32_t>(p->step, p->max_samples)
+                 : std::max<uint32_t>(1u, std::min(p->step, p->max_samples - std::min(n_uniform, p->max_samples)));
+  }
+  out.min_count = res[kAdaptiveResMinN] == 0xFFFFFFFFu ? 0u : res[kAdaptiveResMinN];
+  out.max_count = res[kAdaptiveResMaxN];
+  if (!(f->flags & SPTR_FRAME_NO_RESOLVE)) {
+    launch_adapt_resolve(ad.bufs, fv, static_cast<uint32_t*>(c.tiles.p), static_cast<uint8_t*>(c.image.p), s);
+    API_HIP(hipGetLastError());
+  }
+  API_HIP(hipEventRecord(ad.ev[1], s));
+  API_HIP(hipStreamSynchronize(s));
+  unsigned long long tot[kTotWords];
+  API_HIP(hipMemcpy(tot, ad.tot.p, sizeof(tot), hipMemcpyDeviceToHost));
+  if (tot[kTotOverflow]) return fail(c, SPTR_ERR_HIP, "render_adaptive: segmented stream overflow (internal error)");
+  if (tot[kTotStackOverflow]) return fail(c, SPTR_ERR_HIP, "render_adaptive: BVH traversal stack overflow (internal error)");
+  float ms = 0.0f;
+  API_HIP(hipEventElapsedTime(&ms, ad.ev[0], ad.ev[1]));
+  out.ms = ms;
+  out.rays_closest = tot[kTotClosest];
+  out.rays_shadow = tot[kTotShadow];
+  ad.valid = true;
+  ad.cam = f->camera;
+  ad.W = f->width;
+  ad.H = f->height;
+  ad.G = G;
+  ad.R = R;
+  ad.max_depth = f->max_depth;
+  ad.epoch = c.epoch;
+  if (info) *info = out;
+  return SPTR_OK;
+}
+
+int sptr_read_sample_counts(sptr_ctx* x, uint32_t* counts) {
+  if (!x || !counts) return SPTR_ERR_INVALID;
+  Context& c = x->c;
+  auto& ad = x->ad;
+  if (!ad.valid || c.last_samples != kAdaptiveMark || ad.P != c.P)
+    return fail(c, SPTR_ERR_INVALID, "read_sample_counts: the context holds no adaptive state");
+  API_HIP(hipSetDevice(c.device));
+  std::vector<uint32_t> n(c.P);
+  API_HIP(hipMemcpy(n.data(), ad.bufs.n, (size_t)c.P * 4, hipMemcpyDeviceToHost));
+  std::memset(counts, 0, (size_t)c.W * c.H * 4);
+  for (uint32_t l = 0; l < c.P; ++l) {
+    int px, py;
+    if (host_local_pixel(c, l, px, py)) counts[(size_t)py * c.W + px] = n[l];
+  }
+  return SPTR_OK;
 }
 
 int sptr_primary_rays(sptr_ctx* x, const sptr_camera* cam, int32_t W, int32_t H, uint32_t acc, float* dirs,

@@ -19,6 +19,7 @@
 #include <utility>
 #include <vector>
 
+#include "adaptive_rule.h"
 #include "dev_owned.h"
 #include "prim_mat_table.h"
 #include "ray_batch.h"
@@ -724,6 +725,32 @@ void launch_ray_keys(const SceneView& sv, const float4* rays, uint32_t n, uint64
 // buffer and folds the chunk's per-block tallies into w.tot
 unsigned launch_rays_inject(const RayBatchView& b, const RayChunk& ck, const WaveView& w, hipStream_t s);
 void launch_rays_gather(const RayBatchView& b, const RayChunk& ck, const WaveView& w, hipStream_t s);
+// kernels_adaptive.h: sptr_render_adaptive.  The state beside the accumulation (E, n), the list of a selection
+// and the selection's words live in one device block, base; guard_off: the four guard runs around E, n and the
+// list, in words from base.
+struct AdaptiveBufs {
+  uint32_t* base;
+  float4* E;
+  uint32_t* n;
+  uint32_t* list;
+  uint32_t* bstat;
+  uint32_t* result;
+  uint32_t guard_off[4];
+};
+constexpr uint32_t kAdaptiveGuardWords = 16;          // per guard run
+constexpr uint32_t kAdaptiveGuardValue = 0xA5C3F00Du;
+constexpr uint32_t kAdaptiveStatWords = 8;            // per selection block
+// result words of a selection: the group's list length, the active pixels, the smallest active key below / above
+// the group's (0xFFFFFFFF: none), the smallest / largest n of the valid pixels, whether a guard word changed
+enum : uint32_t { kAdaptiveResGroup = 0, kAdaptiveResActive, kAdaptiveResKeyBelow, kAdaptiveResKeyAbove, kAdaptiveResMinN,
+                  kAdaptiveResMaxN, kAdaptiveResGuardBad, kAdaptiveResWords = 8 };
+// the active pixels of f whose adaptive_key is `key`, compacted into b.list in ascending local index, and b.result
+void launch_adapt_select(const AdaptiveBufs& b, const AdaptiveRule& rule, uint32_t key, const FrameView& f, hipStream_t s);
+// one chunk of list entries: the producer (returns the segments it published, as launch_rays_inject) and the consumer
+unsigned launch_adapt_inject(const AdaptiveBufs& b, const RayChunk& ck, uint32_t seed_offset, const FrameView& f,
+                             const WaveView& w, hipStream_t s);
+void launch_adapt_gather(const AdaptiveBufs& b, const RayChunk& ck, const FrameView& f, const WaveView& w, hipStream_t s);
+void launch_adapt_resolve(const AdaptiveBufs& b, const FrameView& f, uint32_t* tiles, uint8_t* image, hipStream_t s);
 // one wave spinning for `ticks` of the device wall clock (sptr_overlap_probe)
 void launch_spin(uint64_t ticks, hipStream_t s);
 

@@ -352,4 +352,40 @@ bool HipBackend::renderRays(const float* rays, const uint32_t* seeds, uint32_t n
   return true;
 }
 
+bool HipBackend::renderAdaptive(uint8_t* rgb, int width, int height, const Camera& camera, const AdaptiveSettings& as,
+                                AdaptiveInfo* info, uint32_t* counts) {
+  if (!ctx_ || !built_) {
+    err_ = "HipBackend::renderAdaptive: build() has not succeeded";
+    return false;
+  }
+  if (!syncState()) {
+    err_ = std::string("HipBackend: state upload failed: ") + sptr_last_error(ctx_);
+    return false;
+  }
+  sptr_frame fr{};
+  fr.width = width;
+  fr.height = height;
+  fr.camera = camera.toDevice();
+  fr.frame_begin = 1;
+  fr.spp = 1;
+  fr.max_depth = settings_.max_depth;
+  fr.shard_rank = 0;
+  fr.shard_count = 1;
+  fr.integrator = SPTR_INTEGRATOR_WAVEFRONT;
+  sptr_adaptive_params ap{};
+  ap.threshold = as.threshold;
+  ap.min_samples = as.min_samples;
+  ap.max_samples = as.max_samples;
+  ap.step = as.step;
+  // the accumulation now holds unequal counts: render() starts a new one
+  frame_index_ = 0;
+  has_last_camera_ = false;
+  if (sptr_render_adaptive(ctx_, &fr, &ap, info) != SPTR_OK || (rgb && sptr_read_rgb8(ctx_, rgb) != SPTR_OK) ||
+      (counts && sptr_read_sample_counts(ctx_, counts) != SPTR_OK)) {
+    err_ = std::string("HipBackend::renderAdaptive: ") + sptr_last_error(ctx_);
+    return false;
+  }
+  return true;
+}
+
 }  // namespace backends

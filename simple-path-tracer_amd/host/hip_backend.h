@@ -139,6 +139,19 @@ class HipBackend {
   };
   bool renderRays(const float* rays, const uint32_t* seeds, uint32_t n, uint32_t samples, uint32_t frame_index,
                   float* radiance, bool accumulate = false, bool normalize = false, RayRenderInfo* info = nullptr);
+  // sptr_render_adaptive: a new accumulation of the wavefront integrator that keeps sampling only the pixels whose
+  // half-buffer error is not yet below `threshold` (at least min_samples, at most max_samples per pixel, `step`
+  // more per pass; include/sptr_hip.h states the rule), Settings::max_depth bounces deep, with the current
+  // materials, lights and environment.  rgb (width * height * 3, may be null) takes the image, every pixel
+  // resolved by its own count; counts (width * height, may be null) the samples per pixel.  The next render()
+  // starts a new accumulation.
+  struct AdaptiveSettings {
+    float threshold = 0.02f;
+    uint32_t min_samples = 16, max_samples = 64, step = 16;
+  };
+  using AdaptiveInfo = sptr_adaptive_info;
+  bool renderAdaptive(uint8_t* rgb, int width, int height, const Camera& camera, const AdaptiveSettings& as,
+                      AdaptiveInfo* info = nullptr, uint32_t* counts = nullptr);
   uint32_t frameIndex() const { return frame_index_; }
   const std::string& lastError() const { return err_; }
   const std::vector<uint32_t>& getGeomMaterialMapping() const { return geom_material_; }

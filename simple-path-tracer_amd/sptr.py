@@ -142,7 +142,22 @@ class RayRender(C.Structure):
                 ("radiance", C.c_void_p), ("reserved", C.c_uint32 * 4)]
 
 
+class AdaptiveParams(C.Structure):
+    """sptr_adaptive_params."""
+    _fields_ = [("threshold", C.c_float), ("min_samples", C.c_uint32), ("max_samples", C.c_uint32),
+                ("step", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class AdaptiveInfo(C.Structure):
+    """sptr_adaptive_info."""
+    _fields_ = [("samples", C.c_uint64), ("rays_closest", C.c_uint64), ("rays_shadow", C.c_uint64),
+                ("passes", C.c_uint32), ("chunks", C.c_uint32), ("active_first", C.c_uint32),
+                ("active_last", C.c_uint32), ("min_count", C.c_uint32), ("max_count", C.c_uint32),
+                ("ms", C.c_double), ("reserved", C.c_uint32 * 4)]
+
+
 SPTR_RAYS_DEVICE_PTRS, SPTR_RAYS_ACCUMULATE, SPTR_RAYS_NORMALIZE = 1, 2, 4
+SPTR_ADAPTIVE_CONTINUE = 1
 SPTR_AOV_ALBEDO, SPTR_AOV_NORMAL, SPTR_AOV_DEPTH, SPTR_AOV_ID, SPTR_AOV_UV = 0, 1, 2, 3, 4
 DEFAULT_MAX_HISTORY = 4  # the cap to ask set_denoise_history for without a number of one's own (DESIGN.md §6f)
 
@@ -163,6 +178,7 @@ EXPORTS = [
     "sptr_set_dynamic", "sptr_update_geometry", "sptr_refit_info",
     "sptr_set_rest_positions", "sptr_update_transforms", "sptr_tree_cost",
     "sptr_query_rays", "sptr_query_info", "sptr_render_rays", "sptr_ray_render_info",
+    "sptr_render_adaptive", "sptr_read_sample_counts",
     "sptr_host_builtin_scene", "sptr_host_scene_view", "sptr_host_scene_free", "sptr_host_camera_lookat",
     "sptr_host_preset_materials", "sptr_host_default_lights", "sptr_host_equirect_to_faces",
     "sptr_host_pack_tiles", "sptr_host_unpack_tiles", "sptr_host_load_hdr", "sptr_host_free",
@@ -242,6 +258,8 @@ def lib() -> C.CDLL:
         "sptr_query_info": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), up, up]),
         "sptr_render_rays": (C.c_int, [vp, C.POINTER(RayRender), vp]),
         "sptr_ray_render_info": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(u64), C.POINTER(u64), up]),
+        "sptr_render_adaptive": (C.c_int, [vp, C.POINTER(Frame), C.POINTER(AdaptiveParams), C.POINTER(AdaptiveInfo)]),
+        "sptr_read_sample_counts": (C.c_int, [vp, up]),
         "sptr_host_builtin_scene": (C.c_int, [C.c_char_p, u32, u32, C.POINTER(vp)]),
         "sptr_host_scene_view": (C.c_int, [vp, C.POINTER(Scene)]),
         "sptr_host_scene_free": (None, [vp]),
@@ -924,6 +942,30 @@ class Renderer:
         ms, c, s, k = C.c_double(), C.c_uint64(), C.c_uint64(), C.c_uint32()
         self._check(self._L.sptr_ray_render_info(self._h, C.byref(ms), C.byref(c), C.byref(s), C.byref(k)), "ray_render_info")
         return {"ms": ms.value, "closest": c.value, "shadow": s.value, "chunks": k.value}
+
+    def render_adaptive(self, cam: Camera, width: int, height: int, threshold: float, min_samples: int,
+                        max_samples: int, step: int, max_depth: int = 6, cont: bool = False, shard=(0, 1),
+                        frame_flags: int = 0, flags: int | None = None, reserved=(0, 0, 0),
+                        integrator: int = SPTR_INTEGRATOR_WAVEFRONT, frame_begin: int = 1) -> dict:
+        """sptr_render_adaptive: sample every pixel until its half-buffer error falls below threshold (at least
+        min_samples, at most max_samples, step more per pass); cont goes on from the last adaptive call's state.
+        Returns sptr_adaptive_info's fields.  The image, accumulation and counts are read with read_rgb8,
+        read_accum and read_sample_counts.  (flags, reserved, integrator, frame_begin: as the C structs take
+        them, for the error cases.)"""
+        f = Frame(width, height, cam, frame_begin, 1, max_depth, shard[0], shard[1], frame_flags, integrator, 0)
+        p = AdaptiveParams(threshold, min_samples, max_samples, step,
+                           (SPTR_ADAPTIVE_CONTINUE if cont else 0) if flags is None else flags,
+                           (C.c_uint32 * 3)(*reserved))
+        info = AdaptiveInfo()
+        self._check(self._L.sptr_render_adaptive(self._h, C.byref(f), C.byref(p), C.byref(info)), "render_adaptive")
+        self.width, self.height = width, height
+        return {k: getattr(info, k) for k, _ in AdaptiveInfo._fields_ if k != "reserved"}
+
+    def read_sample_counts(self) -> np.ndarray:
+        """(H, W) uint32: the samples every pixel of the last adaptive call's image holds (other shards' 0)."""
+        out = np.zeros((self.height, self.width), np.uint32)
+        self._check(self._L.sptr_read_sample_counts(self._h, _u(out)), "read_sample_counts")
+        return out
 
     def primary_rays(self, cam: Camera, width: int, height: int, acc: int):
         dirs = np.zeros((height, width, 3), np.float32)

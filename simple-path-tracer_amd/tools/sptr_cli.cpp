@@ -45,6 +45,12 @@
 // ray N samples (frame indices 1 .. N), --depth the bounces.  --out takes the linear image, the mean radiance, as
 // a little-endian PFM (rows top to bottom in the file: scale -1, first row y = 0); the --json line is
 // {"panorama": [W, H], "samples", "depth", "ms", "closest", "shadow", "chunks"} (sptr_ray_render_info).
+// --adaptive THR [--min-spp A] [--spp B] [--step K] [--counts FILE]: instead of the frames, one adaptive call
+// through HipBackend::renderAdaptive (sptr_render_adaptive): every pixel takes at least A (default 16) and at most
+// B (default 64) samples, K (default 16) more per pass, until its error is below THR.  --out takes the image as
+// usual, --counts the samples per pixel as a one-channel little-endian PFM (rows top to bottom: scale -1); the
+// --json line is {"adaptive": THR, "min_spp", "max_spp", "step", "width", "height", "depth"} and sptr_adaptive_info's
+// fields.
 #include <algorithm>
 #include <cmath>
 #include <chrono>
@@ -81,6 +87,10 @@ int main(int argc, char** argv) {
   int w = 800, h = 600, spp = 4, depth = 6, warmup = 0;
   bool json = false, lagged = false, rebuild = false, query_centre = false, motion = false, rigid = false;
   int pano_w = 0, pano_h = 0;
+  bool adaptive = false, spp_given = false;
+  double adaptive_thr = 0.0;
+  int min_spp = 16, step = 16;
+  std::string counts_out;
   int animate = 0;
   std::string integrator = "wavefront";
   int spf = 4, launch_mode = 0, denoise = 0, history = 0;
@@ -91,7 +101,11 @@ int main(int argc, char** argv) {
     if (a == "--scene") scene_name = next();
     else if (a == "--w") w = std::atoi(next());
     else if (a == "--h") h = std::atoi(next());
-    else if (a == "--spp") spp = std::atoi(next());
+    else if (a == "--spp") spp = std::atoi(next()), spp_given = true;
+    else if (a == "--adaptive") adaptive = true, adaptive_thr = std::atof(next());
+    else if (a == "--min-spp") min_spp = std::atoi(next());
+    else if (a == "--step") step = std::atoi(next());
+    else if (a == "--counts") counts_out = next();
     else if (a == "--depth") depth = std::atoi(next());
     else if (a == "--env") env = next();
     else if (a == "--out") out = next();
@@ -120,7 +134,7 @@ int main(int argc, char** argv) {
       }
     }
     else {
-      std::fprintf(stderr, "usage: %s [--scene S] [--w W] [--h H] [--spp N] [--depth D] [--env sky|F.hdr] [--out F] [--warmup N] [--json] [--lagged] [--denoise N] [--history [M]] [--motion] [--orbit DEG] [--animate K [--rebuild] [--rigid]] [--query-centre-rays] [--panorama W H]\n",
+      std::fprintf(stderr, "usage: %s [--scene S] [--w W] [--h H] [--spp N] [--depth D] [--env sky|F.hdr] [--out F] [--warmup N] [--json] [--lagged] [--denoise N] [--history [M]] [--motion] [--orbit DEG] [--animate K [--rebuild] [--rigid]] [--query-centre-rays] [--panorama W H] [--adaptive THR [--min-spp A] [--step K] [--counts F]]\n",
                    argv[0]);
       return 2;
     }
@@ -200,6 +214,45 @@ int main(int argc, char** argv) {
     std::fprintf(fp, "PF\n%d %d\n-1.0\n", pano_w, pano_h);
     std::fwrite(rad.data(), sizeof(float), rad.size(), fp);
     std::fclose(fp);
+    return 0;
+  }
+  if (adaptive) {
+    std::vector<unsigned char> aimg(size_t(w) * h * 3);
+    std::vector<uint32_t> cnt(size_t(w) * h);
+    backends::HipBackend::AdaptiveSettings as;
+    as.threshold = float(adaptive_thr);
+    as.min_samples = uint32_t(std::max(0, min_spp));
+    as.max_samples = uint32_t(std::max(0, spp_given ? spp : 64));
+    as.step = uint32_t(std::max(0, step));
+    backends::HipBackend::AdaptiveInfo ai{};
+    if (!be.renderAdaptive(aimg.data(), w, h, cam, as, &ai, cnt.data())) {
+      std::fprintf(stderr, "%s\n", be.lastError().c_str());
+      return 1;
+    }
+    if (json)
+      std::printf("{\"adaptive\": %.9g, \"scene\": \"%s\", \"min_spp\": %u, \"max_spp\": %u, \"step\": %u, \"width\": %d, "
+                  "\"height\": %d, \"depth\": %d, \"samples\": %llu, \"rays_closest\": %llu, \"rays_shadow\": %llu, "
+                  "\"passes\": %u, \"chunks\": %u, \"active_first\": %u, \"active_last\": %u, \"min_count\": %u, "
+                  "\"max_count\": %u, \"ms\": %.4f}\n",
+                  double(as.threshold), scene_name.c_str(), as.min_samples, as.max_samples, as.step, w, h, depth,
+                  (unsigned long long)ai.samples, (unsigned long long)ai.rays_closest, (unsigned long long)ai.rays_shadow,
+                  ai.passes, ai.chunks, ai.active_first, ai.active_last, ai.min_count, ai.max_count, ai.ms);
+    else
+      std::printf("scene=%s %dx%d adaptive %g, %u..%u spp: %.2f samples per pixel, %u passes, %.2f ms device\n", scene_name.c_str(),
+                  w, h, double(as.threshold), as.min_samples, as.max_samples, double(ai.samples) / (double(w) * h), ai.passes, ai.ms);
+    if (!counts_out.empty()) {
+      std::vector<float> cf(cnt.begin(), cnt.end());
+      FILE* fc = std::fopen(counts_out.c_str(), "wb");
+      if (!fc) return 1;
+      std::fprintf(fc, "Pf\n%d %d\n-1.0\n", w, h);
+      std::fwrite(cf.data(), sizeof(float), cf.size(), fc);
+      std::fclose(fc);
+    }
+    FILE* fa = std::fopen(out.c_str(), "wb");
+    if (!fa) return 1;
+    std::fprintf(fa, "P6\n%d %d\n255\n", w, h);
+    std::fwrite(aimg.data(), 1, aimg.size(), fa);
+    std::fclose(fa);
     return 0;
   }
   std::vector<unsigned char> img(size_t(w) * h * 3);
