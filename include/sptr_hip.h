@@ -635,6 +635,61 @@ int sptr_query_rays(sptr_ctx* ctx, const sptr_ray_query* query, void* stream);
  * traversal-stack-overflow flag (a synchronous query checks the flag itself).  Any pointer may be NULL. */
 int sptr_query_info(sptr_ctx* ctx, double* ms_sort, double* ms_trace, uint32_t* sorted, uint32_t* queries);
 
+/* ---- multi-hit ray queries (symbols added within ABI 9: no existing struct or entry point changed) ---------
+ * The K = max_hits nearest hits along each ray, in order: lidar with several returns, the thickness of an
+ * object (entry and exit), what lies behind a glass surface, how many surfaces a ray crosses, picking through
+ * the front surface.  One walk per ray that keeps a list instead of a minimum (k_rayquery_multi).
+ *
+ * Candidate hits of ray i with interval (tnear, tfar), read as sptr_query_rays reads it, per primitive:
+ *   triangle: at most one, what the closest-hit triangle test reports for that triangle on the ray's own
+ *             interval (same arithmetic, same acceptance |den| tnear < T <= |den| tfar);
+ *   sphere  : at most two.  The first is what the closest-hit sphere test reports on (tnear, tfar), at t_a;
+ *             the second, if there is a first, is what the same test reports on (t_a, tfar) — a second
+ *             evaluation with tnear = t_a, quirks included (the test's t > 0 rule; a tangent sphere with
+ *             t1 == t2 gives one hit).  The first is reported with prim = 0, the second with prim = 1.
+ *   A triangle left out of the tree because it was exactly degenerate at upload gives nothing; a triangle the
+ *   tree references several times (sptr_set_split_refs) is one primitive and gives one hit.
+ * Result: the first K candidates in ascending order of the key (t, geomID, primID), t compared as float and
+ * the ids as unsigned, resolved exactly as sptr_query_rays reports them.  The order therefore depends on
+ * nothing but the scene and the ray: not on the tree, the walk, the leaf size, the tree order, a refit or the
+ * trace order.  count[i] = min(K, number of candidates).  Hit j of ray i is element i * K + j of every per-hit
+ * array.  Slot j < count[i] holds geom, prim, t, the unnormalised Ng (the stored triangle normal, or
+ * (P - c) / r with P = o + t d for a sphere) and uv (sptr_query_rays' barycentrics for a triangle, 0 for a
+ * sphere).  Slots j >= count[i] are filled: ids 0xFFFFFFFF, t = +inf, Ng = 0, uv = 0.
+ * With K = 1, t equals sptr_query_rays' closest-hit t bit for bit, and the ids equal its ids unless two
+ * primitives tie exactly at that t.
+ *
+ * Pointers, streams, order and scratch: the rules of sptr_query_rays, word for word.  Host pointers are staged
+ * and the call is synchronous; a non-NULL stream is for device pointers only and only enqueues; consecutive
+ * enqueued queries (of either kind) must share one stream; n == 0 returns SPTR_OK with no launch; a
+ * traversal-stack overflow is reported as sptr_query_rays reports it.
+ * SPTR_ERR_INVALID: SPTR_QUERY_ANY_HIT or an unknown flag, both sort flags, max_hits outside
+ * 1 .. SPTR_MULTI_HIT_MAX, n > 2^28 or n * max_hits > 2^28, NULL count or rays with n > 0, non-zero pad or
+ * reserved, a misaligned device ray buffer, host pointers with a stream, a lane context.  SPTR_ERR_NO_SCENE
+ * before an upload.  A refused call writes nothing and leaves the context as it was. */
+enum { SPTR_MULTI_HIT_MAX = 16 };
+typedef struct sptr_multi_hit_query {
+  const float* rays;   /* n x 8 floats: o3 d3 tnear tfar; 16-byte aligned when a device pointer */
+  uint32_t n;          /* <= 2^28, and n * max_hits <= 2^28 */
+  uint32_t flags;      /* SPTR_QUERY_DEVICE_PTRS | SPTR_QUERY_SORT | SPTR_QUERY_NO_SORT */
+  uint32_t max_hits;   /* K: 1 .. SPTR_MULTI_HIT_MAX */
+  uint32_t pad;        /* 0 */
+  uint32_t* count;     /* n; required */
+  uint32_t* geom;      /* n*K; each of these may be NULL and is then not written */
+  uint32_t* prim;
+  float* t;
+  float* ng;           /* n*K x 3 */
+  float* uv;           /* n*K x 2 */
+  uint64_t reserved[4];/* 0 */
+} sptr_multi_hit_query;
+int sptr_query_multi_hit(sptr_ctx* ctx, const sptr_multi_hit_query* query, void* stream);
+/* Waits for the last multi-hit query: the device times of its sort phase and of its trace launch, whether it
+ * was sorted, the multi-hit queries launched so far, and the list capacity (entries per ray) and LDS bytes per
+ * block (static and dynamic) of the kernel instantiation it launched; zeros before the first.  SPTR_ERR_HIP if
+ * it set the traversal-stack-overflow flag, as sptr_query_info.  Any pointer may be NULL. */
+int sptr_multi_hit_info(sptr_ctx* ctx, double* ms_sort, double* ms_trace, uint32_t* sorted, uint32_t* queries,
+                        uint32_t* list_capacity, uint32_t* lds_bytes);
+
 /* ---- path-traced radiance for caller-supplied rays (symbols added within ABI 9: no existing struct or
  *      entry point changed) ------------------------------------------------------------------------------
  * sptr_render renders through the reference's pinhole camera and sptr_query_rays answers what a ray hits; this

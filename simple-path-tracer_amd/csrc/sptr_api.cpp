@@ -107,6 +107,13 @@ struct sptr_ctx {
     bool sorted = false;
     uint32_t count = 0;
   } rq;
+  // sptr_query_multi_hit: it shares rq's scratch (so consecutive enqueued queries of either kind share a stream)
+  // and keeps the events and the facts of its own last query for sptr_multi_hit_info
+  struct MultiHit {
+    sptr::DevEvent ev[3];  // begin, after the sort, end
+    bool issued = false, sorted = false;
+    uint32_t count = 0, list_capacity = 0, lds_bytes = 0;
+  } mh;
   // sptr_render_rays (the caller's context; a pixel lane holds none): the call's own totals block (WaveView::tot
   // of its launches, so that the render totals never see them), the carried sum of a ray whose sample range is
   // split, the staging of host-pointer calls, and the events of the last call: begin and end on the context's
@@ -143,6 +150,7 @@ struct sptr_ctx {
     if (copy_stream) (void)hipStreamSynchronize(copy_stream);  // the lagged readback's copy
     // a query enqueued on a caller's stream (the caller synchronises it first; this costs nothing then)
     if (rq.issued) (void)hipEventSynchronize(rq.ev[2]);
+    if (mh.issued) (void)hipEventSynchronize(mh.ev[2]);
     if (reg_ptr) (void)hipHostUnregister(reg_ptr);
     delete lane;
   }
@@ -2259,6 +2267,7 @@ static int ensure_geom_first(sptr_ctx* x) {
 static int query_wait(sptr_ctx* x) {
   Context& c = x->c;
   if (x->rq.issued) API_HIP(hipEventSynchronize(x->rq.ev[2]));
+  if (x->mh.issued) API_HIP(hipEventSynchronize(x->mh.ev[2]));
   return SPTR_OK;
 }
 
@@ -2273,26 +2282,21 @@ static int query_check_flag(sptr_ctx* x) {
   return fail(c, SPTR_ERR_HIP, "query: BVH traversal stack overflow (internal error)");
 }
 
-// One validated batch with device pointers, enqueued on s: [keys, radix sort,] trace.
-static int enqueue_query(sptr_ctx* x, const sptr_ray_query& q, hipStream_t s) {
+// What every enqueued batch needs first: the overflow flag, the geomID offsets, and, for a sorted batch of n rays,
+// scratch for the keys, the indices and the radix sort (shared by sptr_query_rays and sptr_query_multi_hit).
+static int query_scratch(sptr_ctx* x, uint32_t n, bool sort, hipStream_t s) {
   Context& c = x->c;
   auto& rq = x->rq;
-  const SceneView sv = scene_view(c);
-  const bool any = (q.flags & SPTR_QUERY_ANY_HIT) != 0u;
-  const bool sort = (q.flags & SPTR_QUERY_SORT) != 0u ||
-                    ((q.flags & SPTR_QUERY_NO_SORT) == 0u && sv.lds_bytes == 0u && query_sorts_by_default(sv, q.n));
-  for (DevEvent& e : rq.ev)
-    if (!e) API_HIP(hipEventCreate(e.put()));
   if (!rq.flag.p) {
     API_HIP(rq.flag.ensure(16));
     API_HIP(hipMemset(rq.flag.p, 0, 16));
   }
   const int rg = ensure_geom_first(x);
   if (rg != SPTR_OK) return rg;
-  size_t temp_bytes = 0;
   if (sort) {
-    API_HIP(radix_sort_pairs_u64(nullptr, temp_bytes, nullptr, nullptr, nullptr, nullptr, q.n, s));
-    const size_t kb = (size_t)q.n * 8, ib = (size_t)q.n * 4;
+    size_t temp_bytes = 0;
+    API_HIP(radix_sort_pairs_u64(nullptr, temp_bytes, nullptr, nullptr, nullptr, nullptr, n, s));
+    const size_t kb = (size_t)n * 8, ib = (size_t)n * 4;
     if (rq.keys.bytes < kb || rq.keys_sorted.bytes < kb || rq.index.bytes < ib || rq.order.bytes < ib ||
         rq.temp.bytes < temp_bytes) {
       const int rw = query_wait(x);  // an enqueued query may still use the old scratch
@@ -2304,6 +2308,34 @@ static int enqueue_query(sptr_ctx* x, const sptr_ray_query& q, hipStream_t s) {
       API_HIP(rq.temp.ensure(temp_bytes));
     }
   }
+  return SPTR_OK;
+}
+
+// The sort phase on s: keys, radix sort; the trace then reads rq.order.
+static int query_sort(sptr_ctx* x, const SceneView& sv, const float4* rays, uint32_t n, hipStream_t s) {
+  Context& c = x->c;
+  auto& rq = x->rq;
+  launch_ray_keys(sv, rays, n, static_cast<uint64_t*>(rq.keys.p), static_cast<uint32_t*>(rq.index.p), s);
+  API_HIP(hipGetLastError());
+  size_t tb = rq.temp.bytes;
+  API_HIP(radix_sort_pairs_u64(rq.temp.p, tb, static_cast<const uint64_t*>(rq.keys.p),
+                               static_cast<uint64_t*>(rq.keys_sorted.p), static_cast<const uint32_t*>(rq.index.p),
+                               static_cast<uint32_t*>(rq.order.p), n, s));
+  return SPTR_OK;
+}
+
+// One validated batch with device pointers, enqueued on s: [keys, radix sort,] trace.
+static int enqueue_query(sptr_ctx* x, const sptr_ray_query& q, hipStream_t s) {
+  Context& c = x->c;
+  auto& rq = x->rq;
+  const SceneView sv = scene_view(c);
+  const bool any = (q.flags & SPTR_QUERY_ANY_HIT) != 0u;
+  const bool sort = (q.flags & SPTR_QUERY_SORT) != 0u ||
+                    ((q.flags & SPTR_QUERY_NO_SORT) == 0u && sv.lds_bytes == 0u && query_sorts_by_default(sv, q.n));
+  for (DevEvent& e : rq.ev)
+    if (!e) API_HIP(hipEventCreate(e.put()));
+  const int rs = query_scratch(x, q.n, sort, s);
+  if (rs != SPTR_OK) return rs;
   RayQueryView v{};
   v.rays = reinterpret_cast<const float4*>(q.rays);
   v.n = q.n;
@@ -2321,12 +2353,8 @@ static int enqueue_query(sptr_ctx* x, const sptr_ray_query& q, hipStream_t s) {
   v.stack_overflow = static_cast<uint32_t*>(rq.flag.p);
   API_HIP(hipEventRecord(rq.ev[0], s));
   if (sort) {
-    launch_ray_keys(sv, v.rays, q.n, static_cast<uint64_t*>(rq.keys.p), static_cast<uint32_t*>(rq.index.p), s);
-    API_HIP(hipGetLastError());
-    size_t tb = rq.temp.bytes;
-    API_HIP(radix_sort_pairs_u64(rq.temp.p, tb, static_cast<const uint64_t*>(rq.keys.p),
-                                 static_cast<uint64_t*>(rq.keys_sorted.p), static_cast<const uint32_t*>(rq.index.p),
-                                 static_cast<uint32_t*>(rq.order.p), q.n, s));
+    const int rk = query_sort(x, sv, v.rays, q.n, s);
+    if (rk != SPTR_OK) return rk;
     API_HIP(hipEventRecord(rq.ev[1], s));
     v.order = static_cast<const uint32_t*>(rq.order.p);
   }
@@ -2418,6 +2446,137 @@ int sptr_query_info(sptr_ctx* x, double* ms_sort, double* ms_trace, uint32_t* so
   if (sorted) *sorted = rq.issued && rq.sorted ? 1u : 0u;
   if (queries) *queries = rq.count;
   return rq.issued ? query_check_flag(x) : SPTR_OK;
+}
+
+// ---- multi-hit ray queries ----------------------------------------------------------------------------
+constexpr uint32_t kMultiHitFlags = SPTR_QUERY_DEVICE_PTRS | SPTR_QUERY_SORT | SPTR_QUERY_NO_SORT;
+
+// One validated batch with device pointers, enqueued on s: [keys, radix sort,] trace; enqueue_query's twin.
+static int enqueue_multi_hit(sptr_ctx* x, const sptr_multi_hit_query& q, hipStream_t s) {
+  Context& c = x->c;
+  auto& rq = x->rq;
+  auto& mh = x->mh;
+  const SceneView sv = scene_view(c);
+  const bool sort = (q.flags & SPTR_QUERY_SORT) != 0u ||
+                    ((q.flags & SPTR_QUERY_NO_SORT) == 0u && sv.lds_bytes == 0u && query_sorts_by_default(sv, q.n));
+  for (DevEvent& e : mh.ev)
+    if (!e) API_HIP(hipEventCreate(e.put()));
+  const int rs = query_scratch(x, q.n, sort, s);
+  if (rs != SPTR_OK) return rs;
+  RayMultiView v{};
+  v.rays = reinterpret_cast<const float4*>(q.rays);
+  v.n = q.n;
+  v.k = q.max_hits;
+  v.count = q.count;
+  v.geom = q.geom;
+  v.prim = q.prim;
+  v.t = q.t;
+  v.ng = q.ng;
+  v.uv = q.uv;
+  v.tri_orig = static_cast<const uint32_t*>(c.tri_orig.p);
+  v.geom_first = static_cast<const uint32_t*>(x->geom_first.p);
+  v.stack_overflow = static_cast<uint32_t*>(rq.flag.p);
+  API_HIP(hipEventRecord(mh.ev[0], s));
+  if (sort) {
+    const int rk = query_sort(x, sv, v.rays, q.n, s);
+    if (rk != SPTR_OK) return rk;
+    API_HIP(hipEventRecord(mh.ev[1], s));
+    v.order = static_cast<const uint32_t*>(rq.order.p);
+  }
+  launch_rayquery_multi(sv, v, s, &mh.list_capacity, &mh.lds_bytes);
+  API_HIP(hipGetLastError());
+  API_HIP(hipEventRecord(mh.ev[2], s));
+  mh.issued = true;
+  mh.sorted = sort;
+  ++mh.count;
+  return SPTR_OK;
+}
+
+int sptr_query_multi_hit(sptr_ctx* x, const sptr_multi_hit_query* q, void* stream) {
+  if (!x || !q) return SPTR_ERR_INVALID;
+  Context& c = x->c;
+  if (x->is_lane) return fail(c, SPTR_ERR_INVALID, "query_multi_hit: not on a lane context");
+  const bool dev = (q->flags & SPTR_QUERY_DEVICE_PTRS) != 0u;
+  if (q->flags & ~kMultiHitFlags) return fail(c, SPTR_ERR_INVALID, "query_multi_hit: SPTR_QUERY_ANY_HIT or unknown flags");
+  if ((q->flags & SPTR_QUERY_SORT) && (q->flags & SPTR_QUERY_NO_SORT))
+    return fail(c, SPTR_ERR_INVALID, "query_multi_hit: SPTR_QUERY_SORT and SPTR_QUERY_NO_SORT exclude each other");
+  if (q->max_hits < 1u || q->max_hits > (uint32_t)SPTR_MULTI_HIT_MAX)
+    return fail(c, SPTR_ERR_INVALID, "query_multi_hit: max_hits must be 1 .. SPTR_MULTI_HIT_MAX");
+  if (q->n > kQueryMaxRays || (uint64_t)q->n * q->max_hits > kQueryMaxRays)
+    return fail(c, SPTR_ERR_INVALID, "query_multi_hit: more than 2^28 rays or hit slots");
+  if (q->n && !q->rays) return fail(c, SPTR_ERR_INVALID, "query_multi_hit: no rays");
+  if (q->n && !q->count) return fail(c, SPTR_ERR_INVALID, "query_multi_hit: the count output is required");
+  if (q->pad || q->reserved[0] || q->reserved[1] || q->reserved[2] || q->reserved[3])
+    return fail(c, SPTR_ERR_INVALID, "query_multi_hit: pad and reserved must be 0");
+  if (!dev && stream) return fail(c, SPTR_ERR_INVALID, "query_multi_hit: host pointers cannot be enqueued on a stream");
+  if (dev && (reinterpret_cast<uintptr_t>(q->rays) & 15u))
+    return fail(c, SPTR_ERR_INVALID, "query_multi_hit: the device ray buffer must be 16-byte aligned");
+  if (!c.have_scene) return fail(c, SPTR_ERR_NO_SCENE, "query_multi_hit: no scene");
+  if (q->n == 0u) return SPTR_OK;
+  API_HIP(hipSetDevice(c.device));
+  if (stream) return enqueue_multi_hit(x, *q, static_cast<hipStream_t>(stream));  // only enqueues
+  if (sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;
+  const int rw = query_wait(x);
+  if (rw != SPTR_OK) return rw;
+  sptr_multi_hit_query d = *q;
+  const size_t n = q->n, m = n * q->max_hits;
+  // host pointers: rays in, then count | geom | prim | t | ng | uv out, staged in the context
+  const size_t off_geom = n * 4, off_prim = off_geom + m * 4, off_t = off_prim + m * 4, off_ng = off_t + m * 4,
+               off_uv = off_ng + m * 12, total = off_uv + m * 8;
+  if (!dev) {
+    auto& rq = x->rq;
+    API_HIP(rq.stage_in.ensure(n * 32));
+    API_HIP(rq.stage_out.ensure(total));
+    API_HIP(hipMemcpy(rq.stage_in.p, q->rays, n * 32, hipMemcpyHostToDevice));
+    char* o = static_cast<char*>(rq.stage_out.p);
+    d.rays = static_cast<const float*>(rq.stage_in.p);
+    d.count = reinterpret_cast<uint32_t*>(o);
+    d.geom = q->geom ? reinterpret_cast<uint32_t*>(o + off_geom) : nullptr;
+    d.prim = q->prim ? reinterpret_cast<uint32_t*>(o + off_prim) : nullptr;
+    d.t = q->t ? reinterpret_cast<float*>(o + off_t) : nullptr;
+    d.ng = q->ng ? reinterpret_cast<float*>(o + off_ng) : nullptr;
+    d.uv = q->uv ? reinterpret_cast<float*>(o + off_uv) : nullptr;
+  }
+  const int rc = enqueue_multi_hit(x, d, c.stream);
+  if (rc != SPTR_OK) return rc;
+  API_HIP(hipStreamSynchronize(c.stream));
+  const int rf = query_check_flag(x);
+  if (rf != SPTR_OK) return rf;
+  if (!dev) {
+    API_HIP(hipMemcpy(q->count, d.count, n * 4, hipMemcpyDeviceToHost));
+    if (q->geom) API_HIP(hipMemcpy(q->geom, d.geom, m * 4, hipMemcpyDeviceToHost));
+    if (q->prim) API_HIP(hipMemcpy(q->prim, d.prim, m * 4, hipMemcpyDeviceToHost));
+    if (q->t) API_HIP(hipMemcpy(q->t, d.t, m * 4, hipMemcpyDeviceToHost));
+    if (q->ng) API_HIP(hipMemcpy(q->ng, d.ng, m * 12, hipMemcpyDeviceToHost));
+    if (q->uv) API_HIP(hipMemcpy(q->uv, d.uv, m * 8, hipMemcpyDeviceToHost));
+  }
+  return SPTR_OK;
+}
+
+int sptr_multi_hit_info(sptr_ctx* x, double* ms_sort, double* ms_trace, uint32_t* sorted, uint32_t* queries,
+                        uint32_t* list_capacity, uint32_t* lds_bytes) {
+  if (!x) return SPTR_ERR_INVALID;
+  Context& c = x->c;
+  auto& mh = x->mh;
+  double ms_s = 0.0, ms_t = 0.0;
+  if (mh.issued) {
+    API_HIP(hipSetDevice(c.device));
+    API_HIP(hipEventSynchronize(mh.ev[2]));
+    float ms = 0.0f;
+    if (mh.sorted) {
+      API_HIP(hipEventElapsedTime(&ms, mh.ev[0], mh.ev[1]));
+      ms_s = ms;
+    }
+    API_HIP(hipEventElapsedTime(&ms, mh.sorted ? mh.ev[1] : mh.ev[0], mh.ev[2]));
+    ms_t = ms;
+  }
+  if (ms_sort) *ms_sort = ms_s;
+  if (ms_trace) *ms_trace = ms_t;
+  if (sorted) *sorted = mh.issued && mh.sorted ? 1u : 0u;
+  if (queries) *queries = mh.count;
+  if (list_capacity) *list_capacity = mh.list_capacity;
+  if (lds_bytes) *lds_bytes = mh.lds_bytes;
+  return mh.issued ? query_check_flag(x) : SPTR_OK;
 }
 
 // ---- path-traced radiance for caller-supplied rays ---------------------------------------------------

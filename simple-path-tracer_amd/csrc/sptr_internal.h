@@ -21,6 +21,7 @@
 
 #include "adaptive_rule.h"
 #include "dev_owned.h"
+#include "hit_list.h"
 #include "prim_mat_table.h"
 #include "ray_batch.h"
 #include "sptr_hip.h"
@@ -342,6 +343,21 @@ struct RayQueryView {
   const uint32_t* tri_orig;    // as AovView's
   const uint32_t* geom_first;
   uint32_t* stack_overflow;    // sticky flag
+};
+// One batch of multi-hit queries on caller buffers (k_rayquery_multi): device pointers; hit j of ray i at i * k + j.
+struct RayMultiView {
+  const float4* rays;     // as RayQueryView's
+  uint32_t n, k;          // rays, max_hits
+  const uint32_t* order;  // as RayQueryView's
+  uint32_t* count;        // n
+  uint32_t* geom;         // n * k each; may be null (not written)
+  uint32_t* prim;
+  float* t;
+  float* ng;              // n * k x 3
+  float* uv;              // n * k x 2
+  const uint32_t* tri_orig;
+  const uint32_t* geom_first;
+  uint32_t* stack_overflow;
 };
 // One call of sptr_render_rays (k_rays_inject, k_rays_gather): device pointers, indexed by ray; its chunks are
 // RayChunks (ray_batch.h).
@@ -719,6 +735,8 @@ void launch_atrous_history(const DenoiseView& v, const float4* cin, float4* cout
 // kernels_query.h: one batch of ray queries (sptr_query_rays), and the sort keys of a batch with the
 // identity indices 0..n-1 beside them (the radix sort's values)
 void launch_rayquery(const SceneView& sv, const RayQueryView& q, bool anyhit, hipStream_t s);
+// the list capacity instantiated for q.k and the kernel's LDS bytes per block (static + dynamic) are returned
+void launch_rayquery_multi(const SceneView& sv, const RayMultiView& q, hipStream_t s, uint32_t* list_capacity, uint32_t* lds_bytes);
 void launch_ray_keys(const SceneView& sv, const float4* rays, uint32_t n, uint64_t* keys, uint32_t* index, hipStream_t s);
 // kernels_rays.h: one chunk of sptr_render_rays.  The producer writes the chunk's paths into rs[0] / w.segN and
 // returns the segments it published (the nseg of the depth-0 trace); the consumer sums rad[] into the caller's

@@ -325,6 +325,35 @@ bool HipBackend::queryRays(const float* rays, uint32_t n, bool anyHit, HitBuffer
   return true;
 }
 
+bool HipBackend::queryMultiHit(const float* rays, uint32_t n, uint32_t maxHits, MultiHitBuffers& out) {
+  if (!ctx_ || !built_) {
+    err_ = "HipBackend::queryMultiHit: build() has not succeeded";
+    return false;
+  }
+  const size_t m = size_t(n) * maxHits;
+  out.count.assign(n, 0u);
+  out.geom.assign(m, 0u);
+  out.prim.assign(m, 0u);
+  out.t.assign(m, 0.0f);
+  out.ng.assign(m * 3, 0.0f);
+  out.uv.assign(m * 2, 0.0f);
+  sptr_multi_hit_query q{};
+  q.rays = rays;
+  q.n = n;
+  q.max_hits = maxHits;
+  q.count = out.count.data();
+  q.geom = out.geom.data();
+  q.prim = out.prim.data();
+  q.t = out.t.data();
+  q.ng = out.ng.data();
+  q.uv = out.uv.data();
+  if (sptr_query_multi_hit(ctx_, &q, nullptr) != SPTR_OK) {
+    err_ = std::string("HipBackend::queryMultiHit: ") + sptr_last_error(ctx_);
+    return false;
+  }
+  return true;
+}
+
 bool HipBackend::renderRays(const float* rays, const uint32_t* seeds, uint32_t n, uint32_t samples, uint32_t frame_index,
                             float* radiance, bool accumulate, bool normalize, RayRenderInfo* info) {
   if (!ctx_ || !built_) {

@@ -126,6 +126,14 @@ class HipBackend {
     std::vector<uint8_t> occluded;
   };
   bool queryRays(const float* rays, uint32_t n, bool anyHit, HitBuffers& out);
+  // sptr_query_multi_hit with host pointers: per ray the maxHits nearest hits in ascending (t, geomID, primID).
+  // count has n entries; hit j of ray i is element i * maxHits + j of geom, prim, t, ng (x 3) and uv (x 2), the
+  // slots beyond a ray's count filled as include/sptr_hip.h describes.
+  struct MultiHitBuffers {
+    std::vector<uint32_t> count, geom, prim;
+    std::vector<float> t, ng, uv;
+  };
+  bool queryMultiHit(const float* rays, uint32_t n, uint32_t maxHits, MultiHitBuffers& out);
   // sptr_render_rays with host pointers: the wavefront integrator's radiance along n caller-supplied rays of 8
   // floats (o3, unit d3, two ignored words) against the built scene and the current materials, lights and
   // environment, Settings::max_depth bounces deep.  radiance (n x 3) takes, per ray, the sum of `samples` paths

@@ -135,6 +135,16 @@ class RayQuery(C.Structure):
                 ("occluded", C.c_void_p), ("reserved", C.c_uint64 * 4)]
 
 
+class MultiHitQuery(C.Structure):
+    """sptr_multi_hit_query: pointers as addresses (host or device, by SPTR_QUERY_DEVICE_PTRS)."""
+    _fields_ = [("rays", C.c_void_p), ("n", C.c_uint32), ("flags", C.c_uint32), ("max_hits", C.c_uint32),
+                ("pad", C.c_uint32), ("count", C.c_void_p), ("geom", C.c_void_p), ("prim", C.c_void_p),
+                ("t", C.c_void_p), ("ng", C.c_void_p), ("uv", C.c_void_p), ("reserved", C.c_uint64 * 4)]
+
+
+SPTR_MULTI_HIT_MAX = 16
+
+
 class RayRender(C.Structure):
     """sptr_ray_render: pointers as addresses (host or device, by SPTR_RAYS_DEVICE_PTRS)."""
     _fields_ = [("rays", C.c_void_p), ("seeds", C.c_void_p), ("n", C.c_uint32), ("samples", C.c_uint32),
@@ -177,7 +187,7 @@ EXPORTS = [
     "sptr_set_history_motion", "sptr_read_motion", "sptr_motion_info",
     "sptr_set_dynamic", "sptr_update_geometry", "sptr_refit_info",
     "sptr_set_rest_positions", "sptr_update_transforms", "sptr_tree_cost",
-    "sptr_query_rays", "sptr_query_info", "sptr_render_rays", "sptr_ray_render_info",
+    "sptr_query_rays", "sptr_query_info", "sptr_query_multi_hit", "sptr_multi_hit_info", "sptr_render_rays", "sptr_ray_render_info",
     "sptr_render_adaptive", "sptr_read_sample_counts",
     "sptr_host_builtin_scene", "sptr_host_scene_view", "sptr_host_scene_free", "sptr_host_camera_lookat",
     "sptr_host_preset_materials", "sptr_host_default_lights", "sptr_host_equirect_to_faces",
@@ -256,6 +266,8 @@ def lib() -> C.CDLL:
         "sptr_tree_cost": (C.c_int, [vp] + [C.POINTER(C.c_double)] * 4),
         "sptr_query_rays": (C.c_int, [vp, C.POINTER(RayQuery), vp]),
         "sptr_query_info": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), up, up]),
+        "sptr_query_multi_hit": (C.c_int, [vp, C.POINTER(MultiHitQuery), vp]),
+        "sptr_multi_hit_info": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), up, up, up, up]),
         "sptr_render_rays": (C.c_int, [vp, C.POINTER(RayRender), vp]),
         "sptr_ray_render_info": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(u64), C.POINTER(u64), up]),
         "sptr_render_adaptive": (C.c_int, [vp, C.POINTER(Frame), C.POINTER(AdaptiveParams), C.POINTER(AdaptiveInfo)]),
@@ -871,6 +883,86 @@ class Renderer:
         so, n = C.c_uint32(), C.c_uint32()
         self._check(self._L.sptr_query_info(self._h, C.byref(s), C.byref(t), C.byref(so), C.byref(n)), "query_info")
         return {"ms_sort": s.value, "ms_trace": t.value, "sorted": so.value, "queries": n.value}
+
+    def query_multi_hit(self, rays, max_hits: int, sort: bool | None = None, fields=None, out: dict | None = None,
+                        stream: int | None = None) -> dict:
+        """sptr_query_multi_hit: per ray the max_hits = K nearest hits in ascending (t, geomID, primID)
+        (include/sptr_hip.h states which hits a primitive gives).  rays, sort, out and stream are query_rays'.
+
+        The result is a dict with count (n, uint32: the hits found, at most K) and the per-hit arrays named by
+        fields (default: all of geom, prim, t, ng, uv), shaped (n, K), (n, K, 3) for ng and (n, K, 2) for uv;
+        slots at and beyond a ray's count hold 0xFFFFFFFF ids, t = +inf and zeros.  numpy in, numpy out; device
+        tensors in, torch tensors out."""
+        K = int(max_hits)
+        device = hasattr(rays, "data_ptr")
+        if device:
+            import torch
+
+            if rays.element_size() != 4 or not rays.is_floating_point() or not rays.is_contiguous() or rays.numel() % 8:
+                raise SptrError("query_multi_hit: device rays must be a contiguous float32 tensor of n x 8")
+            n = rays.numel() // 8
+            tdt = {np.uint32: torch.uint32, np.float32: torch.float32}
+
+            def alloc(shape, dt):
+                return torch.empty(shape, dtype=tdt[dt], device=rays.device)
+
+            def addr(a):
+                return a.data_ptr()
+
+            def ok(a, size, dt):
+                return a.is_contiguous() and a.numel() == size and a.dtype == tdt[dt] and a.device == rays.device
+        else:
+            if stream is not None:
+                raise SptrError("query_multi_hit: a stream needs device tensors")
+            rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+            n = len(rays)
+
+            def alloc(shape, dt):
+                return np.zeros(shape, dt)
+
+            def addr(a):
+                return a.ctypes.data
+
+            def ok(a, size, dt):
+                return isinstance(a, np.ndarray) and a.flags.c_contiguous and a.size == size and a.dtype == dt
+        known = [g for g, _, _ in self._QUERY_FIELDS]
+        names = known if fields is None else list(fields)
+        if any(f not in known for f in names):
+            raise SptrError(f"query_multi_hit: fields must name some of geom, prim, t, ng, uv (got {names})")
+        kk = max(K, 0)
+        want = (("count", (n,), np.uint32),) + tuple((f, (n, kk, cols) if cols > 1 else (n, kk), dt)
+                                                     for f, cols, dt in self._QUERY_FIELDS if f in names)
+        res = {}
+        for name, shape, dt in want:
+            a = (out or {}).get(name)
+            if a is None:
+                a = alloc(shape, dt)
+            elif not ok(a, int(np.prod(shape)), dt):
+                raise SptrError(f"query_multi_hit: out[{name!r}] must be contiguous, of {shape} {np.dtype(dt).name}")
+            res[name] = a
+        q = MultiHitQuery()
+        q.rays = addr(rays) if n else None
+        q.n = n
+        q.max_hits = K if 0 <= K < 2 ** 32 else 0
+        q.flags = ((SPTR_QUERY_DEVICE_PTRS if device else 0)
+                   | (0 if sort is None else SPTR_QUERY_SORT if sort else SPTR_QUERY_NO_SORT))
+        for name, a in res.items():  # (an empty tensor has no address: n == 0 writes nothing)
+            setattr(q, name, addr(a) or (C.addressof(self._QUERY_EMPTY) if n == 0 else None))
+        if device and stream is None and n:
+            torch.cuda.current_stream(rays.device).synchronize()  # the rays' (and the outputs') producers
+        self._check(self._L.sptr_query_multi_hit(self._h, C.byref(q), C.c_void_p(stream) if stream else None),
+                    "query_multi_hit")
+        return res
+
+    def multi_hit_info(self) -> dict:
+        """sptr_multi_hit_info: waits for the last multi-hit query; query_info's values for it, and the list
+        capacity and LDS bytes per block of the kernel instantiation it launched."""
+        s, t = C.c_double(), C.c_double()
+        so, n, cap, lds = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+        self._check(self._L.sptr_multi_hit_info(self._h, C.byref(s), C.byref(t), C.byref(so), C.byref(n), C.byref(cap),
+                                                C.byref(lds)), "multi_hit_info")
+        return {"ms_sort": s.value, "ms_trace": t.value, "sorted": so.value, "queries": n.value,
+                "list_capacity": cap.value, "lds_bytes": lds.value}
 
     def render_rays(self, rays, seeds=None, samples: int = 1, frame_index: int = 1, max_depth: int = 6,
                     accumulate: bool = False, normalize: bool = False, out=None, stream: int | None = None):

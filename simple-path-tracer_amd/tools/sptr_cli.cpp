@@ -5,7 +5,7 @@
 //   sptr_cli [--scene default|default_emitter|test_triangle|sphere_mesh:STACKS:SLICES|gltf:PATH]
 //            [--w 800] [--h 600] [--spp 4] [--depth 6] [--env sky|FILE.hdr] [--out image.ppm]
 //            [--warmup N] [--json] [--integrator wavefront|pathtracer|optix] [--spf 4] [--launch-mode 0-3]
-//            [--lagged] [--denoise N] [--history [M]] [--motion] [--orbit DEG] [--animate K [--rebuild] [--rigid]] [--query-centre-rays]
+//            [--lagged] [--denoise N] [--history [M]] [--motion] [--orbit DEG] [--animate K [--rebuild] [--rigid]] [--query-centre-rays [--multi-hit K]]
 // --spp N renders N progressive frames of 1 spp each (GLRenderer's m_accumulated_samples loop);
 // --warmup N renders N untimed frames first (then restarts the accumulation by a camera change);
 // --json prints one line with per-frame wall-clock statistics (render + RGB8 read back, as the
@@ -37,6 +37,8 @@
 // --query-centre-rays: after the render, the W x H pixel-centre rays of the camera (the rays of the first-hit
 // AOVs: direction getRayDirection((x + 0.5) / W, (y + 0.5) / H), tnear 0, tfar inf) go through
 // HipBackend::queryRays; the --json line adds "query": {"rays": n, "hits": h, "tri_hits": k}.
+// --multi-hit K (with --query-centre-rays): the same rays also go through HipBackend::queryMultiHit, and the
+// "query" object gains "multi_hit": {"k": K, "hits": all hits listed, "count_hist": rays that listed 0 .. K hits}.
 // --panorama W H: instead of the frames, an equirectangular panorama of W x H pixels from the camera position
 // through HipBackend::renderRays (sptr_render_rays): row y has polar angle theta = pi (y + 0.5) / H from +Y and
 // column x azimuth phi = 2 pi (x + 0.5) / W, both evaluated in float32 as written (float(pi) times the float
@@ -86,6 +88,7 @@ int main(int argc, char** argv) {
   std::string scene_name = "default", env = "sky", out = "image.ppm";
   int w = 800, h = 600, spp = 4, depth = 6, warmup = 0;
   bool json = false, lagged = false, rebuild = false, query_centre = false, motion = false, rigid = false;
+  int multi_hit = 0;  // --multi-hit K
   int pano_w = 0, pano_h = 0;
   bool adaptive = false, spp_given = false;
   double adaptive_thr = 0.0;
@@ -125,6 +128,7 @@ int main(int argc, char** argv) {
     else if (a == "--rebuild") rebuild = true;
     else if (a == "--rigid") rigid = true;
     else if (a == "--query-centre-rays") query_centre = true;
+    else if (a == "--multi-hit" && i + 1 < argc) multi_hit = std::atoi(argv[++i]);
     else if (a == "--panorama") {
       pano_w = std::atoi(next());
       pano_h = std::atoi(next());
@@ -134,7 +138,7 @@ int main(int argc, char** argv) {
       }
     }
     else {
-      std::fprintf(stderr, "usage: %s [--scene S] [--w W] [--h H] [--spp N] [--depth D] [--env sky|F.hdr] [--out F] [--warmup N] [--json] [--lagged] [--denoise N] [--history [M]] [--motion] [--orbit DEG] [--animate K [--rebuild] [--rigid]] [--query-centre-rays] [--panorama W H] [--adaptive THR [--min-spp A] [--step K] [--counts F]]\n",
+      std::fprintf(stderr, "usage: %s [--scene S] [--w W] [--h H] [--spp N] [--depth D] [--env sky|F.hdr] [--out F] [--warmup N] [--json] [--lagged] [--denoise N] [--history [M]] [--motion] [--orbit DEG] [--animate K [--rebuild] [--rigid]] [--query-centre-rays [--multi-hit K]] [--panorama W H] [--adaptive THR [--min-spp A] [--step K] [--counts F]]\n",
                    argv[0]);
       return 2;
     }
@@ -339,7 +343,12 @@ int main(int argc, char** argv) {
   const sptr_stats tot = be.flushStats();  // (lagged: waits for the last frames, inside the clock)
   const double wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   const uint64_t rays = tot.rays_closest + tot.rays_shadow;
-  size_t q_rays = 0, q_hits = 0, q_tri_hits = 0;
+  size_t q_rays = 0, q_hits = 0, q_tri_hits = 0, mh_hits = 0;
+  std::vector<size_t> mh_hist;
+  if (multi_hit != 0 && (!query_centre || multi_hit < 0)) {
+    std::fprintf(stderr, "--multi-hit K needs --query-centre-rays and K >= 1\n");
+    return 1;
+  }
   if (query_centre) {
     std::vector<float> qr(size_t(w) * h * 8);
     const sptr_camera dc = cam.toDevice();
@@ -364,6 +373,18 @@ int main(int argc, char** argv) {
       ++q_hits;
       if (g < tri_geoms) ++q_tri_hits;
     }
+    if (multi_hit > 0) {  // the same rays through sptr_query_multi_hit: how many of them found 0, 1, .. K hits
+      backends::HipBackend::MultiHitBuffers mb;
+      if (!be.queryMultiHit(qr.data(), uint32_t(size_t(w) * h), uint32_t(multi_hit), mb)) {
+        std::fprintf(stderr, "%s\n", be.lastError().c_str());
+        return 1;
+      }
+      mh_hist.assign(size_t(multi_hit) + 1, 0);
+      for (uint32_t c : mb.count) {
+        mh_hits += c;
+        ++mh_hist[std::min<size_t>(c, size_t(multi_hit))];
+      }
+    }
   }
   const double ms = tot.ms_total;
   if (json) {
@@ -387,7 +408,15 @@ int main(int argc, char** argv) {
     std::printf(", \"rigid\": %d, \"transform_updates\": %d, \"tree_cost\": %.17g, \"root_area\": %.17g, "
                 "\"tree_cost_at_build\": %.17g, \"root_area_at_build\": %.17g",
                 rigid ? 1 : 0, sent_transforms, tc[0], tc[1], tc[2], tc[3]);
-    if (query_centre) std::printf(", \"query\": {\"rays\": %zu, \"hits\": %zu, \"tri_hits\": %zu}", q_rays, q_hits, q_tri_hits);
+    if (query_centre) {
+      std::printf(", \"query\": {\"rays\": %zu, \"hits\": %zu, \"tri_hits\": %zu", q_rays, q_hits, q_tri_hits);
+      if (multi_hit > 0) {
+        std::printf(", \"multi_hit\": {\"k\": %d, \"hits\": %zu, \"count_hist\": [", multi_hit, mh_hits);
+        for (size_t i = 0; i < mh_hist.size(); ++i) std::printf("%s%zu", i ? ", " : "", mh_hist[i]);
+        std::printf("]}");
+      }
+      std::printf("}");
+    }
     std::printf("}\n");
   } else {
     std::printf("scene=%s %dx%d spp=%d depth=%d: %.2f ms device, %.2f ms wall, %.1f Mrays/s (device)\n",
