@@ -253,6 +253,24 @@ int sptr_set_bounce_chain(sptr_ctx* ctx, uint32_t mode);
  * first batch, 0 if it did not split. */
 int sptr_set_sky_split(sptr_ctx* ctx, uint32_t mode, uint32_t bulk_threads);
 int sptr_sky_split_info(sptr_ctx* ctx, uint32_t* bulk_threads);
+/* Shadow entries (symbols added within ABI 9: no existing struct or entry point changed): for a scene staged in
+ * LDS with one directional light, whose shadow rays are traced in place by the shading launches, a table of
+ * R x R light-space cells holds where a shadow ray whose origin projects into the cell starts its walk of the
+ * BVH: nowhere (nothing can occlude it), at a node, or at one leaf's sub-range.  The table is built at the
+ * first render call that qualifies and serves every call until the scene (upload, refit, transforms) or the
+ * light changes.  mode 0 = off; 1 = automatic (the default): the first table after an upload is built by a
+ * wavefront call of at least 2^23 samples, a table that replaces one ended by a refit, a transform update or
+ * another light direction only by a call of at least 2^27 (an animated scene walks from the root below that
+ * and pays no build), and a cached table is used by every call; 2 = built by any wavefront call.  The image and the ray counters
+ * do not depend on it.  sptr_shadow_entries_info: the setting, the builds so far and, while a table is
+ * current, its cells per side, its bytes, and the shares of cells whose walk starts below the root and of
+ * cells whose rays are unoccluded without a walk. */
+typedef struct sptr_shadow_entries_info_t {
+  uint32_t mode, cells, bytes, builds;
+  float cells_below_root, cells_unoccluded;
+} sptr_shadow_entries_info_t;
+int sptr_set_shadow_entries(sptr_ctx* ctx, uint32_t mode);
+int sptr_shadow_entries_info(sptr_ctx* ctx, sptr_shadow_entries_info_t* out);
 /* Maximum primitives per BVH leaf range (1..16; 0 = automatic, the default: 8 for scenes staged in
  * LDS, 1 otherwise); applies to the next sptr_upload_scene. */
 int sptr_set_leaf_size(sptr_ctx* ctx, uint32_t max_prims);

@@ -1041,16 +1041,18 @@ __device__ __forceinline__ bool traverse_w(const Staged& sc, const SceneView& sv
 constexpr uint32_t kEntryFieldBits = 13, kEntryFieldMask = (1u << kEntryFieldBits) - 1u;
 // traverse_w of a bounce-0 camera ray from the walk root its pixel starts at (primary_root: kNoHit, a node,
 // the scene's own leaf-range root, or a leaf entry); the wide BVH has no entries and starts at its root
-template <bool kW4, bool kCount, int N>
-__device__ __forceinline__ bool traverse_w_from(const Staged& sc, const SceneView& sv, uint32_t root, const Ray& r,
+// kAny, tnear: the query (a camera ray: closest hit from 0; a shadow ray from its cell's entry, shadow_occluded:
+// any hit from 1e-4)
+template <bool kW4, bool kAny, bool kCount, int N>
+__device__ __forceinline__ bool traverse_w_from(const Staged& sc, const SceneView& sv, uint32_t root, const Ray& r, float tnear,
                                                 float& tfar, uint32_t& ref, Visits& vc, LdsStackN<N>& ls) {
   if constexpr (kW4) {
-    return traverse_wide<false, kCount>(sc.nodes4, sc.prim_ref, sc.tris, sc.sph, sv.root4, r, 0.0f, tfar, ref, vc, ls);
+    return traverse_wide<kAny, kCount>(sc.nodes4, sc.prim_ref, sc.tris, sc.sph, sv.root4, r, tnear, tfar, ref, vc, ls);
   } else {
     if (root & kLeafBit) {  // (kNoHit too: the caller tests it first)
       // the scene's own root when the scene is one leaf range; else a leaf entry (k_cull<true>, entry_leaf): the
       // leaf's box, held by its parent, then the entry's sub-range
-      if (root == sv.root) return leaf_test<false, kCount>(root, sc.prim_ref, sc.tris, sc.sph, r, 0.0f, tfar, ref, vc);
+      if (root == sv.root) return leaf_test<kAny, kCount>(root, sc.prim_ref, sc.tris, sc.sph, r, tnear, tfar, ref, vc);
       // The one child's six planes are read by address (16 + 8 bytes), not both boxes and a select.
       // The entry is decoded here, at each use.  It is a per-pixel value: hoisted out of the callers' sample
       // loops, the decoded addresses stayed live across them (k_trace_wp: three registers spilled, two reloads
@@ -1064,12 +1066,44 @@ __device__ __forceinline__ bool traverse_w_from(const Staged& sc, const SceneVie
       const float2 z = reinterpret_cast<const float2*>(nd + 2)[right];           // z.xy | z.zw
       if (kCount) ++vc.nodes;
       float tent;
-      if (!slab(xy.x, xy.y, xy.z, xy.w, z.x, z.y, r, 0.0f, tfar, tent)) return false;
+      if (!slab(xy.x, xy.y, xy.z, xy.w, z.x, z.y, r, tnear, tfar, tent)) return false;
       const uint32_t range = kLeafBit | (((root >> 4) & kEntryFieldMask) << kLeafCountBits) | (root & kLeafRangeMask);
-      return leaf_test<false, kCount>(range, sc.prim_ref, sc.tris, sc.sph, r, 0.0f, tfar, ref, vc);
+      return leaf_test<kAny, kCount>(range, sc.prim_ref, sc.tris, sc.sph, r, tnear, tfar, ref, vc);
     }
-    return traverse<false, kCount>(sc.nodes, sc.prim_ref, sc.tris, sc.sph, root, r, 0.0f, tfar, ref, vc, ls);
+    return traverse<kAny, kCount>(sc.nodes, sc.prim_ref, sc.tris, sc.sph, root, r, tnear, tfar, ref, vc, ls);
   }
+}
+
+// The in-place shadow ray {so, ldir, [1e-4, stfar]} of lights[0] in an LDS-staged BVH2 scene: is it occluded?
+// With a shadow entry table (sh.shadow_entry: one directional light) the walk starts at the entry of the
+// origin's light-space cell: nowhere (kNoHit: no primitive can be hit from the cell), at a node or at one
+// leaf's sub-range.  An origin outside the table, or no table, starts at the scene's root, which is the walk
+// traverse_w<false, true> makes.  The skipped subtrees hold no primitive that any ray of the cell can hit
+// (shadow_entry.h), so the answer is the root walk's.
+// shadow_root is the lookup alone.  k_shade_trace, where the time is, asks for the word as soon as the light
+// term has the origin and ahead of continue_path, whose arithmetic hides the load's latency: one register held
+// across continue_path, none across eval_brdf (C2, builds alternated, five runs each: looked up at the walk
+// 1.765-1.785 ms/step, ahead of the continuation 1.749-1.769).
+// The other kernels look it up at the walk.
+__device__ __forceinline__ uint32_t shadow_root(const SceneView& sv, const ShadeView& sh, vec3 so) {
+  uint32_t root = sv.root;
+  if (sh.shadow_entry) {
+    uint32_t i, j;
+    if (shadow_cell(sh.shadow_frame, so, i, j)) root = sh.shadow_entry[j * sh.shadow_frame.R + i];
+  }
+  return root;
+}
+template <bool kCount, int N>
+__device__ __forceinline__ bool shadow_occluded_from(const Staged& sc, const SceneView& sv, uint32_t root, vec3 so, vec3 ldir,
+                                                     float stfar, Visits& vc, LdsStackN<N>& ls) {
+  if (root == kNoHit) return false;
+  uint32_t ref = kNoHit;
+  return traverse_w_from<false, true, kCount>(sc, sv, root, make_ray(so, ldir), 1e-4f, stfar, ref, vc, ls);
+}
+template <bool kCount, int N>
+__device__ __forceinline__ bool shadow_occluded(const Staged& sc, const SceneView& sv, const ShadeView& sh, vec3 so, vec3 ldir,
+                                                float stfar, Visits& vc, LdsStackN<N>& ls) {
+  return shadow_occluded_from<kCount>(sc, sv, shadow_root(sv, sh, so), so, ldir, stfar, vc, ls);
 }
 
 // traverse_w with the wide BVH's top levels read from an LDS copy (stage_top; ntop = 0: none) — the
@@ -1284,33 +1318,53 @@ __device__ __forceinline__ Box child_box(const BvhNode& g, bool right) {
   return right ? Box{v3(g.rxy.x, g.rxy.z, g.z.z), v3(g.rxy.y, g.rxy.w, g.z.w)}
                : Box{v3(g.lxy.x, g.lxy.z, g.z.x), v3(g.lxy.y, g.lxy.w, g.z.y)};
 }
+// The region whose rays a descent (cull_descend) tests boxes and primitives against: box_out / sphere_out /
+// tri_out answer "no ray of the region can hit this", erring only towards "may hit".
+// A pixel quad's pyramid of camera rays (cull_entry; cull_prims.h).
+struct PyramidRegion {
+  CullPyramid py;
+  __device__ __forceinline__ bool box_out(const Box& b) const { return box_outside(b, py.n, py.o); }
+  // The primitive's own box against the side planes first (box_outside, ~40 instructions): most primitives
+  // of a touched leaf lie far from the quad, and the exact tests (a few hundred instructions, with square
+  // roots) then run only for those near it.  The boxes are padded by more than the exact tests' own
+  // inflation and rounding (cull_prims.h), so the prefilter culls nothing they would keep.
+  __device__ __forceinline__ bool sphere_out(float4 s) const {
+    const vec3 c = v3(s.x, s.y, s.z), v = c - py.o;
+    const float rb = fabsf(s.w) + 1.1e-3f * (fabsf(v.x) + fabsf(v.y) + fabsf(v.z)) +
+                     1e-5f * (py.ol + fabsf(c.x) + fabsf(c.y) + fabsf(c.z));
+    return box_outside(Box{c - v3(rb, rb, rb), c + v3(rb, rb, rb)}, py.n, py.o) || cull_sphere_outside(py, c, s.w);
+  }
+  __device__ __forceinline__ bool tri_out(vec3 v0, vec3 v1, vec3 v2) const {
+    const vec3 lo3 = v3(fminf(v0.x, fminf(v1.x, v2.x)), fminf(v0.y, fminf(v1.y, v2.y)), fminf(v0.z, fminf(v1.z, v2.z)));
+    const vec3 hi3 = v3(fmaxf(v0.x, fmaxf(v1.x, v2.x)), fmaxf(v0.y, fmaxf(v1.y, v2.y)), fmaxf(v0.z, fmaxf(v1.z, v2.z)));
+    const float pad = 1e-5f * (fabsf(lo3.x) + fabsf(lo3.y) + fabsf(lo3.z) + fabsf(hi3.x) + fabsf(hi3.y) + fabsf(hi3.z) + py.ol);
+    return box_outside(Box{lo3 - v3(pad, pad, pad), hi3 + v3(pad, pad, pad)}, py.n, py.o) || cull_triangle_outside(py, v0, v1, v2);
+  }
+};
+// A light-space cell's prism of directional shadow rays (k_shadow_entries; shadow_entry.h).
+struct PrismRegion {
+  ShadowPrism p;
+  __device__ __forceinline__ bool box_out(const Box& b) const { return shadow_box_outside(p, b.lo, b.hi); }
+  __device__ __forceinline__ bool sphere_out(float4 s) const { return shadow_sphere_outside(p, v3(s.x, s.y, s.z), s.w); }
+  __device__ __forceinline__ bool tri_out(vec3 v0, vec3 v1, vec3 v2) const { return shadow_triangle_outside(p, v0, v1, v2); }
+};
 // candidates of one leaf range: their first and last position in prim_ref (lo > hi: none)
-__device__ __forceinline__ void cull_leaf(const Staged& sc, const CullPyramid& py, uint32_t link, uint32_t& lo, uint32_t& hi) {
+template <class Region>
+__device__ __forceinline__ void cull_leaf(const Staged& sc, const Region& rg, uint32_t link, uint32_t& lo, uint32_t& hi) {
   const uint32_t start = (link & ~kLeafBit) >> kLeafCountBits, cnt = (link & kLeafRangeMask) + 1u;
   lo = kNoHit;
   hi = 0u;
   for (uint32_t j = 0; j < cnt; ++j) {
     const uint32_t pr = sc.prim_ref[start + j];
     const uint32_t idx = pr & kIndexMask;
-    // The primitive's own box against the side planes first (box_outside, ~40 instructions): most primitives
-    // of a touched leaf lie far from the quad, and the exact tests (a few hundred instructions, with square
-    // roots) then run only for those near it.  The boxes are padded by more than the exact tests' own
-    // inflation and rounding (cull_prims.h), so the prefilter culls nothing they would keep.
     bool out;
     if (pr & kSphereBit) {
-      const float4 s = sc.sph[idx];
-      const vec3 c = v3(s.x, s.y, s.z), v = c - py.o;
-      const float rb = fabsf(s.w) + 1.1e-3f * (fabsf(v.x) + fabsf(v.y) + fabsf(v.z)) +
-                       1e-5f * (py.ol + fabsf(c.x) + fabsf(c.y) + fabsf(c.z));
-      out = box_outside(Box{c - v3(rb, rb, rb), c + v3(rb, rb, rb)}, py.n, py.o) || cull_sphere_outside(py, c, s.w);
+      out = rg.sphere_out(sc.sph[idx]);
     } else {
       // triangle record: v0, e1 = v0 - v1, e2 = v2 - v0 (tri_hit4)
       const float4 a = sc.tris[3u * idx], b = sc.tris[3u * idx + 1u], c = sc.tris[3u * idx + 2u];
       const vec3 v0 = v3(a.x, a.y, a.z), v1 = v0 - v3(a.w, b.x, b.y), v2 = v0 + v3(b.z, b.w, c.x);
-      const vec3 lo3 = v3(fminf(v0.x, fminf(v1.x, v2.x)), fminf(v0.y, fminf(v1.y, v2.y)), fminf(v0.z, fminf(v1.z, v2.z)));
-      const vec3 hi3 = v3(fmaxf(v0.x, fmaxf(v1.x, v2.x)), fmaxf(v0.y, fmaxf(v1.y, v2.y)), fmaxf(v0.z, fmaxf(v1.z, v2.z)));
-      const float pad = 1e-5f * (fabsf(lo3.x) + fabsf(lo3.y) + fabsf(lo3.z) + fabsf(hi3.x) + fabsf(hi3.y) + fabsf(hi3.z) + py.ol);
-      out = box_outside(Box{lo3 - v3(pad, pad, pad), hi3 + v3(pad, pad, pad)}, py.n, py.o) || cull_triangle_outside(py, v0, v1, v2);
+      out = rg.tri_out(v0, v1, v2);
     }
     if (!out) {
       lo = min(lo, start + j);
@@ -1322,21 +1376,12 @@ __device__ __forceinline__ uint32_t entry_leaf(uint32_t parent, uint32_t side, u
   if (parent >= kEntryFieldMask || hi > kEntryFieldMask) return parent;  // (does not fit: the parent node, a plain entry)
   return kLeafBit | (parent << 18) | (side << 17) | (lo << 4) | (hi - lo);
 }
+// The descent itself, for the rays of region rg (a scene with a root node), down to at most `limit` levels.
 // sc: the scene as the block staged it in LDS (the descent's node and primitive reads are dependent loads)
-__device__ __forceinline__ uint32_t cull_entry(const Staged& sc, const SceneView& sv, const FrameView& f, int x, int y, int npx,
-                                               CullStack& cs) {
-  if (sv.root == kNoHit) return kNoHit;
-  const float u0 = (float(x) - kCullMarginPx) / float(f.W), u1 = (float(x + npx) + kCullMarginPx) / float(f.W);
-  const float v0 = (float(y) - kCullMarginPx) / float(f.H), v1 = (float(y + npx) + kCullMarginPx) / float(f.H);
-  auto dir = [&](float u, float v) {
-    return f.cam_f + ((u - 0.5f) * 2.0f * f.half_w) * f.cam_r + (-(v - 0.5f) * 2.0f * f.half_h) * f.cam_u;
-  };
-  const CullPyramid py = cull_pyramid(f.cam_pos, dir(u0, v0), dir(u1, v0), dir(u1, v1), dir(u0, v1));
+template <class Region>
+__device__ __forceinline__ uint32_t cull_descend(const Staged& sc, const SceneView& sv, const Region& rg, uint32_t limit,
+                                                 CullStack& cs) {
   uint32_t lo, hi;
-  // a scene that is one leaf range has no box to test first: as in the box cull, nothing is culled and every
-  // camera ray tests the range (tests/test_gpu_bounce_order.py counts on those rays being traced)
-  if ((sv.root & kLeafBit) || sv.num_nodes == 0u) return sv.root;
-  const uint32_t limit = min(f.cull_depth, (uint32_t)kCullEntryDepth);
   uint32_t* st = &cs.st[0][threadIdx.x];     // entry i at st[i * kBlock]
   uint16_t* path = &cs.path[0][threadIdx.x];  // likewise
   int sp = 0;
@@ -1344,11 +1389,11 @@ __device__ __forceinline__ uint32_t cull_entry(const Staged& sc, const SceneView
   // popped since the last candidate (the path beyond it has been, or may be, overwritten)
   uint32_t ncand = 0u, common = kNoHit, mind = kNoHit, anc = sv.root, one_lo = 0u, one_hi = 0u, one_side = 0u;
   bool one_leaf = false;  // the candidates so far are primitives of one leaf, child one_side of anc: prim_ref[one_lo .. one_hi]
-  auto push_children = [&](uint32_t node, uint32_t depth) {  // the children whose boxes the pyramid may touch
+  auto push_children = [&](uint32_t node, uint32_t depth) {  // the children whose boxes the region may touch
     const BvhNode g = sc.nodes[node];
     path[(depth - 1u) * kBlock] = (uint16_t)node;
-    if (!box_outside(child_box(g, true), py.n, f.cam_pos)) st[sp++ * kBlock] = cull_pack(g.link.y, depth, 1u);
-    if (!box_outside(child_box(g, false), py.n, f.cam_pos)) st[sp++ * kBlock] = cull_pack(g.link.x, depth, 0u);
+    if (!rg.box_out(child_box(g, true))) st[sp++ * kBlock] = cull_pack(g.link.y, depth, 1u);
+    if (!rg.box_out(child_box(g, false))) st[sp++ * kBlock] = cull_pack(g.link.x, depth, 0u);
   };
   push_children(sv.root, 1u);
   while (sp > 0) {
@@ -1356,7 +1401,7 @@ __device__ __forceinline__ uint32_t cull_entry(const Staged& sc, const SceneView
     const uint32_t link = e & (kCullLeaf - 1u), depth = (e >> 18) & 63u, side = (e >> 24) & 1u;  // its ancestors: path[0 .. depth)
     mind = min(mind, depth);
     if (e & kCullLeaf) {
-      cull_leaf(sc, py, kLeafBit | ((link >> 4) << kLeafCountBits) | (link & kLeafRangeMask), lo, hi);
+      cull_leaf(sc, rg, kLeafBit | ((link >> 4) << kLeafCountBits) | (link & kLeafRangeMask), lo, hi);
       if (lo > hi) continue;
       one_leaf = ncand++ == 0u;
       common = one_leaf ? depth : min(common, mind);  // (the first candidate's ancestors: path[0 .. depth))
@@ -1382,6 +1427,20 @@ __device__ __forceinline__ uint32_t cull_entry(const Staged& sc, const SceneView
   if (ncand == 0u) return kNoHit;
   if (one_leaf) return entry_leaf(anc, one_side, one_lo, one_hi);
   return anc;
+}
+__device__ __forceinline__ uint32_t cull_entry(const Staged& sc, const SceneView& sv, const FrameView& f, int x, int y, int npx,
+                                               CullStack& cs) {
+  if (sv.root == kNoHit) return kNoHit;
+  const float u0 = (float(x) - kCullMarginPx) / float(f.W), u1 = (float(x + npx) + kCullMarginPx) / float(f.W);
+  const float v0 = (float(y) - kCullMarginPx) / float(f.H), v1 = (float(y + npx) + kCullMarginPx) / float(f.H);
+  auto dir = [&](float u, float v) {
+    return f.cam_f + ((u - 0.5f) * 2.0f * f.half_w) * f.cam_r + (-(v - 0.5f) * 2.0f * f.half_h) * f.cam_u;
+  };
+  const PyramidRegion rg{cull_pyramid(f.cam_pos, dir(u0, v0), dir(u1, v0), dir(u1, v1), dir(u0, v1))};
+  // a scene that is one leaf range has no box to test first: as in the box cull, nothing is culled and every
+  // camera ray tests the range (tests/test_gpu_bounce_order.py counts on those rays being traced)
+  if ((sv.root & kLeafBit) || sv.num_nodes == 0u) return sv.root;
+  return cull_descend(sc, sv, rg, min(f.cull_depth, (uint32_t)kCullEntryDepth), cs);
 }
 // one entry word per 2x2 pixel quad, in k_cull's thread order: tile, then quad row, then quad column
 __device__ __forceinline__ uint32_t entry_index(uint32_t l) {
@@ -1744,7 +1803,7 @@ __global__ void __launch_bounds__(kBlock, kW4 ? SPTR_TRACE4_WAVES : SPTR_TRACE_P
         if (!(ablate(f) & 2u) && root != kNoHit) {
           const Ray r = make_ray(f.cam_pos, pr.d);
           const uint32_t v0 = vc.nodes;
-          hit = traverse_w_from<kW4, kCount>(sc, sv, root, r, tfar, ref, vc, s_stack);
+          hit = traverse_w_from<kW4, false, kCount>(sc, sv, root, r, 0.0f, tfar, ref, vc, s_stack);
           if (kCount) hist_ray(s_hist, vc.nodes - v0);
         }
         if (!hit) {
@@ -1873,7 +1932,7 @@ __global__ void __launch_bounds__(kBlock, kW4 ? SPTR_TRACE4_WAVES : (kHiOcc ? 8 
         if (root != kNoHit) {
           const Ray r = make_ray(f.cam_pos, pr.d);
           const uint32_t v0 = vc.nodes;
-          if constexpr (kEntries) hit = traverse_w_from<kW4, kCount>(sc, sv, root, r, tfar, ref, vc, s_stack);
+          if constexpr (kEntries) hit = traverse_w_from<kW4, false, kCount>(sc, sv, root, r, 0.0f, tfar, ref, vc, s_stack);
           else hit = traverse_w<kW4, false, kCount>(sc, sv, r, 0.0f, tfar, ref, vc, s_stack);
           if (kCount) hist_ray(s_hist, vc.nodes - v0);
         }
@@ -1999,7 +2058,7 @@ __global__ void __launch_bounds__(kBlock, (kW4 && !kPrimary) ? SPTR_TRACE4_WAVES
       // 1 = constant environment, 4 = primary misses write no radiance
       if (!(kPrimary && ((ablate(f) & 2u) || culled))) {
         const uint32_t v0 = vc.nodes;
-        if constexpr (kPrimary && kLds && !kW4) hit = traverse_w_from<kW4, kCount>(sc, sv, root, r, tfar, ref, vc, s_stack);
+        if constexpr (kPrimary && kLds && !kW4) hit = traverse_w_from<kW4, false, kCount>(sc, sv, root, r, 0.0f, tfar, ref, vc, s_stack);
         else hit = traverse_w<kW4, false, kCount>(sc, sv, r, 0.0f, tfar, ref, vc, s_stack);
         if (kCount) hist_ray(s_hist, vc.nodes - v0);
       }
@@ -2646,10 +2705,8 @@ __global__ void __launch_bounds__(kBlock, SPTR_SHADE_WAVES)
     }
     if (kFuse) {
       if (lit) {
-        const Ray r = make_ray(so, ldir);
-        uint32_t ref = kNoHit;
         ++rays;
-        if (!traverse_w<false, true, false>(sc, sv, r, 1e-4f, stfar, ref, vc, s_stack)) {
+        if (!shadow_occluded<false>(sc, sv, sh, so, ldir, stfar, vc, s_stack)) {
           if (!dirty) radv = xyz(w.rad[p]);  // kPrimary starts dirty at zero radiance
           dirty = true;
           radv = radv + contrib;
@@ -2736,9 +2793,8 @@ __device__ __forceinline__ void bounce_ray(const Staged& sc, const SceneView& sv
     rout.thr[seg0 + jn] = f4(thr, 0.0f);
   }
   if (lit) {
-    uint32_t ref = kNoHit;
     ++rays;
-    if (!traverse_w<false, true, false>(sc, sv, make_ray(so, ldir), 1e-4f, stfar, ref, vc, s_stack)) {
+    if (!shadow_occluded<false>(sc, sv, sh, so, ldir, stfar, vc, s_stack)) {
       if (!dirty) radv = xyz(w.rad[p]);
       dirty = true;
       radv = radv + contrib;
@@ -2834,9 +2890,8 @@ __device__ __forceinline__ void bounce01_path(const Staged& sc, const SceneView&
       const bool lit = light_faces(sh.lights[0], sf) && light_term(sh.lights[0], sf, -pr.d, thr, so, ldir, stfar, contrib);
       active = continue_path(sf, pr.d, 0u, thr, rng, ro, rd) && !last1;
       if (lit) {
-        uint32_t sref = kNoHit;
         ++rays;
-        if (!traverse_w<false, true, false>(sc, sv, make_ray(so, ldir), 1e-4f, stfar, sref, vc, s_stack)) radv = radv + contrib;
+        if (!shadow_occluded<false>(sc, sv, sh, so, ldir, stfar, vc, s_stack)) radv = radv + contrib;
       }
     }
   }
@@ -2868,9 +2923,8 @@ __device__ __forceinline__ void bounce01_path(const Staged& sc, const SceneView&
     rout.thr[seg0 + jn] = f4(thr, 0.0f);
   }
   if (lit) {
-    uint32_t sref = kNoHit;
     ++rays;
-    if (!traverse_w<false, true, false>(sc, sv, make_ray(so, ldir), 1e-4f, stfar, sref, vc, s_stack)) radv = radv + contrib;
+    if (!shadow_occluded<false>(sc, sv, sh, so, ldir, stfar, vc, s_stack)) radv = radv + contrib;
   }
   if (valid) w.rad[p] = f4(radv, 0.0f);
 }
@@ -3081,12 +3135,13 @@ __device__ __forceinline__ void rad_add(const WaveView& w, uint32_t p, bool& dir
   radv = radv + c;
 }
 // One lit light's in-place shadow ray (Light::isOccluded): the contribution is added if nothing is hit.
-__device__ __forceinline__ void shadow_add(const Staged& sc, const SceneView& sv, const WaveView& w, uint32_t p, vec3 so,
-                                           vec3 ldir, float stfar, vec3 contrib, bool& dirty, vec3& radv, Visits& vc,
-                                           LdsStack& s_stack, uint32_t& rays) {
-  uint32_t sref = kNoHit;
+// sroot: its walk root (shadow_root), asked for by the caller ahead of the continuation.
+__device__ __forceinline__ void shadow_add(const Staged& sc, const SceneView& sv, const ShadeView& sh, const FrameView& f,
+                                           const WaveView& w, uint32_t p, uint32_t sroot, vec3 so, vec3 ldir, float stfar,
+                                           vec3 contrib, bool& dirty, vec3& radv, Visits& vc, LdsStack& s_stack, uint32_t& rays) {
   ++rays;
-  if (!traverse_w<false, true, false>(sc, sv, make_ray(so, ldir), 1e-4f, stfar, sref, vc, s_stack))
+  // SPTR_ABLATE (timing experiments only, wrong images): 8 = the shadow ray is unoccluded without a walk
+  if ((ablate(f) & 8u) || !shadow_occluded_from<false>(sc, sv, sroot, so, ldir, stfar, vc, s_stack))
     rad_add(w, p, dirty, radv, contrib);
 }
 // The per-record body: the record of slot `slot` (valid: this thread holds one), its output appended to the
@@ -3099,7 +3154,7 @@ __device__ __forceinline__ void shade_trace(const Staged& sc, const SceneView& s
                                             uint32_t slot, uint32_t seg0, uint32_t* s_cnt, Visits& vc, LdsStack& s_stack,
                                             uint32_t& rays, uint32_t& traced) {
   bool active = false, dirty = kFirst && valid, lit = false;
-  uint32_t p = 0u, rng = 0u;
+  uint32_t p = 0u, rng = 0u, sroot = kNoHit;
   vec3 thr = v3(1.0f, 1.0f, 1.0f), radv = v3(0.0f, 0.0f, 0.0f), no, nd, so, ldir, contrib;
   float stfar = 0.0f;
   if (valid) {  // shade(depth - 1)
@@ -3133,10 +3188,13 @@ __device__ __forceinline__ void shade_trace(const Staged& sc, const SceneView& s
       const vec3 emission = v3(sf.m.emission[0], sf.m.emission[1], sf.m.emission[2]);
       if (dot(emission, emission) > 0.0f) rad_add(w, p, dirty, radv, thr * emission);
       if (light_faces(sh.lights[0], sf)) lit = light_term(sh.lights[0], sf, -rd, thr, so, ldir, stfar, contrib);
+      // the shadow ray's walk root (its cell's table word), asked for behind the light term and ahead of the
+      // continuation, whose arithmetic hides the load: one register across continue_path, none across eval_brdf
+      if (lit) sroot = shadow_root(sv, sh, so);
       active = continue_path(sf, rd, (uint32_t)(depth - 1), thr, rng, no, nd);
     }
   }
-  if (lit) shadow_add(sc, sv, w, p, so, ldir, stfar, contrib, dirty, radv, vc, s_stack, rays);
+  if (lit) shadow_add(sc, sv, sh, f, w, p, sroot, so, ldir, stfar, contrib, dirty, radv, vc, s_stack, rays);
   bool hit = false;
   float tfar = __builtin_huge_valf();
   uint32_t href = kNoHit;
@@ -3166,6 +3224,7 @@ __device__ __forceinline__ void shade_trace(const Staged& sc, const SceneView& s
       const vec3 emission = v3(sf.m.emission[0], sf.m.emission[1], sf.m.emission[2]);
       if (dot(emission, emission) > 0.0f) rad_add(w, p, dirty, radv, thr * emission);
       if (light_faces(sh.lights[0], sf)) lit = light_term(sh.lights[0], sf, -nd, thr, so, ldir, stfar, contrib);
+      if (lit) sroot = shadow_root(sv, sh, so);
       if (!last) cont = continue_path(sf, nd, (uint32_t)depth, thr, rng, no2, nd2);
     }
     const uint32_t jn = block_append(s_cnt, cont);
@@ -3178,7 +3237,7 @@ __device__ __forceinline__ void shade_trace(const Staged& sc, const SceneView& s
       rout.d[seg0 + jn] = f4(nd2, __uint_as_float(p));
       rout.thr[seg0 + jn] = f4(thr, 0.0f);
     }
-    if (lit) shadow_add(sc, sv, w, p, so, ldir, stfar, contrib, dirty, radv, vc, s_stack, rays);
+    if (lit) shadow_add(sc, sv, sh, f, w, p, sroot, so, ldir, stfar, contrib, dirty, radv, vc, s_stack, rays);
   }
   if (dirty) w.rad[p] = f4(radv, 0.0f);
 }
@@ -3271,12 +3330,16 @@ __global__ void __launch_bounds__(kBlock, kW4 ? SPTR_SHADOW4_WAVES : SPTR_SHADOW
       const vec3 dir = (ts > 2u && sh.lights[li].type != 0)
                            ? xyz(task[2])
                            : v3(sh.lights[li].v[0], sh.lights[li].v[1], sh.lights[li].v[2]);
-      const Ray r = make_ray(xyz(a), dir);
       float tfar = a.w;
-      uint32_t ref = kNoHit;
       ++rays;
       const uint32_t v0 = vc.nodes;
-      const bool occ = traverse_w<kW4, true, kCount>(sc, sv, r, 1e-4f, tfar, ref, vc, s_stack);
+      bool occ;
+      if (kLds && !kW4 && li == 0u) {  // the roots of the in-place shadow rays (the table is lights[0]'s)
+        occ = shadow_occluded<kCount>(sc, sv, sh, xyz(a), dir, tfar, vc, s_stack);
+      } else {
+        uint32_t ref = kNoHit;
+        occ = traverse_w<kW4, true, kCount>(sc, sv, make_ray(xyz(a), dir), 1e-4f, tfar, ref, vc, s_stack);
+      }
       if (kCount) hist_ray(s_hist, vc.nodes - v0);
       if (!occ) {
         if (!any) rv = xyz(w.rad[p]);
@@ -3499,9 +3562,14 @@ __global__ void __launch_bounds__(kBlock, kLds ? SPTR_TAIL_WAVES_LDS : SPTR_TAIL
         float st;
         if (!light_term(sh.lights[li], sf, view, thr, so, ldir, st, contrib)) continue;
         ++n_shadow;
-        uint32_t sref = kNoHit;
-        if (!traverse_w_top<kW4, true, false>(sc, sv, top, ntop, make_ray(so, ldir), 1e-4f, st, sref, vc, s_stack))
-          radv = radv + contrib;
+        bool occ;
+        if (kLds && !kW4 && li == 0u) {  // (the table is lights[0]'s)
+          occ = shadow_occluded<false>(sc, sv, sh, so, ldir, st, vc, s_stack);
+        } else {
+          uint32_t sref = kNoHit;
+          occ = traverse_w_top<kW4, true, false>(sc, sv, top, ntop, make_ray(so, ldir), 1e-4f, st, sref, vc, s_stack);
+        }
+        if (!occ) radv = radv + contrib;
       }
       vec3 no, nd;
       if (!continue_path(sf, rd, depth, thr, rng, no, nd)) break;
@@ -4670,6 +4738,24 @@ unsigned launch_shade(const SceneView& sv, const ShadeView& sh, const FrameView&
         }(fl);
       },
       Flags<>{}, depth == 0 && !stream_rays, fuse);
+}
+
+// The shadow entry table (shadow_entry.h): one thread per light-space cell runs cull_entry's descent with the
+// cell's prism for the region.  The scene is staged in LDS as in k_cull<true>; grid: R * R / kBlock blocks.
+__global__ void __launch_bounds__(kBlock) k_shadow_entries(SceneView sv, ShadowFrame fr, uint32_t* table) {
+  extern __shared__ float4 lds[];
+  __shared__ CullStack s_cs;
+  const Staged sc = stage_scene<true>(sv, lds);
+  __syncthreads();
+  const uint32_t cell = blockIdx.x * kBlock + threadIdx.x;
+  if (cell >= fr.R * fr.R) return;
+  const uint32_t j = cell / fr.R, i = cell - j * fr.R;
+  const PrismRegion rg{shadow_prism(fr, i, j)};
+  table[cell] = cull_descend(sc, sv, rg, (uint32_t)kCullEntryDepth, s_cs);
+}
+void launch_shadow_entries(const SceneView& sv, const ShadowFrame& fr, uint32_t* table, hipStream_t s) {
+  const uint32_t cells = fr.R * fr.R;
+  hipLaunchKernelGGL(k_shadow_entries, dim3((cells + kBlock - 1u) / kBlock), dim3(kBlock), sv.lds_bytes, s, sv, fr, table);
 }
 
 bool cull_entries_apply(const SceneView& sv) { return sv.lds_bytes != 0u && sv.width == 2u; }

@@ -483,9 +483,23 @@ FrameView frame_view(const Context& c, const sptr_frame& f) {
   return v;
 }
 
+// The shadow entry table of cc (Context::se) is current: built for cc's scene as it stands and for the light
+// direction of the one directional light the shading context holds.  What it was built for is its whole key:
+// an upload, a refit, a transform update or other lights leave it unused until refresh_shadow_entries rebuilds it.
+static bool shadow_entries_current(const Context& cc) {
+  const Context& c = shading(cc);
+  if (!cc.se.valid || cc.se.geom_rev != cc.geom_rev || c.lights_host.size() != 1u) return false;
+  const DevLight& l = c.lights_host[0];
+  return l.type == 0 && cc.se.light.type == 0 && std::memcmp(l.v, cc.se.light.v, sizeof(l.v)) == 0;
+}
+
 ShadeView shade_view(const Context& cc) {
   const Context& c = shading(cc);
   ShadeView s{};
+  if (cc.shadow_mode != 0u && shadow_entries_current(cc) && cull_entries_apply(scene_view(cc))) {
+    s.shadow_entry = static_cast<const uint32_t*>(cc.se.table.p);
+    s.shadow_frame = cc.se.frame;
+  }
   s.mats = static_cast<const DevMaterial*>(c.mats.p);
   s.num_mats = (uint32_t)c.mats_host.size();
   s.geom_mat = static_cast<const uint32_t*>(c.geom_mat.p);
@@ -1193,6 +1207,63 @@ uint32_t enqueue_wavefront(Context& c, const sptr_frame& f, uint32_t k, int T, h
   return waves;
 }
 
+// The shadow entry table (ShadeView::shadow_entry, shadow_entry.h) of a wavefront call: built on the render
+// stream ahead of the call's launch sequence, never inside it, when the call qualifies and no current table is
+// cached.  It qualifies when the scene is an LDS-staged BVH2 with a root node, its one light is directional and
+// the call's shadow rays are traced in place (shade_fuses_shadows), and, in the automatic mode, when the call is
+// large enough.  A cached table serves every call (shade_view), whatever its size.
+// The bounds follow kExactRecullMinSamples' reasoning, a fixed cost against a gain that grows with the call's
+// samples, with this table's figures: a build is one launch of the cull's descent (41 us on C2's scene) and a
+// 64-byte read-back with a stream synchronisation, about 55 us together, and the walks gain 0.41 us per million
+// samples (C2: 54 us on 132.7 M).
+//   The first build after an upload (kShadowEntryMinSamples, 2^23): a scene that is uploaded and then rendered
+//   keeps its table from call to call, so the build is paid once where the in-sequence cull is paid in every
+//   call.  A call of 2^23 samples gains 3.4 us; a caller that accumulates with calls of that size has the build
+//   back within sixteen of them (the pixel lanes of C2's 4-way shard and its 8-way shard, 16.6 M samples a call,
+//   are such callers; a 1-spp frame, 2 M at 1080p, is not).
+//   A rebuild (kShadowEntryRebuildMinSamples, 2^27): a table that a refit, a transform update or a turn of the
+//   light has ended says the caller animates, and the next change may end the new one after a single call.  That
+//   call alone must then pay: 55 us / 0.41 us per million = 134 M samples.  Below it the call walks from the
+//   root, as it did before there were tables, and pays neither the launch nor the synchronisation.
+// Bounds that give no usable frame are remembered with the scene and light they belong to and not read again.
+// A build changes the kernels' arguments, so it ends the validity of a captured launch graph (the epoch).
+constexpr uint64_t kShadowEntryMinSamples = 1ull << 23;
+constexpr uint64_t kShadowEntryRebuildMinSamples = 1ull << 27;
+int refresh_shadow_entries(Context& c, const sptr_frame& f, hipStream_t s) {
+  if (c.shadow_mode == 0u) return SPTR_OK;
+  const SceneView sv = scene_view(c);
+  const ShadeView sh = shade_view(c);
+  if (sh.shadow_entry) return SPTR_OK;  // current
+  if (!cull_entries_apply(sv) || !shade_fuses_shadows(sv, sh, false) || sh.lights[0].type != 0) return SPTR_OK;
+  if (sv.root == kNoHit || (sv.root & kLeafBit) || sv.num_nodes == 0u) return SPTR_OK;
+  const DevLight& l = sh.lights[0];
+  if (c.se.no_frame && c.se.geom_rev == c.geom_rev && std::memcmp(l.v, c.se.light.v, sizeof(l.v)) == 0) return SPTR_OK;
+  if (c.shadow_mode == 1u) {
+    const bool first = c.se.upload_rev != c.upload_rev;  // nothing was built for this upload yet
+    if ((uint64_t)c.P * f.spp < (first ? kShadowEntryMinSamples : kShadowEntryRebuildMinSamples)) return SPTR_OK;
+  }
+  BvhNode root;
+  API_HIP(hipMemcpyAsync(&root, sv.nodes + sv.root, sizeof(BvhNode), hipMemcpyDeviceToHost, s));
+  API_HIP(hipStreamSynchronize(s));
+  const vec3 lo = v3(std::min(root.lxy.x, root.rxy.x), std::min(root.lxy.z, root.rxy.z), std::min(root.z.x, root.z.z));
+  const vec3 hi = v3(std::max(root.lxy.y, root.rxy.y), std::max(root.lxy.w, root.rxy.w), std::max(root.z.y, root.z.w));
+  ShadowFrame fr;
+  c.se.valid = false;
+  c.se.geom_rev = c.geom_rev;
+  c.se.light = l;
+  c.se.upload_rev = c.upload_rev;
+  c.se.no_frame = !shadow_frame(v3(l.v[0], l.v[1], l.v[2]), lo, hi, kShadowEntryCells, fr);
+  if (c.se.no_frame) return SPTR_OK;  // (no usable bounds: root walks)
+  API_HIP(c.se.table.ensure((size_t)fr.R * fr.R * 4));
+  launch_shadow_entries(sv, fr, static_cast<uint32_t*>(c.se.table.p), s);
+  API_HIP(hipGetLastError());
+  c.se.valid = true;
+  c.se.frame = fr;
+  ++c.se.builds;
+  ++c.epoch;
+  return SPTR_OK;
+}
+
 // The bounce-0 pixel-frustum cull mask (and unculled-pixel list) of a wavefront call's camera.  It is
 // launched directly on the render stream ahead of the call's launch sequence, never inside it: a
 // captured launch graph therefore holds no k_cull, and whichever camera a replayed graph was
@@ -1684,6 +1755,14 @@ static int set_sky_split_one(sptr_ctx* x, uint32_t mode, uint32_t bulk_threads) 
   return SPTR_OK;
 }
 
+static int set_shadow_entries_one(sptr_ctx* x, uint32_t mode) {
+  if (!x) return SPTR_ERR_INVALID;
+  if (mode > 2u) return fail(x->c, SPTR_ERR_INVALID, "shadow entries must be 0 (off), 1 (automatic) or 2 (always)");
+  if (x->c.shadow_mode != mode) ++x->c.epoch;  // (the table is part of the shading launches' arguments)
+  x->c.shadow_mode = mode;
+  return SPTR_OK;
+}
+
 static int set_split_refs_one(sptr_ctx* x, uint32_t max_pieces) {
   if (!x) return SPTR_ERR_INVALID;
   if (max_pieces == 0u) max_pieces = 1u;
@@ -1740,6 +1819,8 @@ static int upload_scene_one(sptr_ctx* x, const sptr_scene* s) {
   if (rc != SPTR_OK) return rc;
   c.have_scene = true;
   ++c.epoch;
+  ++c.geom_rev;
+  ++c.upload_rev;
   return resolve_geom_materials(c);
 }
 
@@ -1930,6 +2011,8 @@ static int render_one(sptr_ctx* x, const sptr_frame* f, void* stream, sptr_stats
       if (rc != SPTR_OK) return rc;
     }
     const int T = std::max(1, (int)(c.tail_depth ? c.tail_depth : auto_tail_depth((uint64_t)k * c.P, scene_view(c))));
+    rc = refresh_shadow_entries(c, *f, s);  // (ahead of the key: a build bumps the epoch)
+    if (rc != SPTR_OK) return rc;
     key.epoch = c.epoch;  // ensure_wave may have reallocated
     key.k = k;
     key.tail = (uint32_t)T;
@@ -3179,6 +3262,7 @@ static int refit_one(Context& c, const float* d_pos, const float* d_sph, const f
   if (sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;  // a pending render may still read the old boxes
   const int rc = refit_lbvh(c, d_pos, reinterpret_cast<const float4*>(d_sph), d_xf);
   ++c.epoch;  // cull mask, AOV planes and captured graphs were computed for the old coordinates
+  ++c.geom_rev;  // ... and the shadow entry table
   return rc;
 }
 
@@ -4015,6 +4099,35 @@ int sptr_set_sky_split(sptr_ctx* x, uint32_t mode, uint32_t bulk_threads) {
 int sptr_sky_split_info(sptr_ctx* x, uint32_t* bulk_threads) {
   if (!x || !bulk_threads) return SPTR_ERR_INVALID;
   *bulk_threads = x->c.sky_split_last;
+  return SPTR_OK;
+}
+
+int sptr_set_shadow_entries(sptr_ctx* x, uint32_t mode) {
+  const int rc = set_shadow_entries_one(x, mode);
+  return rc == SPTR_OK ? lane_forward(x, set_shadow_entries_one(x ? x->lane : nullptr, mode)) : rc;
+}
+
+int sptr_shadow_entries_info(sptr_ctx* x, sptr_shadow_entries_info_t* out) {
+  if (!x || !out) return SPTR_ERR_INVALID;
+  Context& c = x->c;
+  std::memset(out, 0, sizeof(*out));
+  out->mode = c.shadow_mode;
+  out->builds = c.se.builds;
+  if (!shade_view(c).shadow_entry) return SPTR_OK;  // no current table
+  const uint32_t R = c.se.frame.R, n = R * R;
+  std::vector<uint32_t> words(n);
+  API_HIP(hipSetDevice(c.device));
+  API_HIP(hipDeviceSynchronize());  // (the build ran on the stream of the call that made it)
+  API_HIP(hipMemcpy(words.data(), c.se.table.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  uint32_t below = 0u, none = 0u;
+  for (uint32_t w : words) {
+    below += w != c.root ? 1u : 0u;
+    none += w == kNoHit ? 1u : 0u;
+  }
+  out->cells = R;
+  out->bytes = n * 4u;
+  out->cells_below_root = (float)below / (float)n;
+  out->cells_unoccluded = (float)none / (float)n;
   return SPTR_OK;
 }
 

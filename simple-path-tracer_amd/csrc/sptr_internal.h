@@ -24,6 +24,7 @@
 #include "hit_list.h"
 #include "prim_mat_table.h"
 #include "ray_batch.h"
+#include "shadow_entry.h"
 #include "sptr_hip.h"
 #include "sptr_math.h"
 #include "tile_map.h"
@@ -152,6 +153,11 @@ struct ShadeView {
   // read it from global memory.  Not part of SceneView::lds_bytes.
   const uint32_t* prim_mat;
   uint32_t pm_lds_bytes;
+  // Walk entry words of lights[0]'s shadow rays, one per light-space cell (k_shadow_entries, shadow_entry.h):
+  // kNoHit (unoccluded, no walk), a node, or a leaf entry; cell (i, j) at [j * R + i].  Null: no table, every
+  // shadow ray walks from the scene's root.  Set only for one directional light and an LDS-staged BVH2 scene.
+  const uint32_t* shadow_entry;
+  ShadowFrame shadow_frame;
 };
 
 struct FrameView {
@@ -588,6 +594,21 @@ struct Context {
   DevBuf cull;   // bounce-0 pixel-frustum cull mask, 1 bit per local pixel (k_cull)
   DevBuf plist;  // the local pixels k_cull did not cull, each tile's run in pixel order; their count at [P]
   DevBuf entry;  // the exact cull's walk entry word per 2x2 pixel quad (FrameView::entry), computed with the mask
+  // Shadow entries (ShadeView::shadow_entry): the table and what it was built for.  geom_rev counts this
+  // context's scene uploads and refits; the light is the parent's lights[0] for a pixel lane.
+  uint64_t geom_rev = 1;
+  uint64_t upload_rev = 1;   // counts this context's scene uploads alone
+  uint32_t shadow_mode = 1;  // sptr_set_shadow_entries: 0 off, 1 automatic, 2 always
+  struct ShadowEntries {
+    DevBuf table;
+    bool valid = false;
+    uint64_t geom_rev = 0;
+    DevLight light{};
+    uint64_t upload_rev = 0;   // the upload the last build (or refused build) belonged to
+    bool no_frame = false;     // geom_rev / light are those of bounds that gave no usable frame: not tried again
+    ShadowFrame frame{};
+    uint32_t builds = 0;
+  } se;
   // what the mask was computed for (state epoch, camera): k_cull reruns only when these change
   uint64_t cull_epoch = 0;
   sptr_camera cull_cam{};
@@ -688,6 +709,10 @@ bool cull_entries_apply(const SceneView& sv);
 // list_culled: also the culled valid pixels, from the back of plist (a call whose bounce 0 splits, sky_split.h)
 void launch_cull(const SceneView& sv, const FrameView& f, uint32_t* mask, uint32_t* plist, uint32_t* entry, bool list_culled,
                  hipStream_t s);
+// Cells per side of the shadow entry table ("Shadow entries": the sweep of 64 / 128 / 256).
+constexpr uint32_t kShadowEntryCells = 128;
+// one entry word per cell of fr (an LDS-staged BVH2 scene with a root node): table[j * R + i]
+void launch_shadow_entries(const SceneView& sv, const ShadowFrame& fr, uint32_t* table, hipStream_t s);
 // capped: at most 4 waves per SIMD (beside the launch chain); else full occupancy
 void launch_sky(const ShadeView& sh, const FrameView& f, bool capped, hipStream_t s);
 // k_sky's list mode (f.split_threads bulk threads, sky_split.h) and the threads of its resident grid

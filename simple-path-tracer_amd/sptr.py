@@ -118,6 +118,11 @@ class TreeOrderInfo(C.Structure):
                 ("cost_sah", C.c_double), ("cost_morton", C.c_double)]
 
 
+class ShadowEntriesInfo(C.Structure):  # sptr_shadow_entries_info_t
+    _fields_ = [("mode", C.c_uint32), ("cells", C.c_uint32), ("bytes", C.c_uint32), ("builds", C.c_uint32),
+                ("cells_below_root", C.c_float), ("cells_unoccluded", C.c_float)]
+
+
 class DenoiseParams(C.Structure):
     _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_depth", C.c_float),
                 ("sigma_albedo", C.c_float), ("normal_log2_power", C.c_uint32), ("reserved", C.c_uint32 * 3)]
@@ -176,7 +181,7 @@ _lib = None
 # every symbol include/sptr_hip.h declares
 EXPORTS = [
     "sptr_abi_version", "sptr_create", "sptr_destroy", "sptr_last_error", "sptr_set_debug_mode",
-    "sptr_set_wave_paths", "sptr_set_launch_mode", "sptr_set_pixel_lanes", "sptr_pixel_lanes_info", "sptr_graph_info", "sptr_capture_error", "sptr_overlap_probe", "sptr_set_tail_depth", "sptr_set_bounce_chain", "sptr_set_sky_split", "sptr_sky_split_info", "sptr_set_leaf_size", "sptr_set_tree_order", "sptr_tree_info", "sptr_set_split_refs", "sptr_set_stragglers", "sptr_set_bvh_width", "sptr_upload_scene", "sptr_set_materials", "sptr_set_lights",
+    "sptr_set_wave_paths", "sptr_set_launch_mode", "sptr_set_pixel_lanes", "sptr_pixel_lanes_info", "sptr_graph_info", "sptr_capture_error", "sptr_overlap_probe", "sptr_set_tail_depth", "sptr_set_bounce_chain", "sptr_set_sky_split", "sptr_sky_split_info", "sptr_set_shadow_entries", "sptr_shadow_entries_info", "sptr_set_leaf_size", "sptr_set_tree_order", "sptr_tree_info", "sptr_set_split_refs", "sptr_set_stragglers", "sptr_set_bvh_width", "sptr_upload_scene", "sptr_set_materials", "sptr_set_lights",
     "sptr_set_environment", "sptr_scene_info", "sptr_scene_layout_info", "sptr_render", "sptr_collect_stats",
     "sptr_read_rgb8", "sptr_read_rgb8_lagged",
     "sptr_read_accum",
@@ -222,6 +227,8 @@ def lib() -> C.CDLL:
         "sptr_set_bounce_chain": (C.c_int, [vp, u32]),
         "sptr_set_sky_split": (C.c_int, [vp, u32, u32]),
         "sptr_sky_split_info": (C.c_int, [vp, C.POINTER(u32)]),
+        "sptr_set_shadow_entries": (C.c_int, [vp, u32]),
+        "sptr_shadow_entries_info": (C.c_int, [vp, C.POINTER(ShadowEntriesInfo)]),
         "sptr_set_leaf_size": (C.c_int, [vp, u32]),
         "sptr_set_tree_order": (C.c_int, [vp, u32]),
         "sptr_tree_info": (C.c_int, [vp, C.POINTER(TreeOrderInfo)]),
@@ -627,6 +634,19 @@ class Renderer:
         t = C.c_uint32()
         self._check(self._L.sptr_sky_split_info(self._h, C.byref(t)), "sky_split_info")
         return {"bulk_threads": t.value}
+
+    def set_shadow_entries(self, mode: int):
+        """0 off, 1 automatic (the first table after an upload built by a call of at least 2^23 samples, a rebuild
+        after a refit, transform update or light change by one of at least 2^27; a cached table always used), 2
+        built by any wavefront call (sptr_set_shadow_entries)."""
+        self._check(self._L.sptr_set_shadow_entries(self._h, mode), "set_shadow_entries")
+
+    def shadow_entries_info(self) -> dict:
+        """{"mode", "cells" per side, "bytes", "builds", "cells_below_root", "cells_unoccluded"}; cells 0: no
+        current table (sptr_shadow_entries_info)."""
+        i = ShadowEntriesInfo()
+        self._check(self._L.sptr_shadow_entries_info(self._h, C.byref(i)), "shadow_entries_info")
+        return {k: getattr(i, k) for k, _ in ShadowEntriesInfo._fields_}
 
     def set_leaf_size(self, n: int):
         self._check(self._L.sptr_set_leaf_size(self._h, n), "set_leaf_size")
