@@ -708,6 +708,67 @@ int sptr_query_multi_hit(sptr_ctx* ctx, const sptr_multi_hit_query* query, void*
 int sptr_multi_hit_info(sptr_ctx* ctx, double* ms_sort, double* ms_trace, uint32_t* sorted, uint32_t* queries,
                         uint32_t* list_capacity, uint32_t* lds_bytes);
 
+/* ---- closest-point queries (symbols added within ABI 9: no existing struct or entry point changed) ---------
+ * Which surface point is nearest to this point, and how far is it: distance fields, collision and contact,
+ * snapping, registration, occupancy.  One walk per point, pruned by the distance to a node's box
+ * (k_pointquery).  csrc/closest_point.h is the normative text; in words:
+ *
+ * Candidate of a primitive for point p:
+ *   triangle: from the stored record (v0, e1 = v0 - v1, e2 = v2 - v0, in the uploaded index order), the nearest
+ *             of four points in float32: the clamped projections of p onto the three edges, and the projection
+ *             onto the face (an orthogonalised two-by-two solve) when its weights are inside the triangle.  Each
+ *             is a convex combination q = (1 - u - v) v0 + u v1 + v v2 with clamped weights (sptr_query_rays'
+ *             vertex convention), and its d2 is dot(p - q, p - q) of that q, never a plane distance.  A triangle
+ *             left out of the tree because it is exactly degenerate (a stored normal of exactly zero) gives
+ *             nothing; a triangle the tree references several times (sptr_set_split_refs) is one primitive.
+ *   sphere  : a surface, as for rays: m = p - c, len = sqrt(m.m), d2 = (len - r)^2, q = c + m (r / len), or
+ *             c + (r, 0, 0) when len == 0; ng = (q - c) / r per component (0 for a radius of 0); uv = 0.
+ * Result of point i (p.xyz, max_dist): the candidate with the smallest key (d2, geomID, primID) among those
+ * with d2 <= max_dist * max_dist (one float32 multiply), d2 compared as float and the ids as unsigned, resolved
+ * as sptr_query_rays reports them (a sphere has prim 0).  max_dist = +inf accepts everything.  The result
+ * depends on nothing but the scene and the point: not on the tree, its width, the leaf size, the tree order,
+ * split references, a refit or the order of the walk.  Outputs: geom, prim, dist2 = d2, dist = sqrt(dist2)
+ * (correctly rounded), point = q, uv = (u, v), ng (the stored unnormalised triangle normal, as
+ * sptr_query_rays).  A miss — nothing within max_dist, max_dist negative or NaN, a coordinate of p that is
+ * not finite (no walk for the last two) — gives ids 0xFFFFFFFF, dist2 = dist = +inf, point = uv = ng = 0.
+ * Coordinates so large that their differences overflow float32 are outside the definition.
+ *
+ * Pointers, streams, order and scratch: the rules of sptr_query_rays, word for word.  Host pointers are staged
+ * and the call is synchronous; a non-NULL stream is for device pointers only and only enqueues; consecutive
+ * enqueued queries (of any kind) must share one stream; n == 0 returns SPTR_OK with no launch; a
+ * traversal-stack overflow is reported as sptr_query_rays reports it.  SPTR_QUERY_SORT walks the batch in the
+ * order of a 30-bit Morton code of p; with neither sort flag the library decides (at present it never sorts).
+ * SPTR_POINT_COUNT makes the kernel count its node visits and primitive tests (sptr_point_query_info).
+ * SPTR_ERR_INVALID: SPTR_QUERY_ANY_HIT or an unknown flag, both sort flags, n > 2^28, NULL points with n > 0,
+ * non-zero reserved, a device point buffer not 16-byte aligned or a device output not 4-byte aligned, host
+ * pointers with a stream, a lane context.  SPTR_ERR_NO_SCENE before an upload.  A refused call writes nothing
+ * and leaves the context as it was. */
+enum { SPTR_POINT_COUNT = 16u };            /* with SPTR_QUERY_DEVICE_PTRS | SPTR_QUERY_SORT | SPTR_QUERY_NO_SORT */
+typedef struct sptr_point_query {
+  const float* points;   /* n x 4 floats: p.xyz, max_dist; 16-byte aligned when a device pointer */
+  uint32_t n;            /* <= 2^28 */
+  uint32_t flags;
+  uint32_t* geom;        /* outputs; each may be NULL and is then not written */
+  uint32_t* prim;
+  float* dist2;          /* n */
+  float* dist;           /* n; sqrt(dist2), correctly rounded */
+  float* point;          /* n x 3 */
+  float* uv;             /* n x 2 */
+  float* ng;             /* n x 3, unnormalised, as sptr_query_rays */
+  uint64_t reserved[4];  /* 0 */
+} sptr_point_query;
+int sptr_query_points(sptr_ctx* ctx, const sptr_point_query* query, void* stream);
+/* Waits for the last point query: the device times of its sort phase and of its walk, whether it was sorted,
+ * the point queries launched so far, and the node visits and primitive tests of the last query if it set
+ * SPTR_POINT_COUNT (0 otherwise); zeros before the first.  SPTR_ERR_HIP if it set the traversal-stack-overflow
+ * flag, as sptr_query_info.  Any pointer may be NULL. */
+int sptr_point_query_info(sptr_ctx* ctx, double* ms_sort, double* ms_walk, uint32_t* sorted, uint32_t* queries,
+                          uint64_t* node_visits, uint64_t* prim_tests);
+/* The host twin: the same definition by brute force over every primitive of `scene`, host pointers only, no
+ * context and no device (flags must be 0 or sort flags, which are ignored).  The records are built with the
+ * expressions the device uses.  It is the CPU fallback of HipBackend::queryPoints and the tests' yardstick. */
+int sptr_host_query_points(const sptr_scene* scene, const sptr_point_query* query);
+
 /* ---- path-traced radiance for caller-supplied rays (symbols added within ABI 9: no existing struct or
  *      entry point changed) ------------------------------------------------------------------------------
  * sptr_render renders through the reference's pinhole camera and sptr_query_rays answers what a ray hits; this

@@ -5063,6 +5063,7 @@ void launch_primary(const FrameView& f, float* dirs, uint32_t* rng, hipStream_t 
 #include "kernels_denoise.h"
 // batched ray queries on caller buffers (the same traversal, staged or wide as the render kernels')
 #include "kernels_query.h"
+#include "kernels_points.h"
 // path-traced radiance for caller-supplied rays: the producer and consumer around the chain's depth-0 entry
 #include "kernels_rays.h"
 // adaptive sampling: the selection, and a producer and consumer of list entries around the same entry

@@ -114,6 +114,14 @@ struct sptr_ctx {
     bool issued = false, sorted = false;
     uint32_t count = 0, list_capacity = 0, lds_bytes = 0;
   } mh;
+  // sptr_query_points: shares rq's scratch like mh; its own events and facts for sptr_point_query_info, and the two
+  // 64-bit counters of a SPTR_POINT_COUNT query (allocated by the first such query)
+  struct PointQuery {
+    sptr::DevEvent ev[3];  // begin, after the sort, end
+    sptr::DevBuf counters;
+    bool issued = false, sorted = false, counted = false;
+    uint32_t count = 0, lds_bytes = 0;
+  } pq;
   // sptr_render_rays (the caller's context; a pixel lane holds none): the call's own totals block (WaveView::tot
   // of its launches, so that the render totals never see them), the carried sum of a ray whose sample range is
   // split, the staging of host-pointer calls, and the events of the last call: begin and end on the context's
@@ -151,6 +159,7 @@ struct sptr_ctx {
     // a query enqueued on a caller's stream (the caller synchronises it first; this costs nothing then)
     if (rq.issued) (void)hipEventSynchronize(rq.ev[2]);
     if (mh.issued) (void)hipEventSynchronize(mh.ev[2]);
+    if (pq.issued) (void)hipEventSynchronize(pq.ev[2]);
     if (reg_ptr) (void)hipHostUnregister(reg_ptr);
     delete lane;
   }
@@ -2351,6 +2360,7 @@ static int query_wait(sptr_ctx* x) {
   Context& c = x->c;
   if (x->rq.issued) API_HIP(hipEventSynchronize(x->rq.ev[2]));
   if (x->mh.issued) API_HIP(hipEventSynchronize(x->mh.ev[2]));
+  if (x->pq.issued) API_HIP(hipEventSynchronize(x->pq.ev[2]));
   return SPTR_OK;
 }
 
@@ -2660,6 +2670,158 @@ int sptr_multi_hit_info(sptr_ctx* x, double* ms_sort, double* ms_trace, uint32_t
   if (list_capacity) *list_capacity = mh.list_capacity;
   if (lds_bytes) *lds_bytes = mh.lds_bytes;
   return mh.issued ? query_check_flag(x) : SPTR_OK;
+}
+
+// ---- closest-point queries ----------------------------------------------------------------------------
+constexpr uint32_t kPointFlags = SPTR_QUERY_DEVICE_PTRS | SPTR_QUERY_SORT | SPTR_QUERY_NO_SORT | SPTR_POINT_COUNT;
+// Order of a point query that sets neither sort flag: §6d's rule.  No batch size at which keys + sort + sorted walk
+// beat the unsorted walk by more than the spread has been measured, so the default never sorts.
+static bool points_sort_by_default(const SceneView&, uint32_t) { return false; }
+
+// One validated batch with device pointers, enqueued on s: [keys, radix sort,] walk; enqueue_query's twin.
+static int enqueue_points(sptr_ctx* x, const sptr_point_query& q, hipStream_t s) {
+  Context& c = x->c;
+  auto& rq = x->rq;
+  auto& pq = x->pq;
+  const SceneView sv = scene_view(c);
+  const bool sort = (q.flags & SPTR_QUERY_SORT) != 0u ||
+                    ((q.flags & SPTR_QUERY_NO_SORT) == 0u && sv.lds_bytes == 0u && points_sort_by_default(sv, q.n));
+  const bool count = (q.flags & SPTR_POINT_COUNT) != 0u;
+  for (DevEvent& e : pq.ev)
+    if (!e) API_HIP(hipEventCreate(e.put()));
+  const int rs = query_scratch(x, q.n, sort, s);
+  if (rs != SPTR_OK) return rs;
+  if (count) {
+    if (!pq.counters.p) {
+      const int rw = query_wait(x);
+      if (rw != SPTR_OK) return rw;
+      API_HIP(pq.counters.ensure(16));
+    }
+    API_HIP(hipMemsetAsync(pq.counters.p, 0, 16, s));
+  }
+  PointQueryView v{};
+  v.points = reinterpret_cast<const float4*>(q.points);
+  v.n = q.n;
+  v.geom = q.geom;
+  v.prim = q.prim;
+  v.dist2 = q.dist2;
+  v.dist = q.dist;
+  v.point = q.point;
+  v.uv = q.uv;
+  v.ng = q.ng;
+  v.tri_orig = static_cast<const uint32_t*>(c.tri_orig.p);
+  v.geom_first = static_cast<const uint32_t*>(x->geom_first.p);
+  v.stack_overflow = static_cast<uint32_t*>(rq.flag.p);
+  v.counters = count ? static_cast<unsigned long long*>(pq.counters.p) : nullptr;
+  API_HIP(hipEventRecord(pq.ev[0], s));
+  if (sort) {
+    launch_point_keys(sv, v.points, q.n, static_cast<uint64_t*>(rq.keys.p), static_cast<uint32_t*>(rq.index.p), s);
+    API_HIP(hipGetLastError());
+    size_t tb = rq.temp.bytes;
+    API_HIP(radix_sort_pairs_u64(rq.temp.p, tb, static_cast<const uint64_t*>(rq.keys.p),
+                                 static_cast<uint64_t*>(rq.keys_sorted.p), static_cast<const uint32_t*>(rq.index.p),
+                                 static_cast<uint32_t*>(rq.order.p), q.n, s));
+    API_HIP(hipEventRecord(pq.ev[1], s));
+    v.order = static_cast<const uint32_t*>(rq.order.p);
+  }
+  launch_pointquery(sv, v, s, &pq.lds_bytes);
+  API_HIP(hipGetLastError());
+  API_HIP(hipEventRecord(pq.ev[2], s));
+  pq.issued = true;
+  pq.sorted = sort;
+  pq.counted = count;
+  ++pq.count;
+  return SPTR_OK;
+}
+
+int sptr_query_points(sptr_ctx* x, const sptr_point_query* q, void* stream) {
+  if (!x || !q) return SPTR_ERR_INVALID;
+  Context& c = x->c;
+  if (x->is_lane) return fail(c, SPTR_ERR_INVALID, "query_points: not on a lane context");
+  const bool dev = (q->flags & SPTR_QUERY_DEVICE_PTRS) != 0u;
+  if (q->flags & ~kPointFlags) return fail(c, SPTR_ERR_INVALID, "query_points: SPTR_QUERY_ANY_HIT or unknown flags");
+  if ((q->flags & SPTR_QUERY_SORT) && (q->flags & SPTR_QUERY_NO_SORT))
+    return fail(c, SPTR_ERR_INVALID, "query_points: SPTR_QUERY_SORT and SPTR_QUERY_NO_SORT exclude each other");
+  if (q->n > kQueryMaxRays) return fail(c, SPTR_ERR_INVALID, "query_points: more than 2^28 points");
+  if (q->n && !q->points) return fail(c, SPTR_ERR_INVALID, "query_points: no points");
+  if (q->reserved[0] || q->reserved[1] || q->reserved[2] || q->reserved[3])
+    return fail(c, SPTR_ERR_INVALID, "query_points: reserved must be 0");
+  if (!dev && stream) return fail(c, SPTR_ERR_INVALID, "query_points: host pointers cannot be enqueued on a stream");
+  if (dev && ((reinterpret_cast<uintptr_t>(q->points) & 15u) || (reinterpret_cast<uintptr_t>(q->geom) & 3u) ||
+              (reinterpret_cast<uintptr_t>(q->prim) & 3u) || (reinterpret_cast<uintptr_t>(q->dist2) & 3u) ||
+              (reinterpret_cast<uintptr_t>(q->dist) & 3u) || (reinterpret_cast<uintptr_t>(q->point) & 3u) ||
+              (reinterpret_cast<uintptr_t>(q->uv) & 3u) || (reinterpret_cast<uintptr_t>(q->ng) & 3u)))
+    return fail(c, SPTR_ERR_INVALID, "query_points: the device point buffer must be 16-byte aligned, the outputs 4-byte aligned");
+  if (!c.have_scene) return fail(c, SPTR_ERR_NO_SCENE, "query_points: no scene");
+  if (q->n == 0u) return SPTR_OK;
+  API_HIP(hipSetDevice(c.device));
+  if (stream) return enqueue_points(x, *q, static_cast<hipStream_t>(stream));  // only enqueues
+  if (sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;
+  const int rw = query_wait(x);
+  if (rw != SPTR_OK) return rw;
+  sptr_point_query d = *q;
+  const size_t n = q->n;
+  // host pointers: points in, then geom | prim | dist2 | dist | point | uv | ng out, staged in the context
+  const size_t off_prim = n * 4, off_d2 = off_prim + n * 4, off_d = off_d2 + n * 4, off_pt = off_d + n * 4,
+               off_uv = off_pt + n * 12, off_ng = off_uv + n * 8, total = off_ng + n * 12;
+  if (!dev) {
+    auto& rq = x->rq;
+    API_HIP(rq.stage_in.ensure(n * 16));
+    API_HIP(rq.stage_out.ensure(total));
+    API_HIP(hipMemcpy(rq.stage_in.p, q->points, n * 16, hipMemcpyHostToDevice));
+    char* o = static_cast<char*>(rq.stage_out.p);
+    d.points = static_cast<const float*>(rq.stage_in.p);
+    d.geom = q->geom ? reinterpret_cast<uint32_t*>(o) : nullptr;
+    d.prim = q->prim ? reinterpret_cast<uint32_t*>(o + off_prim) : nullptr;
+    d.dist2 = q->dist2 ? reinterpret_cast<float*>(o + off_d2) : nullptr;
+    d.dist = q->dist ? reinterpret_cast<float*>(o + off_d) : nullptr;
+    d.point = q->point ? reinterpret_cast<float*>(o + off_pt) : nullptr;
+    d.uv = q->uv ? reinterpret_cast<float*>(o + off_uv) : nullptr;
+    d.ng = q->ng ? reinterpret_cast<float*>(o + off_ng) : nullptr;
+  }
+  const int rc = enqueue_points(x, d, c.stream);
+  if (rc != SPTR_OK) return rc;
+  API_HIP(hipStreamSynchronize(c.stream));
+  const int rf = query_check_flag(x);
+  if (rf != SPTR_OK) return rf;
+  if (!dev) {
+    if (q->geom) API_HIP(hipMemcpy(q->geom, d.geom, n * 4, hipMemcpyDeviceToHost));
+    if (q->prim) API_HIP(hipMemcpy(q->prim, d.prim, n * 4, hipMemcpyDeviceToHost));
+    if (q->dist2) API_HIP(hipMemcpy(q->dist2, d.dist2, n * 4, hipMemcpyDeviceToHost));
+    if (q->dist) API_HIP(hipMemcpy(q->dist, d.dist, n * 4, hipMemcpyDeviceToHost));
+    if (q->point) API_HIP(hipMemcpy(q->point, d.point, n * 12, hipMemcpyDeviceToHost));
+    if (q->uv) API_HIP(hipMemcpy(q->uv, d.uv, n * 8, hipMemcpyDeviceToHost));
+    if (q->ng) API_HIP(hipMemcpy(q->ng, d.ng, n * 12, hipMemcpyDeviceToHost));
+  }
+  return SPTR_OK;
+}
+
+int sptr_point_query_info(sptr_ctx* x, double* ms_sort, double* ms_walk, uint32_t* sorted, uint32_t* queries,
+                          uint64_t* node_visits, uint64_t* prim_tests) {
+  if (!x) return SPTR_ERR_INVALID;
+  Context& c = x->c;
+  auto& pq = x->pq;
+  double ms_s = 0.0, ms_w = 0.0;
+  uint64_t cnt[2] = {0, 0};
+  if (pq.issued) {
+    API_HIP(hipSetDevice(c.device));
+    API_HIP(hipEventSynchronize(pq.ev[2]));
+    float ms = 0.0f;
+    if (pq.sorted) {
+      API_HIP(hipEventElapsedTime(&ms, pq.ev[0], pq.ev[1]));
+      ms_s = ms;
+    }
+    API_HIP(hipEventElapsedTime(&ms, pq.sorted ? pq.ev[1] : pq.ev[0], pq.ev[2]));
+    ms_w = ms;
+    if (pq.counted) API_HIP(hipMemcpy(cnt, pq.counters.p, 16, hipMemcpyDeviceToHost));
+  }
+  if (ms_sort) *ms_sort = ms_s;
+  if (ms_walk) *ms_walk = ms_w;
+  if (sorted) *sorted = pq.issued && pq.sorted ? 1u : 0u;
+  if (queries) *queries = pq.count;
+  if (node_visits) *node_visits = cnt[0];
+  if (prim_tests) *prim_tests = cnt[1];
+  return pq.issued ? query_check_flag(x) : SPTR_OK;
 }
 
 // ---- path-traced radiance for caller-supplied rays ---------------------------------------------------

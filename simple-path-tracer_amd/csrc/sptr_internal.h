@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "adaptive_rule.h"
+#include "closest_point.h"
 #include "dev_owned.h"
 #include "hit_list.h"
 #include "prim_mat_table.h"
@@ -364,6 +365,23 @@ struct RayMultiView {
   const uint32_t* tri_orig;
   const uint32_t* geom_first;
   uint32_t* stack_overflow;
+};
+// One batch of closest-point queries on caller buffers (k_pointquery): device pointers, indexed by point.
+struct PointQueryView {
+  const float4* points;   // n x (p.xyz, max_dist)
+  uint32_t n;
+  const uint32_t* order;  // as RayQueryView's
+  uint32_t* geom;         // n each; may be null (not written)
+  uint32_t* prim;
+  float* dist2;
+  float* dist;
+  float* point;           // n x 3
+  float* uv;              // n x 2
+  float* ng;              // n x 3
+  const uint32_t* tri_orig;
+  const uint32_t* geom_first;
+  uint32_t* stack_overflow;
+  unsigned long long* counters;  // SPTR_POINT_COUNT: {node visits, primitive tests}, added to; else null
 };
 // One call of sptr_render_rays (k_rays_inject, k_rays_gather): device pointers, indexed by ray; its chunks are
 // RayChunks (ray_batch.h).
@@ -763,6 +781,10 @@ void launch_rayquery(const SceneView& sv, const RayQueryView& q, bool anyhit, hi
 // the list capacity instantiated for q.k and the kernel's LDS bytes per block (static + dynamic) are returned
 void launch_rayquery_multi(const SceneView& sv, const RayMultiView& q, hipStream_t s, uint32_t* list_capacity, uint32_t* lds_bytes);
 void launch_ray_keys(const SceneView& sv, const float4* rays, uint32_t n, uint64_t* keys, uint32_t* index, hipStream_t s);
+// kernels_points.h: one batch of closest-point queries (sptr_query_points; the kernel's LDS bytes per block, static +
+// dynamic, are returned), and the sort keys of a batch with the identity indices beside them
+void launch_pointquery(const SceneView& sv, const PointQueryView& q, hipStream_t s, uint32_t* lds_bytes);
+void launch_point_keys(const SceneView& sv, const float4* points, uint32_t n, uint64_t* keys, uint32_t* index, hipStream_t s);
 // kernels_rays.h: one chunk of sptr_render_rays.  The producer writes the chunk's paths into rs[0] / w.segN and
 // returns the segments it published (the nseg of the depth-0 trace); the consumer sums rad[] into the caller's
 // buffer and folds the chunk's per-block tallies into w.tot

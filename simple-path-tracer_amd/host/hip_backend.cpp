@@ -354,6 +354,36 @@ bool HipBackend::queryMultiHit(const float* rays, uint32_t n, uint32_t maxHits, 
   return true;
 }
 
+bool HipBackend::queryPoints(const float* points, uint32_t n, PointBuffers& out) {
+  if (!ctx_ || !built_) {
+    err_ = "HipBackend::queryPoints: build() has not succeeded";
+    return false;
+  }
+  out.geom.assign(n, 0u);
+  out.prim.assign(n, 0u);
+  out.dist2.assign(n, 0.0f);
+  out.dist.assign(n, 0.0f);
+  out.point.assign(size_t(n) * 3, 0.0f);
+  out.uv.assign(size_t(n) * 2, 0.0f);
+  out.ng.assign(size_t(n) * 3, 0.0f);
+  if (n == 0u) return true;
+  sptr_point_query q{};
+  q.points = points;
+  q.n = n;
+  q.geom = out.geom.data();
+  q.prim = out.prim.data();
+  q.dist2 = out.dist2.data();
+  q.dist = out.dist.data();
+  q.point = out.point.data();
+  q.uv = out.uv.data();
+  q.ng = out.ng.data();
+  if (sptr_query_points(ctx_, &q, nullptr) != SPTR_OK) {
+    err_ = std::string("HipBackend::queryPoints: ") + sptr_last_error(ctx_);
+    return false;
+  }
+  return true;
+}
+
 bool HipBackend::renderRays(const float* rays, const uint32_t* seeds, uint32_t n, uint32_t samples, uint32_t frame_index,
                             float* radiance, bool accumulate, bool normalize, RayRenderInfo* info) {
   if (!ctx_ || !built_) {

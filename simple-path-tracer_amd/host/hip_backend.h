@@ -134,6 +134,14 @@ class HipBackend {
     std::vector<float> t, ng, uv;
   };
   bool queryMultiHit(const float* rays, uint32_t n, uint32_t maxHits, MultiHitBuffers& out);
+  // sptr_query_points with host pointers: per point (n x 4 floats: p.xyz, max_dist) the nearest surface point
+  // within max_dist, as include/sptr_hip.h defines it; point and ng hold 3 floats per point, uv 2.  Without a
+  // device, sptr_host_query_points answers the same question over a flat scene.
+  struct PointBuffers {
+    std::vector<uint32_t> geom, prim;
+    std::vector<float> dist2, dist, point, uv, ng;
+  };
+  bool queryPoints(const float* points, uint32_t n, PointBuffers& out);
   // sptr_render_rays with host pointers: the wavefront integrator's radiance along n caller-supplied rays of 8
   // floats (o3, unit d3, two ignored words) against the built scene and the current materials, lights and
   // environment, Settings::max_depth bounces deep.  radiance (n x 3) takes, per ray, the sum of `samples` paths

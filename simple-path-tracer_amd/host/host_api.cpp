@@ -4,7 +4,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <vector>
 
+#include "../csrc/closest_point.h"
 #include "../csrc/tile_map.h"
 #include "scene_desc.h"
 #include "shading.h"
@@ -122,6 +124,108 @@ int sptr_host_load_hdr(const char* path, float** rgb, int32_t* w, int32_t* h) {
   *rgb = p;
   *w = ww;
   *h = hh;
+  return SPTR_OK;
+}
+
+// The host twin of sptr_query_points: csrc/closest_point.h over every primitive.  The triangle records are built
+// with the device's expressions (tri_record, tri_ng3 in csrc/lbvh_shared.h: e1 = v0 - v1, e2 = v2 - v0, the fmaf
+// form of Ng), so a candidate here has the bits of the candidate there.
+int sptr_host_query_points(const sptr_scene* sc, const sptr_point_query* q) {
+  using namespace sptr;
+  if (!sc || !q) return SPTR_ERR_INVALID;
+  if (q->flags & ~uint32_t(SPTR_QUERY_SORT | SPTR_QUERY_NO_SORT)) return SPTR_ERR_INVALID;
+  if ((q->flags & SPTR_QUERY_SORT) && (q->flags & SPTR_QUERY_NO_SORT)) return SPTR_ERR_INVALID;
+  if (q->n > (1u << 28) || (q->n && !q->points)) return SPTR_ERR_INVALID;
+  if (q->reserved[0] || q->reserved[1] || q->reserved[2] || q->reserved[3]) return SPTR_ERR_INVALID;
+  struct Rec {
+    vec3 v0, e1, e2, ng;
+    uint32_t geom, prim;
+    bool live;
+  };
+  std::vector<Rec> recs(sc->num_tris);
+  uint32_t g = 0;
+  for (uint32_t t = 0; t < sc->num_tris; ++t) {
+    while (g + 1 < sc->num_tri_geoms && t >= sc->tri_geom_first[g + 1]) ++g;
+    const uint32_t* ix = sc->indices + size_t(t) * 3;
+    const float *a = sc->positions + size_t(ix[0]) * 3, *b = sc->positions + size_t(ix[1]) * 3,
+                *c = sc->positions + size_t(ix[2]) * 3;
+    Rec& r = recs[t];
+    r.v0 = v3(a[0], a[1], a[2]);
+    r.e1 = r.v0 - v3(b[0], b[1], b[2]);
+    r.e2 = v3(c[0], c[1], c[2]) - r.v0;
+    r.ng = v3(__builtin_fmaf(r.e2.y, r.e1.z, -(r.e2.z * r.e1.y)), __builtin_fmaf(r.e2.z, r.e1.x, -(r.e2.x * r.e1.z)),
+              __builtin_fmaf(r.e2.x, r.e1.y, -(r.e2.y * r.e1.x)));
+    r.geom = g;
+    r.prim = t - (sc->num_tri_geoms ? sc->tri_geom_first[g] : 0u);
+    r.live = cp_triangle_live(r.ng);
+  }
+  const float inf = __builtin_huge_valf();
+  for (uint32_t i = 0; i < q->n; ++i) {
+    const float* pp = q->points + size_t(i) * 4;
+    const vec3 p = v3(pp[0], pp[1], pp[2]);
+    float bd2 = pp[3] * pp[3];
+    uint32_t bg = 0xFFFFFFFFu, bp = 0xFFFFFFFFu;
+    int64_t bt = -1, bs = -1;
+    if (cp_point_valid(p, pp[3])) {
+      for (uint32_t t = 0; t < sc->num_tris; ++t) {
+        const Rec& r = recs[t];
+        if (!r.live) continue;
+        const float d2 = cp_triangle(r.v0, r.e1, r.e2, p).d2;
+        if (d2 <= bd2 && cp_key_less(d2, r.geom, r.prim, bd2, bg, bp)) {
+          bd2 = d2;
+          bg = r.geom;
+          bp = r.prim;
+          bt = t;
+          bs = -1;
+        }
+      }
+      for (uint32_t s = 0; s < sc->num_spheres; ++s) {
+        const float* sp = sc->spheres + size_t(s) * 4;
+        const float d2 = cp_sphere_d2(v3(sp[0], sp[1], sp[2]), sp[3], p);
+        if (d2 <= bd2 && cp_key_less(d2, sc->num_tri_geoms + s, 0u, bd2, bg, bp)) {
+          bd2 = d2;
+          bg = sc->num_tri_geoms + s;
+          bp = 0u;
+          bs = s;
+          bt = -1;
+        }
+      }
+    }
+    vec3 pt = v3(0.0f, 0.0f, 0.0f), ng = pt;
+    float u = 0.0f, v = 0.0f, d2 = inf;
+    if (bt >= 0) {
+      const Rec& r = recs[size_t(bt)];
+      const CpCand c = cp_triangle(r.v0, r.e1, r.e2, p);
+      d2 = c.d2;
+      pt = c.q;
+      u = c.u;
+      v = c.v;
+      ng = r.ng;
+    } else if (bs >= 0) {
+      const float* sp = sc->spheres + size_t(bs) * 4;
+      const CpCand c = cp_sphere(v3(sp[0], sp[1], sp[2]), sp[3], p, ng);
+      d2 = c.d2;
+      pt = c.q;
+    }
+    if (q->geom) q->geom[i] = bg;
+    if (q->prim) q->prim[i] = bp;
+    if (q->dist2) q->dist2[i] = d2;
+    if (q->dist) q->dist[i] = sq_root(d2);
+    if (q->point) {
+      q->point[size_t(i) * 3 + 0] = pt.x;
+      q->point[size_t(i) * 3 + 1] = pt.y;
+      q->point[size_t(i) * 3 + 2] = pt.z;
+    }
+    if (q->uv) {
+      q->uv[size_t(i) * 2 + 0] = u;
+      q->uv[size_t(i) * 2 + 1] = v;
+    }
+    if (q->ng) {
+      q->ng[size_t(i) * 3 + 0] = ng.x;
+      q->ng[size_t(i) * 3 + 1] = ng.y;
+      q->ng[size_t(i) * 3 + 2] = ng.z;
+    }
+  }
   return SPTR_OK;
 }
 

@@ -150,6 +150,16 @@ class MultiHitQuery(C.Structure):
 SPTR_MULTI_HIT_MAX = 16
 
 
+class PointQuery(C.Structure):
+    """sptr_point_query: pointers as addresses (host or device, by SPTR_QUERY_DEVICE_PTRS)."""
+    _fields_ = [("points", C.c_void_p), ("n", C.c_uint32), ("flags", C.c_uint32), ("geom", C.c_void_p),
+                ("prim", C.c_void_p), ("dist2", C.c_void_p), ("dist", C.c_void_p), ("point", C.c_void_p),
+                ("uv", C.c_void_p), ("ng", C.c_void_p), ("reserved", C.c_uint64 * 4)]
+
+
+SPTR_POINT_COUNT = 16
+
+
 class RayRender(C.Structure):
     """sptr_ray_render: pointers as addresses (host or device, by SPTR_RAYS_DEVICE_PTRS)."""
     _fields_ = [("rays", C.c_void_p), ("seeds", C.c_void_p), ("n", C.c_uint32), ("samples", C.c_uint32),
@@ -192,7 +202,8 @@ EXPORTS = [
     "sptr_set_history_motion", "sptr_read_motion", "sptr_motion_info",
     "sptr_set_dynamic", "sptr_update_geometry", "sptr_refit_info",
     "sptr_set_rest_positions", "sptr_update_transforms", "sptr_tree_cost",
-    "sptr_query_rays", "sptr_query_info", "sptr_query_multi_hit", "sptr_multi_hit_info", "sptr_render_rays", "sptr_ray_render_info",
+    "sptr_query_rays", "sptr_query_info", "sptr_query_multi_hit", "sptr_multi_hit_info",
+    "sptr_query_points", "sptr_point_query_info", "sptr_host_query_points", "sptr_render_rays", "sptr_ray_render_info",
     "sptr_render_adaptive", "sptr_read_sample_counts",
     "sptr_host_builtin_scene", "sptr_host_scene_view", "sptr_host_scene_free", "sptr_host_camera_lookat",
     "sptr_host_preset_materials", "sptr_host_default_lights", "sptr_host_equirect_to_faces",
@@ -275,6 +286,10 @@ def lib() -> C.CDLL:
         "sptr_query_info": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), up, up]),
         "sptr_query_multi_hit": (C.c_int, [vp, C.POINTER(MultiHitQuery), vp]),
         "sptr_multi_hit_info": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), up, up, up, up]),
+        "sptr_query_points": (C.c_int, [vp, C.POINTER(PointQuery), vp]),
+        "sptr_point_query_info": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), up, up, C.POINTER(u64),
+                                            C.POINTER(u64)]),
+        "sptr_host_query_points": (C.c_int, [C.POINTER(Scene), C.POINTER(PointQuery)]),
         "sptr_render_rays": (C.c_int, [vp, C.POINTER(RayRender), vp]),
         "sptr_ray_render_info": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(u64), C.POINTER(u64), up]),
         "sptr_render_adaptive": (C.c_int, [vp, C.POINTER(Frame), C.POINTER(AdaptiveParams), C.POINTER(AdaptiveInfo)]),
@@ -359,6 +374,32 @@ def builtin_scene(name: str, p0: int = 0, p1: int = 0) -> FlatScene:
         )
     finally:
         L.sptr_host_scene_free(h)
+
+
+_POINT_FIELDS = (("geom", 1, np.uint32), ("prim", 1, np.uint32), ("dist2", 1, np.float32), ("dist", 1, np.float32),
+                 ("point", 3, np.float32), ("uv", 2, np.float32), ("ng", 3, np.float32))
+
+
+def host_query_points(scene: FlatScene, points, fields=None) -> dict:
+    """sptr_host_query_points: the host twin of Renderer.query_points, brute force over every primitive of a flat
+    scene with the device's arithmetic (csrc/closest_point.h).  points: (n, 4) float32 (p.xyz, max_dist)."""
+    pts = np.ascontiguousarray(points, np.float32).reshape(-1, 4)
+    n = len(pts)
+    known = [f for f, _, _ in _POINT_FIELDS]
+    names = known if fields is None else list(fields)
+    if any(f not in known for f in names):
+        raise SptrError(f"host_query_points: fields must name some of {known} (got {names})")
+    res = {f: np.zeros((n, cols) if cols > 1 else (n,), dt) for f, cols, dt in _POINT_FIELDS if f in names}
+    q = PointQuery()
+    q.points = pts.ctypes.data if n else None
+    q.n = n
+    for name, a in res.items():
+        setattr(q, name, a.ctypes.data if n else None)
+    cs = scene.to_c()
+    rc = lib().sptr_host_query_points(C.byref(cs), C.byref(q))
+    if rc != 0:
+        raise SptrError(f"host_query_points failed ({rc})")
+    return res
 
 
 def camera_lookat(pos=(0.0, 3.0, 8.0), target=(0.0, 1.0, 0.0), fov=60.0, aspect=800 / 600) -> Camera:
@@ -983,6 +1024,86 @@ class Renderer:
                                                 C.byref(lds)), "multi_hit_info")
         return {"ms_sort": s.value, "ms_trace": t.value, "sorted": so.value, "queries": n.value,
                 "list_capacity": cap.value, "lds_bytes": lds.value}
+
+    def query_points(self, points, sort: bool | None = None, fields=None, out: dict | None = None,
+                     stream: int | None = None, count: bool = False) -> dict:
+        """sptr_query_points: per point (p.xyz, max_dist) the nearest surface point within max_dist
+        (include/sptr_hip.h states the definition).  points, sort, out and stream follow query_rays' conventions
+        with n x 4 floats per point.
+
+        The result is a dict with the arrays named by fields (default: all of geom, prim, dist2, dist, point, uv,
+        ng): geom, prim (n, uint32; 0xFFFFFFFF on a miss), dist2, dist (n; +inf on a miss), point (n, 3), uv (n, 2),
+        ng (n, 3).  numpy in, numpy out; device tensors in, torch tensors out.  count=True (SPTR_POINT_COUNT) makes
+        the kernel count node visits and primitive tests for point_query_info()."""
+        device = hasattr(points, "data_ptr")
+        if device:
+            import torch
+
+            if (points.element_size() != 4 or not points.is_floating_point() or not points.is_contiguous()
+                    or points.numel() % 4):
+                raise SptrError("query_points: device points must be a contiguous float32 tensor of n x 4")
+            n = points.numel() // 4
+            tdt = {np.uint32: torch.uint32, np.float32: torch.float32}
+
+            def alloc(cols, dt):
+                return torch.empty((n, cols) if cols > 1 else (n,), dtype=tdt[dt], device=points.device)
+
+            def addr(a):
+                return a.data_ptr()
+
+            def ok(a, cols, dt):
+                return a.is_contiguous() and a.numel() == n * cols and a.dtype == tdt[dt] and a.device == points.device
+        else:
+            if stream is not None:
+                raise SptrError("query_points: a stream needs device tensors")
+            points = np.ascontiguousarray(points, np.float32).reshape(-1, 4)
+            n = len(points)
+
+            def alloc(cols, dt):
+                return np.zeros((n, cols) if cols > 1 else (n,), dt)
+
+            def addr(a):
+                return a.ctypes.data
+
+            def ok(a, cols, dt):
+                return isinstance(a, np.ndarray) and a.flags.c_contiguous and a.size == n * cols and a.dtype == dt
+        known = [f for f, _, _ in _POINT_FIELDS]
+        names = known if fields is None else list(fields)
+        if any(f not in known for f in names):
+            raise SptrError(f"query_points: fields must name some of {known} (got {names})")
+        res = {}
+        for name, cols, dt in _POINT_FIELDS:
+            if name not in names:
+                continue
+            a = (out or {}).get(name)
+            if a is None:
+                a = alloc(cols, dt)
+            elif not ok(a, cols, dt):
+                raise SptrError(f"query_points: out[{name!r}] must be contiguous, of {n} x {cols} {np.dtype(dt).name}")
+            res[name] = a
+        q = PointQuery()
+        q.points = addr(points) if n else None
+        q.n = n
+        q.flags = ((SPTR_QUERY_DEVICE_PTRS if device else 0) | (SPTR_POINT_COUNT if count else 0)
+                   | (0 if sort is None else SPTR_QUERY_SORT if sort else SPTR_QUERY_NO_SORT))
+        for name, a in res.items():  # (an empty tensor has no address: n == 0 writes nothing)
+            setattr(q, name, addr(a) or (C.addressof(self._QUERY_EMPTY) if n == 0 else None))
+        if device and stream is None and n:
+            torch.cuda.current_stream(points.device).synchronize()  # the points' (and the outputs') producers
+        self._check(self._L.sptr_query_points(self._h, C.byref(q), C.c_void_p(stream) if stream else None),
+                    "query_points")
+        return res
+
+    def point_query_info(self) -> dict:
+        """sptr_point_query_info: waits for the last point query; device ms of its sort phase and walk, whether it
+        was sorted, the point queries so far, and the node visits and primitive tests of a count=True query."""
+        s, t = C.c_double(), C.c_double()
+        so, n = C.c_uint32(), C.c_uint32()
+        nv, nt = C.c_uint64(), C.c_uint64()
+        self._check(self._L.sptr_point_query_info(self._h, C.byref(s), C.byref(t), C.byref(so), C.byref(n), C.byref(nv),
+                                                  C.byref(nt)), "point_query_info")
+        return {"ms_sort": s.value, "ms_walk": t.value, "sorted": so.value, "queries": n.value,
+                "node_visits": nv.value, "prim_tests": nt.value}
 
     def render_rays(self, rays, seeds=None, samples: int = 1, frame_index: int = 1, max_depth: int = 6,
                     accumulate: bool = False, normalize: bool = False, out=None, stream: int | None = None):

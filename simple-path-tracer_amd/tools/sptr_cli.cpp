@@ -5,7 +5,7 @@
 //   sptr_cli [--scene default|default_emitter|test_triangle|sphere_mesh:STACKS:SLICES|gltf:PATH]
 //            [--w 800] [--h 600] [--spp 4] [--depth 6] [--env sky|FILE.hdr] [--out image.ppm]
 //            [--warmup N] [--json] [--integrator wavefront|pathtracer|optix] [--spf 4] [--launch-mode 0-3]
-//            [--lagged] [--denoise N] [--history [M]] [--motion] [--orbit DEG] [--animate K [--rebuild] [--rigid]] [--query-centre-rays [--multi-hit K]]
+//            [--lagged] [--denoise N] [--history [M]] [--motion] [--orbit DEG] [--animate K [--rebuild] [--rigid]] [--query-centre-rays [--multi-hit K]] [--query-points-grid N]
 // --spp N renders N progressive frames of 1 spp each (GLRenderer's m_accumulated_samples loop);
 // --warmup N renders N untimed frames first (then restarts the accumulation by a camera change);
 // --json prints one line with per-frame wall-clock statistics (render + RGB8 read back, as the
@@ -39,6 +39,11 @@
 // HipBackend::queryRays; the --json line adds "query": {"rays": n, "hits": h, "tri_hits": k}.
 // --multi-hit K (with --query-centre-rays): the same rays also go through HipBackend::queryMultiHit, and the
 // "query" object gains "multi_hit": {"k": K, "hits": all hits listed, "count_hist": rays that listed 0 .. K hits}.
+// --query-points-grid N: after the render, an N x N x N grid of points goes through HipBackend::queryPoints with
+// max_dist = inf.  The grid covers the flattened scene's bounds (vertices, and spheres as centre +- radius) grown by
+// 10 % about their centre c with half-extent h (double): coordinate i of an axis is float((c - 1.1 h) + (2.2 h) *
+// ((i + 0.5) / N)), x fastest, then y, then z.  The --json line adds "points": {"n", "found", "dist_min",
+// "dist_max", "dist_sum" (double, summed in index order), "geom_hist": points per geomID}.
 // --panorama W H: instead of the frames, an equirectangular panorama of W x H pixels from the camera position
 // through HipBackend::renderRays (sptr_render_rays): row y has polar angle theta = pi (y + 0.5) / H from +Y and
 // column x azimuth phi = 2 pi (x + 0.5) / W, both evaluated in float32 as written (float(pi) times the float
@@ -89,6 +94,7 @@ int main(int argc, char** argv) {
   int w = 800, h = 600, spp = 4, depth = 6, warmup = 0;
   bool json = false, lagged = false, rebuild = false, query_centre = false, motion = false, rigid = false;
   int multi_hit = 0;  // --multi-hit K
+  int points_grid = 0;  // --query-points-grid N
   int pano_w = 0, pano_h = 0;
   bool adaptive = false, spp_given = false;
   double adaptive_thr = 0.0;
@@ -129,6 +135,7 @@ int main(int argc, char** argv) {
     else if (a == "--rigid") rigid = true;
     else if (a == "--query-centre-rays") query_centre = true;
     else if (a == "--multi-hit" && i + 1 < argc) multi_hit = std::atoi(argv[++i]);
+    else if (a == "--query-points-grid" && i + 1 < argc) points_grid = std::atoi(argv[++i]);
     else if (a == "--panorama") {
       pano_w = std::atoi(next());
       pano_h = std::atoi(next());
@@ -138,7 +145,7 @@ int main(int argc, char** argv) {
       }
     }
     else {
-      std::fprintf(stderr, "usage: %s [--scene S] [--w W] [--h H] [--spp N] [--depth D] [--env sky|F.hdr] [--out F] [--warmup N] [--json] [--lagged] [--denoise N] [--history [M]] [--motion] [--orbit DEG] [--animate K [--rebuild] [--rigid]] [--query-centre-rays [--multi-hit K]] [--panorama W H] [--adaptive THR [--min-spp A] [--step K] [--counts F]]\n",
+      std::fprintf(stderr, "usage: %s [--scene S] [--w W] [--h H] [--spp N] [--depth D] [--env sky|F.hdr] [--out F] [--warmup N] [--json] [--lagged] [--denoise N] [--history [M]] [--motion] [--orbit DEG] [--animate K [--rebuild] [--rigid]] [--query-centre-rays [--multi-hit K]] [--query-points-grid N] [--panorama W H] [--adaptive THR [--min-spp A] [--step K] [--counts F]]\n",
                    argv[0]);
       return 2;
     }
@@ -386,6 +393,65 @@ int main(int argc, char** argv) {
       }
     }
   }
+  size_t pg_n = 0, pg_found = 0;
+  double pg_min = 0.0, pg_max = 0.0, pg_sum = 0.0;
+  std::vector<size_t> pg_hist;
+  if (points_grid < 0 || points_grid > 512) {
+    std::fprintf(stderr, "--query-points-grid N needs 1 <= N <= 512\n");
+    return 1;
+  }
+  if (points_grid > 0) {
+    const scene::FlatScene flat = scene::Flatten(sd);
+    const sptr_scene fv = flat.view();
+    double lo[3] = {0.0, 0.0, 0.0}, hi[3] = {0.0, 0.0, 0.0};
+    bool any = false;
+    auto grow = [&](int a, double l, double h2) {
+      lo[a] = any ? std::min(lo[a], l) : l;
+      hi[a] = any ? std::max(hi[a], h2) : h2;
+    };
+    for (uint32_t v = 0; v < fv.num_verts; ++v) {
+      for (int a = 0; a < 3; ++a) grow(a, fv.positions[size_t(v) * 3 + a], fv.positions[size_t(v) * 3 + a]);
+      any = true;
+    }
+    for (uint32_t k = 0; k < fv.num_spheres; ++k) {
+      const float* sp = fv.spheres + size_t(k) * 4;
+      for (int a = 0; a < 3; ++a) grow(a, double(sp[a]) - double(sp[3]), double(sp[a]) + double(sp[3]));
+      any = true;
+    }
+    const int N = points_grid;
+    std::vector<float> pts(size_t(N) * N * N * 4);
+    double c0[3], h0[3];
+    for (int a = 0; a < 3; ++a) {
+      c0[a] = (lo[a] + hi[a]) / 2.0;
+      h0[a] = (hi[a] - lo[a]) / 2.0;
+    }
+    auto coord = [&](int a, int i) { return float((c0[a] - 1.1 * h0[a]) + (2.2 * h0[a]) * ((i + 0.5) / N)); };
+    size_t at = 0;
+    for (int z = 0; z < N; ++z)
+      for (int y = 0; y < N; ++y)
+        for (int x = 0; x < N; ++x) {
+          pts[at++] = coord(0, x);
+          pts[at++] = coord(1, y);
+          pts[at++] = coord(2, z);
+          pts[at++] = std::numeric_limits<float>::infinity();
+        }
+    backends::HipBackend::PointBuffers pb;
+    pg_n = pts.size() / 4;
+    if (!be.queryPoints(pts.data(), uint32_t(pg_n), pb)) {
+      std::fprintf(stderr, "%s\n", be.lastError().c_str());
+      return 1;
+    }
+    pg_hist.assign(size_t(fv.num_tri_geoms) + fv.num_spheres, 0);
+    for (size_t i = 0; i < pg_n; ++i) {
+      if (pb.geom[i] == 0xFFFFFFFFu) continue;
+      const double d = pb.dist[i];
+      pg_min = pg_found ? std::min(pg_min, d) : d;
+      pg_max = pg_found ? std::max(pg_max, d) : d;
+      pg_sum += d;
+      ++pg_found;
+      if (pb.geom[i] < pg_hist.size()) ++pg_hist[pb.geom[i]];
+    }
+  }
   const double ms = tot.ms_total;
   if (json) {
     std::vector<double> s = frame_ms;
@@ -416,6 +482,12 @@ int main(int argc, char** argv) {
         std::printf("]}");
       }
       std::printf("}");
+    }
+    if (points_grid > 0) {
+      std::printf(", \"points\": {\"n\": %zu, \"found\": %zu, \"dist_min\": %.17g, \"dist_max\": %.17g, \"dist_sum\": %.17g, "
+                  "\"geom_hist\": [", pg_n, pg_found, pg_min, pg_max, pg_sum);
+      for (size_t i = 0; i < pg_hist.size(); ++i) std::printf("%s%zu", i ? ", " : "", pg_hist[i]);
+      std::printf("]}");
     }
     std::printf("}\n");
   } else {
