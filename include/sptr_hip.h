@@ -84,7 +84,9 @@ typedef struct sptr_light {
 
 /* EnvironmentManager state: faces == NULL selects the procedural sky
  * (src/EnvironmentManager.cpp:35-61); otherwise 6 cube faces (+X,-X,+Y,-Y,+Z,-Z) of size*size RGB
- * floats, sampled bilinearly as Cubemap::sample (src/Cubemap.cpp:82-180). */
+ * floats, sampled bilinearly as Cubemap::sample (src/Cubemap.cpp:82-180).  2 <= size <= 26754 (the
+ * device indexes texels in 32 bits: 6 * size * size < 2^32); any other size is SPTR_ERR_INVALID,
+ * refused before faces is read. */
 typedef struct sptr_environment {
   const float* faces;
   int32_t size;

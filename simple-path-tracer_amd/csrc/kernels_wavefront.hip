@@ -1673,7 +1673,8 @@ __device__ __forceinline__ vec3 env_color(const EnvView& sh, vec3 dir) {
   const int x0 = (int)floorf(fx_), y0 = (int)floorf(fy_);
   const int x1 = min(x0 + 1, S - 1), y1 = min(y0 + 1, S - 1);
   const float fx = fx_ - float(x0), fy = fy_ - float(y0);
-  // texel (face, x, y) = env[(face * S + y) * S + x]; 24-bit multiplies (S <= 4096)
+  // texel (face, x, y) = env[(face * S + y) * S + x]; 24-bit multiplies with a 32-bit product: 6 * S * S < 2^32,
+  // S <= kMaxEnvSize = 26 754 (sptr_set_environment refuses larger faces)
   const uint32_t r0 = __umul24((uint32_t)(face * S + y0), (uint32_t)S), r1 = __umul24((uint32_t)(face * S + y1), (uint32_t)S);
   const float4 t00 = sh.env[r0 + (uint32_t)x0], t10 = sh.env[r0 + (uint32_t)x1];
   const float4 t01 = sh.env[r1 + (uint32_t)x0], t11 = sh.env[r1 + (uint32_t)x1];

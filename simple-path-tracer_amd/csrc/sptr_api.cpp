@@ -1917,6 +1917,8 @@ static int set_environment_one(sptr_ctx* x, const sptr_environment* e) {
     return SPTR_OK;
   }
   if (e->size < 2) return fail(c, SPTR_ERR_INVALID, "environment face size must be >= 2");
+  // env_color indexes texels in 32 bits (24-bit row multiplies): 6 * S * S must stay below 2^32
+  if (e->size > kMaxEnvSize) return fail(c, SPTR_ERR_INVALID, "environment face size must be <= 26754");
   const size_t texels = (size_t)6 * e->size * e->size;
   std::vector<float> tmp(texels * 4);
   for (size_t i = 0; i < texels; ++i) {

@@ -130,6 +130,8 @@ struct SceneView {
   uint64_t scene_bytes;  // traversed nodes + triangles + spheres + refs
 };
 
+// Largest cubemap face size: env_color's texel index (face * S + y) * S + x is 32-bit, so 6 * S * S < 2^32
+constexpr int32_t kMaxEnvSize = 26754;
 struct EnvView {
   const float4* env;  // 6*S*S texels (rgb, -) or null for the procedural sky
   int32_t env_size;
