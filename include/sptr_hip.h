@@ -771,6 +771,71 @@ int sptr_point_query_info(sptr_ctx* ctx, double* ms_sort, double* ms_walk, uint3
  * expressions the device uses.  It is the CPU fallback of HipBackend::queryPoints and the tests' yardstick. */
 int sptr_host_query_points(const sptr_scene* scene, const sptr_point_query* query);
 
+/* ---- signed distance queries (symbols added within ABI 9: no existing struct or entry point changed) -------
+ * sptr_query_points with a sign: positive on the side the normals point to, negative on the other, decided by
+ * the angle-weighted pseudonormal of the closest feature (Baerentzen & Aanaes).
+ * csrc/pseudonormal.h is the normative text; in words:
+ *
+ * Tables.  A triangle is live if its stored Ng is not exactly zero; others take no part.  Its unit normal n is
+ * Ng scaled by its largest absolute component and then normalised (contributes nothing if not finite).  Corners
+ * of live triangles of one geometry whose positions compare equal as floats (-0 == +0, NaN equals nothing) are
+ * one welded vertex; geometries never weld with each other.  N_v of a welded vertex: the float32 sum, in
+ * ascending corner index 3t + k, of angle_c * n_t (the triangle's angle at that corner, pn_angle).  N_e of an
+ * unordered pair of distinct welded vertices: the float32 sum, in ascending (t, k), of n_t over the live
+ * triangles with that pair as edge k (edge 0 = v0v1, 1 = v0v2, 2 = v1v2).  An edge is open with exactly one
+ * incidence and irregular unless it has exactly two that traverse it in opposite directions.
+ *
+ * Result of point i: the winner, dist and point q of sptr_query_points, unchanged.  feature says where q lies on
+ * the winner: 0 face, 1 / 2 / 3 edge v0v1 / v0v2 / v1v2, 4 / 5 / 6 vertex v0 / v1 / v2, 7 a sphere, 0xFFFFFFFF a
+ * miss.  normal = N: the stored Ng, N_e or N_v accordingly.  s = ((p-q).x N.x + (p-q).y N.y) + (p-q).z N.z;
+ * signed_dist = -dist if s < 0, else +dist (0 and NaN count as positive); SPTR_SIGNED_FLIP_TRIANGLES negates the
+ * sign of triangle results (for meshes whose stored normals point inward, such as the built-in cube and sphere
+ * mesh).  A sphere: negative iff |p - c| < r, normal = ng; the flip flag does not apply.  A miss: +inf, 0.
+ * The sign is relative to the geometry that owns the nearest surface point: for disjoint closed solids that is
+ * the sign of their union; for intersecting solids it is not.  Open meshes and cracks between vertices that are
+ * not bit-equal give the sign of the nearest feature's pseudonormal, whatever that means there.
+ *
+ * sptr_set_signed_distance(ctx, 1) makes the next sptr_upload_scene keep the triangles' corner positions and
+ * build the tables on the device at its end; sptr_update_geometry and sptr_update_transforms rebuild them
+ * (welding included) before they return.  Without it an upload allocates, launches and keeps what it did
+ * before.  A scene with triangles but no triangle geometry builds no tables.
+ *
+ * sptr_query_signed_distance runs the point query of `q` (same kernels, same outputs) and one sign pass after
+ * it on the same stream.  q.flags: those of sptr_query_points plus SPTR_SIGNED_FLIP_TRIANGLES.  Every rule of
+ * sptr_query_points holds: pointers, streams, sorting, n == 0, refused calls, lane contexts, alignment (the
+ * three new outputs are 4-byte aligned device pointers, each may be NULL).  SPTR_ERR_INVALID also when the scene
+ * was uploaded without sptr_set_signed_distance(1). */
+enum { SPTR_SIGNED_FLIP_TRIANGLES = 32u };
+enum { SPTR_FEATURE_FACE = 0, SPTR_FEATURE_EDGE = 1, SPTR_FEATURE_VERTEX = 4, SPTR_FEATURE_SPHERE = 7 };
+typedef struct sptr_signed_query {
+  sptr_point_query q;
+  float* signed_dist;    /* n */
+  float* normal;         /* n x 3, N, unnormalised */
+  uint32_t* feature;     /* n */
+  uint64_t reserved[4];  /* 0 */
+} sptr_signed_query;
+typedef struct sptr_signed_info_t {
+  uint64_t welded_vertices, edges, open_edges, irregular_edges;
+  uint64_t table_bytes;  /* N_v and N_e per triangle corner and edge (72 B per triangle) and the kept corners (36 B) */
+  uint32_t builds;       /* since the context was created */
+  uint32_t valid;        /* the current scene has tables */
+  uint32_t num_tris;     /* triangles the tables cover (0 without tables) */
+  uint32_t pad;
+  double ms_build;       /* device ms of the last build */
+  double ms_sign;        /* device ms of the last sign pass (waits for it) */
+} sptr_signed_info_t;
+int sptr_set_signed_distance(sptr_ctx* ctx, uint32_t on);
+int sptr_query_signed_distance(sptr_ctx* ctx, const sptr_signed_query* query, void* stream);
+int sptr_signed_info(sptr_ctx* ctx, sptr_signed_info_t* out);
+/* N_v and N_e per uploaded triangle, num_tris x 3 x 3 floats each (corner k, edge k; 0 for a triangle that is not
+ * live), to host memory.  Either pointer may be NULL. */
+int sptr_read_pseudonormals(sptr_ctx* ctx, float* nv, float* ne);
+/* The host twins: the same tables with a stable sort and the same sums in the same order, and the query by
+ * brute force (sptr_host_query_points, then the sign); csrc/pseudonormal.h on both sides, so the device's bits.
+ * counts: welded vertices, edges, open edges, irregular edges; any pointer may be NULL. */
+int sptr_host_pseudonormals(const sptr_scene* scene, float* nv, float* ne, uint64_t counts[4]);
+int sptr_host_query_signed_distance(const sptr_scene* scene, const sptr_signed_query* query);
+
 /* ---- path-traced radiance for caller-supplied rays (symbols added within ABI 9: no existing struct or
  *      entry point changed) ------------------------------------------------------------------------------
  * sptr_render renders through the reference's pinhole camera and sptr_query_rays answers what a ray hits; this

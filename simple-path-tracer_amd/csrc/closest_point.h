@@ -94,6 +94,51 @@ SPTR_HD CpCand cp_triangle(vec3 v0, vec3 e1, vec3 e2, vec3 p) {
   }
   return best;
 }
+// Which candidate won (sptr_query_signed_distance, pseudonormal.h): 0 = the face candidate, whatever its weights;
+// 1, 2, 3 = edge ab, ac, bc, an edge candidate with 0 < t < 1; 4, 5, 6 = vertex a, b, c, an edge candidate with
+// t == 0 or t == 1 (ab: 0 -> a, 1 -> b; ac: 0 -> a, 1 -> c; bc: 0 -> b, 1 -> c); 7 = a sphere; kCpMiss = none.
+constexpr uint32_t kCpFace = 0u, kCpEdge = 1u, kCpVertex = 4u, kCpSphere = 7u, kCpMiss = 0xFFFFFFFFu;
+SPTR_HD uint32_t cp_edge_feature(uint32_t edge, uint32_t lo, uint32_t hi, float t) {
+  return t == 0.0f ? kCpVertex + lo : (t == 1.0f ? kCpVertex + hi : kCpEdge + edge);
+}
+// cp_triangle's candidate, bit for bit (the same expressions in the same order), and its feature code
+SPTR_HD CpCand cp_triangle_feature(vec3 v0, vec3 e1, vec3 e2, vec3 p, uint32_t& feature) {
+  const vec3 ab = -e1, ac = e2, bc = ac - ab, ap = p - v0, bp = ap - ab;
+  const float aa = dot(ab, ab), apab = dot(ap, ab);
+  const float t0 = cp_clamp01(apab, aa);
+  CpCand best = cp_at(p, v0, ab, ac, t0, 0.0f);
+  feature = cp_edge_feature(0u, 0u, 1u, t0);
+  {
+    const float t = cp_clamp01(dot(ap, ac), dot(ac, ac));
+    const CpCand c = cp_at(p, v0, ab, ac, 0.0f, t);
+    if (c.d2 < best.d2) {
+      best = c;
+      feature = cp_edge_feature(1u, 0u, 2u, t);
+    }
+  }
+  {
+    const float t = cp_clamp01(dot(bp, bc), dot(bc, bc));
+    const CpCand c = cp_at(p, v0, ab, ac, 1.0f - t, t);
+    if (c.d2 < best.d2) {
+      best = c;
+      feature = cp_edge_feature(2u, 1u, 2u, t);
+    }
+  }
+  {
+    const float alpha = dot(ab, ac) / aa;
+    const vec3 ep = ac - ab * alpha;
+    const float w = dot(ap, ep) / dot(ep, ep);
+    const float s = apab / aa - alpha * w;
+    if (s >= 0.0f && w >= 0.0f && s + w <= 1.0f) {
+      const CpCand c = cp_at(p, v0, ab, ac, s, w);
+      if (c.d2 < best.d2) {
+        best = c;
+        feature = kCpFace;
+      }
+    }
+  }
+  return best;
+}
 // a triangle whose stored normal is exactly zero is one the build leaves out of the tree: no candidate
 SPTR_HD bool cp_triangle_live(vec3 ng) { return !(ng.x == 0.0f && ng.y == 0.0f && ng.z == 0.0f); }
 

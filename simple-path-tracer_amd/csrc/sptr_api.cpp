@@ -122,6 +122,13 @@ struct sptr_ctx {
     bool issued = false, sorted = false, counted = false;
     uint32_t count = 0, lds_bytes = 0;
   } pq;
+  // sptr_query_signed_distance: the point query's ids when the caller takes none (scratch that grows on demand) and
+  // the events around the last sign pass, which may still run on a caller's stream
+  struct SignedQuery {
+    sptr::DevBuf geom, prim;
+    sptr::DevEvent ev[2];
+    bool issued = false;
+  } sq;
   // sptr_render_rays (the caller's context; a pixel lane holds none): the call's own totals block (WaveView::tot
   // of its launches, so that the render totals never see them), the carried sum of a ray whose sample range is
   // split, the staging of host-pointer calls, and the events of the last call: begin and end on the context's
@@ -160,6 +167,7 @@ struct sptr_ctx {
     if (rq.issued) (void)hipEventSynchronize(rq.ev[2]);
     if (mh.issued) (void)hipEventSynchronize(mh.ev[2]);
     if (pq.issued) (void)hipEventSynchronize(pq.ev[2]);
+    if (sq.issued) (void)hipEventSynchronize(sq.ev[1]);
     if (reg_ptr) (void)hipHostUnregister(reg_ptr);
     delete lane;
   }
@@ -1826,6 +1834,15 @@ static int upload_scene_one(sptr_ctx* x, const sptr_scene* s) {
   const int rc = build_lbvh(c, s->positions, s->num_verts, s->indices, s->num_tris, s->spheres, s->num_spheres, tg.data(),
                             s->num_tri_geoms);
   if (rc != SPTR_OK) return rc;
+  // sptr_set_signed_distance: the pseudonormal tables of this upload (the caller's context only; a scene whose
+  // triangles belong to no geometry has none).  Off: nothing is allocated, launched or kept.
+  if (c.signed_on && !x->is_lane && !(s->num_tris && !s->num_tri_geoms)) {
+    const int rs = signed_build_upload(c, s->positions, s->num_verts, s->indices, s->num_tris, s->spheres, s->num_spheres,
+                                       tg.data(), s->num_tri_geoms);
+    if (rs != SPTR_OK) return rs;
+  } else if (c.sg.valid || c.sg.cpos.p) {
+    signed_release(c);
+  }
   c.have_scene = true;
   ++c.epoch;
   ++c.geom_rev;
@@ -2363,6 +2380,7 @@ static int query_wait(sptr_ctx* x) {
   if (x->rq.issued) API_HIP(hipEventSynchronize(x->rq.ev[2]));
   if (x->mh.issued) API_HIP(hipEventSynchronize(x->mh.ev[2]));
   if (x->pq.issued) API_HIP(hipEventSynchronize(x->pq.ev[2]));
+  if (x->sq.issued) API_HIP(hipEventSynchronize(x->sq.ev[1]));
   return SPTR_OK;
 }
 
@@ -2824,6 +2842,181 @@ int sptr_point_query_info(sptr_ctx* x, double* ms_sort, double* ms_walk, uint32_
   if (node_visits) *node_visits = cnt[0];
   if (prim_tests) *prim_tests = cnt[1];
   return pq.issued ? query_check_flag(x) : SPTR_OK;
+}
+
+// ---- signed distance queries ----------------------------------------------------------------------------
+int sptr_set_signed_distance(sptr_ctx* x, uint32_t on) {
+  if (!x) return SPTR_ERR_INVALID;
+  if (x->is_lane) return fail(x->c, SPTR_ERR_INVALID, "set_signed_distance: not on a lane context");
+  x->c.signed_on = on != 0u;  // read by the next upload
+  return SPTR_OK;
+}
+
+// One validated batch with device pointers, enqueued on s: the point query as it is, then the sign pass.
+static int enqueue_signed(sptr_ctx* x, const sptr_signed_query& q, hipStream_t s) {
+  Context& c = x->c;
+  auto& sq = x->sq;
+  const SignedState& g = c.sg;
+  sptr_point_query d = q.q;
+  d.flags &= ~(uint32_t)SPTR_SIGNED_FLIP_TRIANGLES;
+  for (DevEvent& e : sq.ev)
+    if (!e) API_HIP(hipEventCreate(e.put()));
+  if (!d.geom || !d.prim) {  // the ids go into scratch
+    const size_t nb = (size_t)d.n * 4;
+    if (sq.geom.bytes < nb || sq.prim.bytes < nb) {
+      const int rw = query_wait(x);  // an enqueued query may still use the old scratch
+      if (rw != SPTR_OK) return rw;
+      API_HIP(sq.geom.ensure(nb));
+      API_HIP(sq.prim.ensure(nb));
+    }
+    if (!d.geom) d.geom = static_cast<uint32_t*>(sq.geom.p);
+    if (!d.prim) d.prim = static_cast<uint32_t*>(sq.prim.p);
+  }
+  const int rc = enqueue_points(x, d, s);
+  if (rc != SPTR_OK) return rc;
+  PointSignView v{};
+  v.points = reinterpret_cast<const float4*>(d.points);
+  v.n = d.n;
+  v.geom = d.geom;
+  v.prim = d.prim;
+  v.signed_dist = q.signed_dist;
+  v.normal = q.normal;
+  v.feature = q.feature;
+  v.flip = (q.q.flags & SPTR_SIGNED_FLIP_TRIANGLES) ? 1u : 0u;
+  v.geom_first = static_cast<const uint32_t*>(x->geom_first.p);
+  v.cpos = static_cast<const float*>(g.cpos.p);
+  v.nv = static_cast<const float*>(g.nv.p);
+  v.ne = static_cast<const float*>(g.ne.p);
+  v.sph = static_cast<const float4*>(g.sph.p);
+  v.num_tris = g.num_tris;
+  v.num_sph = g.num_sph;
+  v.num_tri_geoms = g.num_tri_geoms;
+  API_HIP(hipEventRecord(sq.ev[0], s));
+  launch_point_sign(v, s);
+  API_HIP(hipGetLastError());
+  API_HIP(hipEventRecord(sq.ev[1], s));
+  sq.issued = true;
+  return SPTR_OK;
+}
+
+int sptr_query_signed_distance(sptr_ctx* x, const sptr_signed_query* sq_in, void* stream) {
+  if (!x || !sq_in) return SPTR_ERR_INVALID;
+  Context& c = x->c;
+  const sptr_point_query* q = &sq_in->q;
+  if (x->is_lane) return fail(c, SPTR_ERR_INVALID, "query_signed_distance: not on a lane context");
+  const bool dev = (q->flags & SPTR_QUERY_DEVICE_PTRS) != 0u;
+  if (q->flags & ~(kPointFlags | (uint32_t)SPTR_SIGNED_FLIP_TRIANGLES))
+    return fail(c, SPTR_ERR_INVALID, "query_signed_distance: SPTR_QUERY_ANY_HIT or unknown flags");
+  if ((q->flags & SPTR_QUERY_SORT) && (q->flags & SPTR_QUERY_NO_SORT))
+    return fail(c, SPTR_ERR_INVALID, "query_signed_distance: SPTR_QUERY_SORT and SPTR_QUERY_NO_SORT exclude each other");
+  if (q->n > kQueryMaxRays) return fail(c, SPTR_ERR_INVALID, "query_signed_distance: more than 2^28 points");
+  if (q->n && !q->points) return fail(c, SPTR_ERR_INVALID, "query_signed_distance: no points");
+  if (q->reserved[0] || q->reserved[1] || q->reserved[2] || q->reserved[3] || sq_in->reserved[0] || sq_in->reserved[1] ||
+      sq_in->reserved[2] || sq_in->reserved[3])
+    return fail(c, SPTR_ERR_INVALID, "query_signed_distance: reserved must be 0");
+  if (!dev && stream)
+    return fail(c, SPTR_ERR_INVALID, "query_signed_distance: host pointers cannot be enqueued on a stream");
+  if (dev && ((reinterpret_cast<uintptr_t>(q->points) & 15u) || (reinterpret_cast<uintptr_t>(q->geom) & 3u) ||
+              (reinterpret_cast<uintptr_t>(q->prim) & 3u) || (reinterpret_cast<uintptr_t>(q->dist2) & 3u) ||
+              (reinterpret_cast<uintptr_t>(q->dist) & 3u) || (reinterpret_cast<uintptr_t>(q->point) & 3u) ||
+              (reinterpret_cast<uintptr_t>(q->uv) & 3u) || (reinterpret_cast<uintptr_t>(q->ng) & 3u) ||
+              (reinterpret_cast<uintptr_t>(sq_in->signed_dist) & 3u) || (reinterpret_cast<uintptr_t>(sq_in->normal) & 3u) ||
+              (reinterpret_cast<uintptr_t>(sq_in->feature) & 3u)))
+    return fail(c, SPTR_ERR_INVALID,
+                "query_signed_distance: the device point buffer must be 16-byte aligned, the outputs 4-byte aligned");
+  if (!c.have_scene) return fail(c, SPTR_ERR_NO_SCENE, "query_signed_distance: no scene");
+  if (!c.sg.valid)
+    return fail(c, SPTR_ERR_INVALID, "query_signed_distance: the scene was not uploaded with sptr_set_signed_distance(1)");
+  if (q->n == 0u) return SPTR_OK;
+  API_HIP(hipSetDevice(c.device));
+  if (stream) return enqueue_signed(x, *sq_in, static_cast<hipStream_t>(stream));  // only enqueues
+  if (sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;
+  const int rw = query_wait(x);
+  if (rw != SPTR_OK) return rw;
+  sptr_signed_query d = *sq_in;
+  const size_t n = q->n;
+  // host pointers: points in, then the point query's outputs and signed_dist | normal | feature out, staged
+  const size_t off_prim = n * 4, off_d2 = off_prim + n * 4, off_d = off_d2 + n * 4, off_pt = off_d + n * 4,
+               off_uv = off_pt + n * 12, off_ng = off_uv + n * 8, off_sd = off_ng + n * 12, off_nn = off_sd + n * 4,
+               off_ft = off_nn + n * 12, total = off_ft + n * 4;
+  if (!dev) {
+    auto& rq = x->rq;
+    API_HIP(rq.stage_in.ensure(n * 16));
+    API_HIP(rq.stage_out.ensure(total));
+    API_HIP(hipMemcpy(rq.stage_in.p, q->points, n * 16, hipMemcpyHostToDevice));
+    char* o = static_cast<char*>(rq.stage_out.p);
+    d.q.points = static_cast<const float*>(rq.stage_in.p);
+    d.q.geom = reinterpret_cast<uint32_t*>(o);  // (the sign pass reads the ids whether or not the caller takes them)
+    d.q.prim = reinterpret_cast<uint32_t*>(o + off_prim);
+    d.q.dist2 = q->dist2 ? reinterpret_cast<float*>(o + off_d2) : nullptr;
+    d.q.dist = q->dist ? reinterpret_cast<float*>(o + off_d) : nullptr;
+    d.q.point = q->point ? reinterpret_cast<float*>(o + off_pt) : nullptr;
+    d.q.uv = q->uv ? reinterpret_cast<float*>(o + off_uv) : nullptr;
+    d.q.ng = q->ng ? reinterpret_cast<float*>(o + off_ng) : nullptr;
+    d.signed_dist = sq_in->signed_dist ? reinterpret_cast<float*>(o + off_sd) : nullptr;
+    d.normal = sq_in->normal ? reinterpret_cast<float*>(o + off_nn) : nullptr;
+    d.feature = sq_in->feature ? reinterpret_cast<uint32_t*>(o + off_ft) : nullptr;
+  }
+  const int rc = enqueue_signed(x, d, c.stream);
+  if (rc != SPTR_OK) return rc;
+  API_HIP(hipStreamSynchronize(c.stream));
+  const int rf = query_check_flag(x);
+  if (rf != SPTR_OK) return rf;
+  if (!dev) {
+    if (q->geom) API_HIP(hipMemcpy(q->geom, d.q.geom, n * 4, hipMemcpyDeviceToHost));
+    if (q->prim) API_HIP(hipMemcpy(q->prim, d.q.prim, n * 4, hipMemcpyDeviceToHost));
+    if (q->dist2) API_HIP(hipMemcpy(q->dist2, d.q.dist2, n * 4, hipMemcpyDeviceToHost));
+    if (q->dist) API_HIP(hipMemcpy(q->dist, d.q.dist, n * 4, hipMemcpyDeviceToHost));
+    if (q->point) API_HIP(hipMemcpy(q->point, d.q.point, n * 12, hipMemcpyDeviceToHost));
+    if (q->uv) API_HIP(hipMemcpy(q->uv, d.q.uv, n * 8, hipMemcpyDeviceToHost));
+    if (q->ng) API_HIP(hipMemcpy(q->ng, d.q.ng, n * 12, hipMemcpyDeviceToHost));
+    if (sq_in->signed_dist) API_HIP(hipMemcpy(sq_in->signed_dist, d.signed_dist, n * 4, hipMemcpyDeviceToHost));
+    if (sq_in->normal) API_HIP(hipMemcpy(sq_in->normal, d.normal, n * 12, hipMemcpyDeviceToHost));
+    if (sq_in->feature) API_HIP(hipMemcpy(sq_in->feature, d.feature, n * 4, hipMemcpyDeviceToHost));
+  }
+  return SPTR_OK;
+}
+
+int sptr_signed_info(sptr_ctx* x, sptr_signed_info_t* out) {
+  if (!x) return SPTR_ERR_INVALID;
+  Context& c = x->c;
+  const SignedState& g = c.sg;
+  double ms_sign = 0.0;
+  if (x->sq.issued) {
+    API_HIP(hipSetDevice(c.device));
+    API_HIP(hipEventSynchronize(x->sq.ev[1]));
+    float ms = 0.0f;
+    API_HIP(hipEventElapsedTime(&ms, x->sq.ev[0], x->sq.ev[1]));
+    ms_sign = ms;
+  }
+  if (out) {
+    out->welded_vertices = g.valid ? g.counts_h[0] : 0u;
+    out->edges = g.valid ? g.counts_h[1] : 0u;
+    out->open_edges = g.valid ? g.counts_h[2] : 0u;
+    out->irregular_edges = g.valid ? g.counts_h[3] : 0u;
+    out->table_bytes = g.valid ? (uint64_t)g.num_tris * (72u + 36u) : 0u;
+    out->builds = g.builds;
+    out->valid = g.valid ? 1u : 0u;
+    out->num_tris = g.valid ? g.num_tris : 0u;
+    out->pad = 0u;
+    out->ms_build = g.ms_build;
+    out->ms_sign = ms_sign;
+  }
+  return SPTR_OK;
+}
+
+int sptr_read_pseudonormals(sptr_ctx* x, float* nv, float* ne) {
+  if (!x) return SPTR_ERR_INVALID;
+  Context& c = x->c;
+  if (!c.have_scene) return fail(c, SPTR_ERR_NO_SCENE, "read_pseudonormals: no scene");
+  if (!c.sg.valid)
+    return fail(c, SPTR_ERR_INVALID, "read_pseudonormals: the scene was not uploaded with sptr_set_signed_distance(1)");
+  API_HIP(hipSetDevice(c.device));
+  const size_t nb = (size_t)c.sg.num_tris * 36;
+  if (nb == 0) return SPTR_OK;
+  if (nv) API_HIP(hipMemcpy(nv, c.sg.nv.p, nb, hipMemcpyDeviceToHost));
+  if (ne) API_HIP(hipMemcpy(ne, c.sg.ne.p, nb, hipMemcpyDeviceToHost));
+  return SPTR_OK;
 }
 
 // ---- path-traced radiance for caller-supplied rays ---------------------------------------------------
@@ -3449,6 +3642,10 @@ static int refit_scene(sptr_ctx* x, const char* who, const float* d_pos, const f
   const int rc = refit_one(c, d_pos, d_sph, d_xf);  // (returns after c.stream drained: the staging is stable)
   ++d.geom_gen;
   if (rc != SPTR_OK) return rc;
+  if (c.sg.valid) {  // sptr_set_signed_distance: the tables of the moved corners, welding included
+    const int rs = signed_rebuild(c, d_pos, d_xf, reinterpret_cast<const float4*>(d_sph));
+    if (rs != SPTR_OK) return rs;
+  }
   if (d.motion_on)  // the history outlives the refit: its passes follow the epoch, and differ by generation
     for (sptr_ctx::Denoise::Pass* p : {&d.last, &d.carry})
       if (p->valid && p->epoch == epoch_before) p->epoch = c.epoch;

@@ -24,6 +24,7 @@
 #include "dev_owned.h"
 #include "hit_list.h"
 #include "prim_mat_table.h"
+#include "pseudonormal.h"
 #include "ray_batch.h"
 #include "shadow_entry.h"
 #include "sptr_hip.h"
@@ -517,6 +518,23 @@ struct RefitState {
   double cost_upload = 0.0, area_upload = 0.0;
 };
 
+// What an upload after sptr_set_signed_distance(1) keeps for sptr_query_signed_distance (kernels_signed.hip,
+// DESIGN.md par. 6m).  All arrays are in uploaded order: triangle t, corner 3t + k, edge slot 3t + k.
+struct SignedState {
+  bool valid = false;        // the current scene has tables
+  uint32_t num_tris = 0, num_sph = 0, num_tri_geoms = 0;
+  // kept: the corners' world positions (36 B per triangle: what the tables were built from and what the sign pass
+  // rebuilds a record from), the index triples and geomIDs (the next rebuild's inputs), the spheres as uploaded
+  DevBuf cpos, idx, tri_geom, sph;
+  DevBuf nv, ne;             // the table: N_v per corner, N_e per edge slot, 3 floats each (72 B per triangle)
+  // the build's scratch, kept for the next rebuild
+  DevBuf pos, contrib, nhat, live, key_a, key_b, key_s, val0, val1, val2, head, wofs, wid, temp, counts;
+  DevEvent ev[2];            // the last build
+  uint64_t counts_h[4] = {0, 0, 0, 0};  // welded vertices, edges, open edges, irregular edges
+  uint32_t builds = 0;
+  double ms_build = 0.0;
+};
+
 struct Context {
   int device = 0;
   // (the streams come first: members are destroyed in reverse order, so everything below goes before them)
@@ -598,6 +616,8 @@ struct Context {
   bool dynamic = false;  // sptr_set_dynamic: the next upload keeps RefitState
   bool dynamic_xf = false;  // ... its SPTR_DYNAMIC_TRANSFORMS bit: and the rest pose, and records its tree cost
   RefitState rf;
+  bool signed_on = false;  // sptr_set_signed_distance: the next upload builds SignedState's tables
+  SignedState sg;
   // shading state
   std::vector<DevMaterial> mats_host;
   DevBuf mats;
@@ -668,6 +688,32 @@ int refit_tree_cost(Context& c, double* cost, double* root_area);
 // before refit_lbvh overwrites them); returns when done
 int refit_snapshot(Context& c);
 void refit_release(Context& c);  // the buffers; the events stay for the next dynamic upload
+
+// kernels_signed.hip.  signed_build_upload: the upload's part (host arrays in, tables out).  signed_rebuild: new
+// device coordinates (d_pos null: the kept corners; with d_xf, d_pos is the rest pose and each triangle takes its
+// geometry's matrix, as refit_lbvh) and new spheres in upload order (or null).  Both run on c.stream and return
+// when done.  launch_point_sign: the sign pass of one batch (k_point_sign).
+int signed_build_upload(Context& c, const float* h_pos, uint32_t nverts, const uint32_t* h_idx, uint32_t ntris,
+                        const float* h_sph, uint32_t nsph, const uint32_t* h_tri_geom, uint32_t num_tri_geoms);
+int signed_rebuild(Context& c, const float* d_pos, const float* d_xf, const float4* d_sph);
+void signed_release(Context& c);
+struct PointSignView {
+  const float4* points;   // n x (p.xyz, max_dist)
+  uint32_t n;
+  const uint32_t* geom;   // the point query's ids
+  const uint32_t* prim;
+  float* signed_dist;     // outputs; each may be null (not written)
+  float* normal;          // n x 3
+  uint32_t* feature;
+  uint32_t flip;
+  const uint32_t* geom_first;
+  const float* cpos;
+  const float* nv;
+  const float* ne;
+  const float4* sph;
+  uint32_t num_tris, num_sph, num_tri_geoms;
+};
+void launch_point_sign(const PointSignView& v, hipStream_t s);
 
 // kernels_sort.hip: the build's device primitives (temp == nullptr: set temp_bytes only)
 hipError_t scan_u32(void* temp, size_t& temp_bytes, const uint32_t* in, uint32_t* out, uint32_t n, hipStream_t s);

@@ -62,6 +62,7 @@ bool HipBackend::buildFlat(const scene::FlatScene& flat) {
   const uint32_t dyn = settings_.transforms ? uint32_t(SPTR_DYNAMIC_REFIT | SPTR_DYNAMIC_TRANSFORMS)
                                             : (settings_.dynamic ? uint32_t(SPTR_DYNAMIC_REFIT) : 0u);
   if (sptr_set_dynamic(ctx_, dyn) != SPTR_OK) return false;
+  if (sptr_set_signed_distance(ctx_, settings_.signed_distance ? 1u : 0u) != SPTR_OK) return false;
   const int rc = sptr_upload_scene(ctx_, &v);
   if (rc != SPTR_OK) {
     err_ = std::string("HipBackend::build: ") + sptr_last_error(ctx_);
@@ -381,6 +382,48 @@ bool HipBackend::queryPoints(const float* points, uint32_t n, PointBuffers& out)
     err_ = std::string("HipBackend::queryPoints: ") + sptr_last_error(ctx_);
     return false;
   }
+  return true;
+}
+
+bool HipBackend::querySignedDistance(const float* points, uint32_t n, bool flipTriangles, SignedBuffers& out) {
+  if (!ctx_ || !built_) {
+    err_ = "HipBackend::querySignedDistance: build() has not succeeded";
+    return false;
+  }
+  PointBuffers& pb = out.points;
+  pb.geom.assign(n, 0u);
+  pb.prim.assign(n, 0u);
+  pb.dist2.assign(n, 0.0f);
+  pb.dist.assign(n, 0.0f);
+  pb.point.assign(size_t(n) * 3, 0.0f);
+  pb.uv.assign(size_t(n) * 2, 0.0f);
+  pb.ng.assign(size_t(n) * 3, 0.0f);
+  out.signed_dist.assign(n, 0.0f);
+  out.normal.assign(size_t(n) * 3, 0.0f);
+  out.feature.assign(n, 0u);
+  sptr_signed_query q{};
+  q.q.points = points;
+  q.q.n = n;
+  q.q.flags = flipTriangles ? uint32_t(SPTR_SIGNED_FLIP_TRIANGLES) : 0u;
+  q.q.geom = pb.geom.data();
+  q.q.prim = pb.prim.data();
+  q.q.dist2 = pb.dist2.data();
+  q.q.dist = pb.dist.data();
+  q.q.point = pb.point.data();
+  q.q.uv = pb.uv.data();
+  q.q.ng = pb.ng.data();
+  q.signed_dist = out.signed_dist.data();
+  q.normal = out.normal.data();
+  q.feature = out.feature.data();
+  sptr_signed_info_t info{};
+  if (sptr_query_signed_distance(ctx_, &q, nullptr) != SPTR_OK || sptr_signed_info(ctx_, &info) != SPTR_OK) {
+    err_ = std::string("HipBackend::querySignedDistance: ") + sptr_last_error(ctx_);
+    return false;
+  }
+  out.counts[0] = info.welded_vertices;
+  out.counts[1] = info.edges;
+  out.counts[2] = info.open_edges;
+  out.counts[3] = info.irregular_edges;
   return true;
 }
 

@@ -55,6 +55,9 @@ class HipBackend {
     // sets the meshes' object-space vertices as the device's rest pose, and update() sends only the instances'
     // matrices (and the spheres) when nothing else changed
     bool transforms = false;
+    // sptr_set_signed_distance, applied before build(): the build keeps the triangles' corners and builds the
+    // pseudonormal tables querySignedDistance() needs; update() rebuilds them
+    bool signed_distance = false;
   };
   static constexpr uint32_t kLaggedCollect = 32;
   static constexpr uint32_t kDefaultMaxHistory = 4;  // lowest last-frame RMSE of the caps tried
@@ -142,6 +145,18 @@ class HipBackend {
     std::vector<float> dist2, dist, point, uv, ng;
   };
   bool queryPoints(const float* points, uint32_t n, PointBuffers& out);
+  // sptr_query_signed_distance with host pointers (Settings::signed_distance at build()): queryPoints' outputs and,
+  // per point, the signed distance (positive on the side the normals point to; flipTriangles negates triangle
+  // results, for meshes wound like the built-in ones), the pseudonormal N (x 3) and the feature code.  counts: the
+  // tables' welded vertices, edges, open and irregular edges.  Without a device, sptr_host_query_signed_distance
+  // answers the same question over a flat scene.
+  struct SignedBuffers {
+    PointBuffers points;
+    std::vector<float> signed_dist, normal;
+    std::vector<uint32_t> feature;
+    uint64_t counts[4] = {0, 0, 0, 0};
+  };
+  bool querySignedDistance(const float* points, uint32_t n, bool flipTriangles, SignedBuffers& out);
   // sptr_render_rays with host pointers: the wavefront integrator's radiance along n caller-supplied rays of 8
   // floats (o3, unit d3, two ignored words) against the built scene and the current materials, lights and
   // environment, Settings::max_depth bounces deep.  radiance (n x 3) takes, per ray, the sum of `samples` paths

@@ -1,12 +1,14 @@
 // host_api.cpp — C ABI access to the host-side scene layer (sptr_host_* in include/sptr_hip.h), so
 // foreign callers (ctypes harness, CLI) build scenes, cameras and material tables with exactly the
 // C++ code the HipBackend uses.
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "../csrc/closest_point.h"
+#include "../csrc/pseudonormal.h"
 #include "../csrc/tile_map.h"
 #include "scene_desc.h"
 #include "shading.h"
@@ -225,6 +227,169 @@ int sptr_host_query_points(const sptr_scene* sc, const sptr_point_query* q) {
       q->ng[size_t(i) * 3 + 1] = ng.y;
       q->ng[size_t(i) * 3 + 2] = ng.z;
     }
+  }
+  return SPTR_OK;
+}
+
+// The host twin of the device's table build (kernels_signed.hip): csrc/pseudonormal.h's arithmetic, a stable sort
+// where the device runs its stable radix sort, and every sum in the same order.
+namespace {
+struct PnTables {
+  std::vector<float> pos;  // 9 per triangle: the corners
+  std::vector<float> nv, ne;  // 9 per triangle each
+  uint64_t counts[4] = {0, 0, 0, 0};
+};
+sptr::vec3 pn_corner(const PnTables& t, size_t c) { return sptr::v3(t.pos[3 * c], t.pos[3 * c + 1], t.pos[3 * c + 2]); }
+
+void pn_build(const sptr_scene* sc, PnTables& T) {
+  using namespace sptr;
+  const size_t nt = sc->num_tris, nc = nt * 3;
+  T.pos.assign(nc * 3, 0.0f);
+  T.nv.assign(nc * 3, 0.0f);
+  T.ne.assign(nc * 3, 0.0f);
+  std::vector<uint32_t> geom(nt, 0u);
+  std::vector<uint8_t> live(nt, 0);
+  std::vector<vec3> nhat(nt), contrib(nc);
+  uint32_t g = 0;
+  for (size_t t = 0; t < nt; ++t) {
+    while (g + 1 < sc->num_tri_geoms && t >= sc->tri_geom_first[g + 1]) ++g;
+    geom[t] = g;
+    for (int k = 0; k < 3; ++k)
+      for (int a = 0; a < 3; ++a) T.pos[(3 * t + k) * 3 + a] = sc->positions[size_t(sc->indices[3 * t + k]) * 3 + a];
+    const vec3 v0 = pn_corner(T, 3 * t), v1 = pn_corner(T, 3 * t + 1), v2 = pn_corner(T, 3 * t + 2);
+    const vec3 ng = pn_tri_ng(v0, v1, v2);
+    live[t] = cp_triangle_live(ng);
+    if (!live[t]) continue;
+    nhat[t] = pn_unit_normal(ng);
+    for (uint32_t k = 0; k < 3; ++k) contrib[3 * t + k] = nhat[t] * pn_corner_angle(v0, v1, v2, k);
+  }
+  // welding: live corners by (geom, x, y, z) keys, stable, then runs of equal positions
+  std::vector<uint32_t> order;
+  for (size_t c = 0; c < nc; ++c)
+    if (live[c / 3]) order.push_back(uint32_t(c));
+  auto key = [&](uint32_t c, uint64_t& hi, uint64_t& lo) {
+    hi = (uint64_t(geom[c / 3]) << 32) | pn_pos_bits(T.pos[3 * size_t(c)]);
+    lo = (uint64_t(pn_pos_bits(T.pos[3 * size_t(c) + 1])) << 32) | pn_pos_bits(T.pos[3 * size_t(c) + 2]);
+  };
+  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+    uint64_t ah, al, bh, bl;
+    key(a, ah, al);
+    key(b, bh, bl);
+    return ah < bh || (ah == bh && al < bl);
+  });
+  std::vector<uint32_t> wid(nc, 0xFFFFFFFFu);
+  uint32_t nw = 0;
+  for (size_t j = 0; j < order.size();) {
+    size_t e = j + 1;
+    while (e < order.size() && geom[order[e] / 3] == geom[order[e - 1] / 3] &&
+           pn_same_pos(pn_corner(T, order[e]), pn_corner(T, order[e - 1])))
+      ++e;
+    vec3 sum = v3(0.0f, 0.0f, 0.0f);
+    for (size_t i = j; i < e; ++i)
+      if (pn_finite3(nhat[order[i] / 3])) sum = sum + contrib[order[i]];
+    for (size_t i = j; i < e; ++i) {
+      wid[order[i]] = nw;
+      T.nv[3 * size_t(order[i])] = sum.x;
+      T.nv[3 * size_t(order[i]) + 1] = sum.y;
+      T.nv[3 * size_t(order[i]) + 2] = sum.z;
+    }
+    ++nw;
+    j = e;
+  }
+  T.counts[0] = nw;
+  // edges: slots 3t + k by the pair of welded ids, stable
+  std::vector<uint32_t> eorder;
+  std::vector<uint64_t> ekey(nc, kPnDeadKey);
+  for (size_t t = 0; t < nt; ++t)
+    if (live[t])
+      for (uint32_t k = 0; k < 3; ++k) {
+        ekey[3 * t + k] = pn_edge_key(wid[3 * t + pn_edge_lo(k)], wid[3 * t + pn_edge_hi(k)]);
+        if (ekey[3 * t + k] != kPnDeadKey) eorder.push_back(uint32_t(3 * t + k));
+      }
+  std::stable_sort(eorder.begin(), eorder.end(), [&](uint32_t a, uint32_t b) { return ekey[a] < ekey[b]; });
+  for (size_t j = 0; j < eorder.size();) {
+    size_t e = j + 1;
+    while (e < eorder.size() && ekey[eorder[e]] == ekey[eorder[j]]) ++e;
+    vec3 sum = v3(0.0f, 0.0f, 0.0f);
+    uint32_t fwd = 0, bwd = 0;
+    for (size_t i = j; i < e; ++i) {
+      const uint32_t s = eorder[i], t = s / 3, k = s % 3;
+      if (pn_finite3(nhat[t])) sum = sum + nhat[t];
+      if (pn_edge_forward(k, wid[3 * t + pn_edge_lo(k)], wid[3 * t + pn_edge_hi(k)])) ++fwd;
+      else ++bwd;
+    }
+    for (size_t i = j; i < e; ++i) {
+      T.ne[3 * size_t(eorder[i])] = sum.x;
+      T.ne[3 * size_t(eorder[i]) + 1] = sum.y;
+      T.ne[3 * size_t(eorder[i]) + 2] = sum.z;
+    }
+    ++T.counts[1];
+    if (e - j == 1) ++T.counts[2];
+    if (!(fwd == 1 && bwd == 1)) ++T.counts[3];
+    j = e;
+  }
+}
+}  // namespace
+
+int sptr_host_pseudonormals(const sptr_scene* sc, float* nv, float* ne, uint64_t counts[4]) {
+  if (!sc || (sc->num_tris && (!sc->indices || !sc->positions))) return SPTR_ERR_INVALID;
+  if (sc->num_tris && sc->num_tri_geoms && !sc->tri_geom_first) return SPTR_ERR_INVALID;
+  PnTables T;
+  pn_build(sc, T);
+  if (nv && !T.nv.empty()) std::memcpy(nv, T.nv.data(), T.nv.size() * 4);
+  if (ne && !T.ne.empty()) std::memcpy(ne, T.ne.data(), T.ne.size() * 4);
+  if (counts)
+    for (int i = 0; i < 4; ++i) counts[i] = T.counts[i];
+  return SPTR_OK;
+}
+
+// sptr_host_query_points, then the sign of each winner from the tables (pn_triangle_result, pn_sphere_result).
+int sptr_host_query_signed_distance(const sptr_scene* sc, const sptr_signed_query* q) {
+  using namespace sptr;
+  if (!sc || !q) return SPTR_ERR_INVALID;
+  if (q->reserved[0] || q->reserved[1] || q->reserved[2] || q->reserved[3]) return SPTR_ERR_INVALID;
+  if (q->q.flags & ~uint32_t(SPTR_QUERY_SORT | SPTR_QUERY_NO_SORT | SPTR_SIGNED_FLIP_TRIANGLES)) return SPTR_ERR_INVALID;
+  if (sc->num_tris && !sc->num_tri_geoms) return SPTR_ERR_INVALID;  // (no tables for triangles without a geometry)
+  const bool flip = (q->q.flags & SPTR_SIGNED_FLIP_TRIANGLES) != 0u;
+  sptr_point_query pq = q->q;
+  pq.flags &= ~uint32_t(SPTR_SIGNED_FLIP_TRIANGLES);
+  std::vector<uint32_t> geom, prim;
+  if (!pq.geom) {
+    geom.resize(pq.n ? pq.n : 1u);
+    pq.geom = geom.data();
+  }
+  if (!pq.prim) {
+    prim.resize(pq.n ? pq.n : 1u);
+    pq.prim = prim.data();
+  }
+  const int rc = sptr_host_query_points(sc, &pq);
+  if (rc != SPTR_OK) return rc;
+  PnTables T;
+  pn_build(sc, T);
+  const float inf = __builtin_huge_valf();
+  for (uint32_t i = 0; i < pq.n; ++i) {
+    const float* pp = pq.points + size_t(i) * 4;
+    const vec3 p = v3(pp[0], pp[1], pp[2]);
+    const uint32_t g = pq.geom[i];
+    float sd = inf;
+    vec3 n = v3(0.0f, 0.0f, 0.0f);
+    uint32_t f = kCpMiss;
+    if (g != 0xFFFFFFFFu && g < sc->num_tri_geoms) {
+      const size_t t = size_t(sc->tri_geom_first[g]) + pq.prim[i];
+      sd = pn_triangle_result(pn_corner(T, 3 * t), pn_corner(T, 3 * t + 1), pn_corner(T, 3 * t + 2), &T.nv[9 * t], &T.ne[9 * t], p,
+                              flip, n, f);
+    } else if (g != 0xFFFFFFFFu) {
+      const float* sp = sc->spheres + size_t(g - sc->num_tri_geoms) * 4;
+      sd = pn_sphere_result(v3(sp[0], sp[1], sp[2]), sp[3], p, n);
+      f = kCpSphere;
+    }
+    if (q->signed_dist) q->signed_dist[i] = sd;
+    if (q->normal) {
+      q->normal[size_t(i) * 3 + 0] = n.x;
+      q->normal[size_t(i) * 3 + 1] = n.y;
+      q->normal[size_t(i) * 3 + 2] = n.z;
+    }
+    if (q->feature) q->feature[i] = f;
   }
   return SPTR_OK;
 }

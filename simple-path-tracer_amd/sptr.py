@@ -157,7 +157,22 @@ class PointQuery(C.Structure):
                 ("uv", C.c_void_p), ("ng", C.c_void_p), ("reserved", C.c_uint64 * 4)]
 
 
+class SignedQuery(C.Structure):
+    """sptr_signed_query: a PointQuery and the three outputs of the sign pass."""
+    _fields_ = [("q", PointQuery), ("signed_dist", C.c_void_p), ("normal", C.c_void_p), ("feature", C.c_void_p),
+                ("reserved", C.c_uint64 * 4)]
+
+
+class SignedInfo(C.Structure):
+    """sptr_signed_info_t"""
+    _fields_ = [("welded_vertices", C.c_uint64), ("edges", C.c_uint64), ("open_edges", C.c_uint64),
+                ("irregular_edges", C.c_uint64), ("table_bytes", C.c_uint64), ("builds", C.c_uint32),
+                ("valid", C.c_uint32), ("num_tris", C.c_uint32), ("pad", C.c_uint32), ("ms_build", C.c_double),
+                ("ms_sign", C.c_double)]
+
+
 SPTR_POINT_COUNT = 16
+SPTR_SIGNED_FLIP_TRIANGLES = 32
 
 
 class RayRender(C.Structure):
@@ -204,6 +219,8 @@ EXPORTS = [
     "sptr_set_rest_positions", "sptr_update_transforms", "sptr_tree_cost",
     "sptr_query_rays", "sptr_query_info", "sptr_query_multi_hit", "sptr_multi_hit_info",
     "sptr_query_points", "sptr_point_query_info", "sptr_host_query_points", "sptr_render_rays", "sptr_ray_render_info",
+    "sptr_set_signed_distance", "sptr_query_signed_distance", "sptr_signed_info", "sptr_read_pseudonormals",
+    "sptr_host_pseudonormals", "sptr_host_query_signed_distance",
     "sptr_render_adaptive", "sptr_read_sample_counts",
     "sptr_host_builtin_scene", "sptr_host_scene_view", "sptr_host_scene_free", "sptr_host_camera_lookat",
     "sptr_host_preset_materials", "sptr_host_default_lights", "sptr_host_equirect_to_faces",
@@ -290,6 +307,12 @@ def lib() -> C.CDLL:
         "sptr_point_query_info": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), up, up, C.POINTER(u64),
                                             C.POINTER(u64)]),
         "sptr_host_query_points": (C.c_int, [C.POINTER(Scene), C.POINTER(PointQuery)]),
+        "sptr_set_signed_distance": (C.c_int, [vp, u32]),
+        "sptr_query_signed_distance": (C.c_int, [vp, C.POINTER(SignedQuery), vp]),
+        "sptr_signed_info": (C.c_int, [vp, C.POINTER(SignedInfo)]),
+        "sptr_read_pseudonormals": (C.c_int, [vp, fp, fp]),
+        "sptr_host_pseudonormals": (C.c_int, [C.POINTER(Scene), fp, fp, C.POINTER(u64)]),
+        "sptr_host_query_signed_distance": (C.c_int, [C.POINTER(Scene), C.POINTER(SignedQuery)]),
         "sptr_render_rays": (C.c_int, [vp, C.POINTER(RayRender), vp]),
         "sptr_ray_render_info": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(u64), C.POINTER(u64), up]),
         "sptr_render_adaptive": (C.c_int, [vp, C.POINTER(Frame), C.POINTER(AdaptiveParams), C.POINTER(AdaptiveInfo)]),
@@ -399,6 +422,54 @@ def host_query_points(scene: FlatScene, points, fields=None) -> dict:
     rc = lib().sptr_host_query_points(C.byref(cs), C.byref(q))
     if rc != 0:
         raise SptrError(f"host_query_points failed ({rc})")
+    return res
+
+
+_SIGNED_FIELDS = (("signed_dist", 1, np.float32), ("normal", 3, np.float32), ("feature", 1, np.uint32))
+_SIGNED_COUNTS = ("welded_vertices", "edges", "open_edges", "irregular_edges")
+
+
+def _signed_query_set(q: SignedQuery, name: str, value) -> None:
+    setattr(q if name in [f for f, _, _ in _SIGNED_FIELDS] else q.q, name, value)
+
+
+def host_pseudonormals(scene: FlatScene) -> dict:
+    """sptr_host_pseudonormals: the host twin of the device's table build (csrc/pseudonormal.h): nv, ne as
+    (num_tris, 3, 3) float32 (corner k, edge k of each uploaded triangle) and the four counts."""
+    cs = scene.to_c()
+    nt = int(cs.num_tris)
+    nv, ne = np.zeros((nt, 3, 3), np.float32), np.zeros((nt, 3, 3), np.float32)
+    cnt = (C.c_uint64 * 4)()
+    fp = C.POINTER(C.c_float)
+    rc = lib().sptr_host_pseudonormals(C.byref(cs), nv.ctypes.data_as(fp), ne.ctypes.data_as(fp), cnt)
+    if rc != 0:
+        raise SptrError(f"host_pseudonormals failed ({rc})")
+    res = {"nv": nv, "ne": ne}
+    res.update({k: int(cnt[i]) for i, k in enumerate(_SIGNED_COUNTS)})
+    return res
+
+
+def host_query_signed_distance(scene: FlatScene, points, fields=None, flip_triangles: bool = False) -> dict:
+    """sptr_host_query_signed_distance: the host twin of Renderer.query_signed_distance: host_query_points' fields
+    and signed_dist (n), normal (n, 3), feature (n, uint32)."""
+    pts = np.ascontiguousarray(points, np.float32).reshape(-1, 4)
+    n = len(pts)
+    table = _POINT_FIELDS + _SIGNED_FIELDS
+    known = [f for f, _, _ in table]
+    names = known if fields is None else list(fields)
+    if any(f not in known for f in names):
+        raise SptrError(f"host_query_signed_distance: fields must name some of {known} (got {names})")
+    res = {f: np.zeros((n, cols) if cols > 1 else (n,), dt) for f, cols, dt in table if f in names}
+    q = SignedQuery()
+    q.q.points = pts.ctypes.data if n else None
+    q.q.n = n
+    q.q.flags = SPTR_SIGNED_FLIP_TRIANGLES if flip_triangles else 0
+    for name, a in res.items():
+        _signed_query_set(q, name, a.ctypes.data if n else None)
+    cs = scene.to_c()
+    rc = lib().sptr_host_query_signed_distance(C.byref(cs), C.byref(q))
+    if rc != 0:
+        raise SptrError(f"host_query_signed_distance failed ({rc})")
     return res
 
 
@@ -1093,6 +1164,98 @@ class Renderer:
         self._check(self._L.sptr_query_points(self._h, C.byref(q), C.c_void_p(stream) if stream else None),
                     "query_points")
         return res
+
+    def set_signed_distance(self, on: bool = True) -> None:
+        """sptr_set_signed_distance: the next upload keeps the triangles' corners and builds the pseudonormal tables
+        query_signed_distance needs; update_geometry and update_transforms rebuild them."""
+        self._check(self._L.sptr_set_signed_distance(self._h, 1 if on else 0), "set_signed_distance")
+
+    def query_signed_distance(self, points, sort: bool | None = None, fields=None, out: dict | None = None,
+                              stream: int | None = None, count: bool = False, flip_triangles: bool = False) -> dict:
+        """sptr_query_signed_distance: query_points (same conventions, same fields) and, per point, signed_dist (n;
+        negative on the side the normals point away from, +inf on a miss), normal (n, 3: the pseudonormal N of the
+        closest feature, unnormalised) and feature (n, uint32: 0 face, 1-3 edge, 4-6 vertex, 7 sphere, 0xFFFFFFFF
+        miss).  flip_triangles (SPTR_SIGNED_FLIP_TRIANGLES) negates the sign of triangle results, for meshes whose
+        stored normals point inward.  The scene must have been uploaded after set_signed_distance()."""
+        device = hasattr(points, "data_ptr")
+        if device:
+            import torch
+
+            if (points.element_size() != 4 or not points.is_floating_point() or not points.is_contiguous()
+                    or points.numel() % 4):
+                raise SptrError("query_signed_distance: device points must be a contiguous float32 tensor of n x 4")
+            n = points.numel() // 4
+            tdt = {np.uint32: torch.uint32, np.float32: torch.float32}
+
+            def alloc(cols, dt):
+                return torch.empty((n, cols) if cols > 1 else (n,), dtype=tdt[dt], device=points.device)
+
+            def addr(a):
+                return a.data_ptr()
+
+            def ok(a, cols, dt):
+                return a.is_contiguous() and a.numel() == n * cols and a.dtype == tdt[dt] and a.device == points.device
+        else:
+            if stream is not None:
+                raise SptrError("query_signed_distance: a stream needs device tensors")
+            points = np.ascontiguousarray(points, np.float32).reshape(-1, 4)
+            n = len(points)
+
+            def alloc(cols, dt):
+                return np.zeros((n, cols) if cols > 1 else (n,), dt)
+
+            def addr(a):
+                return a.ctypes.data
+
+            def ok(a, cols, dt):
+                return isinstance(a, np.ndarray) and a.flags.c_contiguous and a.size == n * cols and a.dtype == dt
+        table = _POINT_FIELDS + _SIGNED_FIELDS
+        known = [f for f, _, _ in table]
+        names = known if fields is None else list(fields)
+        if any(f not in known for f in names):
+            raise SptrError(f"query_signed_distance: fields must name some of {known} (got {names})")
+        res = {}
+        for name, cols, dt in table:
+            if name not in names:
+                continue
+            a = (out or {}).get(name)
+            if a is None:
+                a = alloc(cols, dt)
+            elif not ok(a, cols, dt):
+                raise SptrError(f"query_signed_distance: out[{name!r}] must be contiguous, of {n} x {cols} "
+                                f"{np.dtype(dt).name}")
+            res[name] = a
+        q = SignedQuery()
+        q.q.points = addr(points) if n else None
+        q.q.n = n
+        q.q.flags = ((SPTR_QUERY_DEVICE_PTRS if device else 0) | (SPTR_POINT_COUNT if count else 0)
+                     | (SPTR_SIGNED_FLIP_TRIANGLES if flip_triangles else 0)
+                     | (0 if sort is None else SPTR_QUERY_SORT if sort else SPTR_QUERY_NO_SORT))
+        for name, a in res.items():  # (an empty tensor has no address: n == 0 writes nothing)
+            _signed_query_set(q, name, addr(a) or (C.addressof(self._QUERY_EMPTY) if n == 0 else None))
+        if device and stream is None and n:
+            torch.cuda.current_stream(points.device).synchronize()  # the points' (and the outputs') producers
+        self._check(self._L.sptr_query_signed_distance(self._h, C.byref(q), C.c_void_p(stream) if stream else None),
+                    "query_signed_distance")
+        return res
+
+    def signed_info(self) -> dict:
+        """sptr_signed_info: the table's counts (welded vertices, edges, open and irregular edges), its bytes, the
+        builds so far, whether the current scene has tables, and the device ms of the last build and of the last
+        sign pass (waits for it)."""
+        s = SignedInfo()
+        self._check(self._L.sptr_signed_info(self._h, C.byref(s)), "signed_info")
+        return {k: getattr(s, k) for k, _ in SignedInfo._fields_ if k != "pad"}
+
+    def read_pseudonormals(self) -> dict:
+        """sptr_read_pseudonormals: N_v and N_e of the uploaded scene's triangles, (num_tris, 3, 3) float32 each
+        (corner k, edge k)."""
+        num_tris = self.signed_info()["num_tris"]
+        nv, ne = np.zeros((num_tris, 3, 3), np.float32), np.zeros((num_tris, 3, 3), np.float32)
+        fp = C.POINTER(C.c_float)
+        self._check(self._L.sptr_read_pseudonormals(self._h, nv.ctypes.data_as(fp), ne.ctypes.data_as(fp)),
+                    "read_pseudonormals")
+        return {"nv": nv, "ne": ne}
 
     def point_query_info(self) -> dict:
         """sptr_point_query_info: waits for the last point query; device ms of its sort phase and walk, whether it

@@ -39,6 +39,9 @@
 // HipBackend::queryRays; the --json line adds "query": {"rays": n, "hits": h, "tri_hits": k}.
 // --multi-hit K (with --query-centre-rays): the same rays also go through HipBackend::queryMultiHit, and the
 // "query" object gains "multi_hit": {"k": K, "hits": all hits listed, "count_hist": rays that listed 0 .. K hits}.
+// --query-points-grid N --signed [--flip]: the grid goes through HipBackend::querySignedDistance instead (the scene is
+// built with Settings::signed_distance) and the counts of negative, positive and missed points and the tables' welded
+// vertex, edge, open and irregular edge counts are printed too.
 // --query-points-grid N: after the render, an N x N x N grid of points goes through HipBackend::queryPoints with
 // max_dist = inf.  The grid covers the flattened scene's bounds (vertices, and spheres as centre +- radius) grown by
 // 10 % about their centre c with half-extent h (double): coordinate i of an axis is float((c - 1.1 h) + (2.2 h) *
@@ -95,6 +98,7 @@ int main(int argc, char** argv) {
   bool json = false, lagged = false, rebuild = false, query_centre = false, motion = false, rigid = false;
   int multi_hit = 0;  // --multi-hit K
   int points_grid = 0;  // --query-points-grid N
+  bool pg_signed = false, pg_flip = false;  // --signed [--flip]
   int pano_w = 0, pano_h = 0;
   bool adaptive = false, spp_given = false;
   double adaptive_thr = 0.0;
@@ -136,6 +140,8 @@ int main(int argc, char** argv) {
     else if (a == "--query-centre-rays") query_centre = true;
     else if (a == "--multi-hit" && i + 1 < argc) multi_hit = std::atoi(argv[++i]);
     else if (a == "--query-points-grid" && i + 1 < argc) points_grid = std::atoi(argv[++i]);
+    else if (a == "--signed") pg_signed = true;
+    else if (a == "--flip") pg_flip = true;
     else if (a == "--panorama") {
       pano_w = std::atoi(next());
       pano_h = std::atoi(next());
@@ -145,7 +151,7 @@ int main(int argc, char** argv) {
       }
     }
     else {
-      std::fprintf(stderr, "usage: %s [--scene S] [--w W] [--h H] [--spp N] [--depth D] [--env sky|F.hdr] [--out F] [--warmup N] [--json] [--lagged] [--denoise N] [--history [M]] [--motion] [--orbit DEG] [--animate K [--rebuild] [--rigid]] [--query-centre-rays [--multi-hit K]] [--query-points-grid N] [--panorama W H] [--adaptive THR [--min-spp A] [--step K] [--counts F]]\n",
+      std::fprintf(stderr, "usage: %s [--scene S] [--w W] [--h H] [--spp N] [--depth D] [--env sky|F.hdr] [--out F] [--warmup N] [--json] [--lagged] [--denoise N] [--history [M]] [--motion] [--orbit DEG] [--animate K [--rebuild] [--rigid]] [--query-centre-rays [--multi-hit K]] [--query-points-grid N [--signed [--flip]]] [--panorama W H] [--adaptive THR [--min-spp A] [--step K] [--counts F]]\n",
                    argv[0]);
       return 2;
     }
@@ -184,6 +190,7 @@ int main(int argc, char** argv) {
   st.motion = motion;
   st.dynamic = animate > 0 && !rebuild;
   st.transforms = st.dynamic && rigid;
+  st.signed_distance = pg_signed;
   be.setSettings(st);
   if (!be.build(sd)) {
     std::fprintf(stderr, "%s\n", be.lastError().c_str());
@@ -396,6 +403,8 @@ int main(int argc, char** argv) {
   size_t pg_n = 0, pg_found = 0;
   double pg_min = 0.0, pg_max = 0.0, pg_sum = 0.0;
   std::vector<size_t> pg_hist;
+  size_t sg_neg = 0, sg_pos = 0, sg_miss = 0;
+  uint64_t sg_counts[4] = {0, 0, 0, 0};
   if (points_grid < 0 || points_grid > 512) {
     std::fprintf(stderr, "--query-points-grid N needs 1 <= N <= 512\n");
     return 1;
@@ -435,11 +444,20 @@ int main(int argc, char** argv) {
           pts[at++] = coord(2, z);
           pts[at++] = std::numeric_limits<float>::infinity();
         }
-    backends::HipBackend::PointBuffers pb;
+    backends::HipBackend::SignedBuffers sb;
+    backends::HipBackend::PointBuffers& pb = sb.points;
     pg_n = pts.size() / 4;
-    if (!be.queryPoints(pts.data(), uint32_t(pg_n), pb)) {
+    if (!(pg_signed ? be.querySignedDistance(pts.data(), uint32_t(pg_n), pg_flip, sb) : be.queryPoints(pts.data(), uint32_t(pg_n), pb))) {
       std::fprintf(stderr, "%s\n", be.lastError().c_str());
       return 1;
+    }
+    if (pg_signed) {
+      for (size_t i = 0; i < pg_n; ++i) {
+        if (sb.feature[i] == 0xFFFFFFFFu) ++sg_miss;
+        else if (std::signbit(sb.signed_dist[i])) ++sg_neg;
+        else ++sg_pos;
+      }
+      for (int i = 0; i < 4; ++i) sg_counts[i] = sb.counts[i];
     }
     pg_hist.assign(size_t(fv.num_tri_geoms) + fv.num_spheres, 0);
     for (size_t i = 0; i < pg_n; ++i) {
@@ -488,6 +506,11 @@ int main(int argc, char** argv) {
                   "\"geom_hist\": [", pg_n, pg_found, pg_min, pg_max, pg_sum);
       for (size_t i = 0; i < pg_hist.size(); ++i) std::printf("%s%zu", i ? ", " : "", pg_hist[i]);
       std::printf("]}");
+      if (pg_signed)
+        std::printf(", \"signed\": {\"flip\": %d, \"negative\": %zu, \"positive\": %zu, \"missed\": %zu, \"welded_vertices\": %llu, "
+                    "\"edges\": %llu, \"open_edges\": %llu, \"irregular_edges\": %llu}",
+                    pg_flip ? 1 : 0, sg_neg, sg_pos, sg_miss, (unsigned long long)sg_counts[0], (unsigned long long)sg_counts[1],
+                    (unsigned long long)sg_counts[2], (unsigned long long)sg_counts[3]);
     }
     std::printf("}\n");
   } else {
