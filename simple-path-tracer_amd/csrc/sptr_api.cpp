@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 
+#include "query_stage.h"
 #include "sptr_internal.h"
 
 #include <dlfcn.h>
@@ -97,38 +98,49 @@ struct sptr_ctx {
     bool aov_uv = false;
     bool motion_used = false;  // the last pass with history on took the motion path
   } dn;
-  // sptr_query_rays (the caller's context; a pixel lane holds none): scratch that grows on demand (sort keys
-  // and identity indices, their sorted copies, the radix sort's temporaries, the stack-overflow flag, the
-  // staging of host-pointer queries) and the events of the last query, which may still run on a caller's stream
-  struct RayQuery {
-    sptr::DevBuf keys, index, keys_sorted, order, temp, flag, stage_in, stage_out;
-    sptr::DevEvent ev[3];                            // begin, after the sort, end
-    bool issued = false;                             // ev[0] and ev[2] (sorted: ev[1] too) are recorded
+  // What every query kind keeps of its last run, which may still be running on a caller's stream
+  struct QueryRun {
+    sptr::DevEvent ev[3];  // begin, after the sort, end
+    bool issued = false;   // ev[0] and ev[2] (sorted: ev[1] too) are recorded
     bool sorted = false;
     uint32_t count = 0;
+  };
+  // sptr_query_rays (the caller's context; a pixel lane holds none): scratch that grows on demand (sort keys
+  // and identity indices, their sorted copies, the radix sort's temporaries, the stack-overflow flag, the
+  // staging of host-pointer queries), shared by every kind so that consecutive enqueued queries share a stream
+  struct RayQuery {
+    sptr::DevBuf keys, index, keys_sorted, order, temp, flag, stage_in, stage_out;
+    QueryRun run;
   } rq;
-  // sptr_query_multi_hit: it shares rq's scratch (so consecutive enqueued queries of either kind share a stream)
-  // and keeps the events and the facts of its own last query for sptr_multi_hit_info
+  // sptr_query_multi_hit: the facts of its last query for sptr_multi_hit_info
   struct MultiHit {
-    sptr::DevEvent ev[3];  // begin, after the sort, end
-    bool issued = false, sorted = false;
-    uint32_t count = 0, list_capacity = 0, lds_bytes = 0;
+    QueryRun run;
+    uint32_t list_capacity = 0, lds_bytes = 0;
   } mh;
-  // sptr_query_points: shares rq's scratch like mh; its own events and facts for sptr_point_query_info, and the two
-  // 64-bit counters of a SPTR_POINT_COUNT query (allocated by the first such query)
+  // sptr_query_points: the facts of its last query for sptr_point_query_info, and the two 64-bit counters of a
+  // SPTR_POINT_COUNT query (allocated by the first such query)
   struct PointQuery {
-    sptr::DevEvent ev[3];  // begin, after the sort, end
+    QueryRun run;
     sptr::DevBuf counters;
-    bool issued = false, sorted = false, counted = false;
-    uint32_t count = 0, lds_bytes = 0;
+    bool counted = false;
+    uint32_t lds_bytes = 0;
   } pq;
   // sptr_query_signed_distance: the point query's ids when the caller takes none (scratch that grows on demand) and
-  // the events around the last sign pass, which may still run on a caller's stream
+  // the run of the last sign pass (never sorted: ev[0] and ev[2])
   struct SignedQuery {
     sptr::DevBuf geom, prim;
-    sptr::DevEvent ev[2];
-    bool issued = false;
+    QueryRun run;
   } sq;
+  // Waits for the last query of every kind, on whichever stream it was enqueued, and returns the first error.  Whoever
+  // frees or regrows what an enqueued query may still use goes through here, so a new kind adds its run to this list only.
+  hipError_t wait_queries() {
+    hipError_t first = hipSuccess;
+    for (QueryRun* r : {&rq.run, &mh.run, &pq.run, &sq.run}) {
+      const hipError_t e = r->issued ? hipEventSynchronize(r->ev[2]) : hipSuccess;
+      if (first == hipSuccess) first = e;
+    }
+    return first;
+  }
   // sptr_render_rays (the caller's context; a pixel lane holds none): the call's own totals block (WaveView::tot
   // of its launches, so that the render totals never see them), the carried sum of a ray whose sample range is
   // split, the staging of host-pointer calls, and the events of the last call: begin and end on the context's
@@ -164,10 +176,7 @@ struct sptr_ctx {
     if (c.stream) (void)hipStreamSynchronize(c.stream);
     if (copy_stream) (void)hipStreamSynchronize(copy_stream);  // the lagged readback's copy
     // a query enqueued on a caller's stream (the caller synchronises it first; this costs nothing then)
-    if (rq.issued) (void)hipEventSynchronize(rq.ev[2]);
-    if (mh.issued) (void)hipEventSynchronize(mh.ev[2]);
-    if (pq.issued) (void)hipEventSynchronize(pq.ev[2]);
-    if (sq.issued) (void)hipEventSynchronize(sq.ev[1]);
+    (void)wait_queries();
     if (reg_ptr) (void)hipHostUnregister(reg_ptr);
     delete lane;
   }
@@ -2374,13 +2383,10 @@ static int ensure_geom_first(sptr_ctx* x) {
   return SPTR_OK;
 }
 
-// the last query, on whichever stream it was enqueued
+// the last query of every kind, on whichever stream it was enqueued
 static int query_wait(sptr_ctx* x) {
   Context& c = x->c;
-  if (x->rq.issued) API_HIP(hipEventSynchronize(x->rq.ev[2]));
-  if (x->mh.issued) API_HIP(hipEventSynchronize(x->mh.ev[2]));
-  if (x->pq.issued) API_HIP(hipEventSynchronize(x->pq.ev[2]));
-  if (x->sq.issued) API_HIP(hipEventSynchronize(x->sq.ev[1]));
+  API_HIP(x->wait_queries());
   return SPTR_OK;
 }
 
@@ -2395,8 +2401,8 @@ static int query_check_flag(sptr_ctx* x) {
   return fail(c, SPTR_ERR_HIP, "query: BVH traversal stack overflow (internal error)");
 }
 
-// What every enqueued batch needs first: the overflow flag, the geomID offsets, and, for a sorted batch of n rays,
-// scratch for the keys, the indices and the radix sort (shared by sptr_query_rays and sptr_query_multi_hit).
+// What every enqueued batch needs first: the overflow flag, the geomID offsets, and, for a sorted batch of n rays or
+// points, scratch for the keys, the indices and the radix sort (shared by every kind).
 static int query_scratch(sptr_ctx* x, uint32_t n, bool sort, hipStream_t s) {
   Context& c = x->c;
   auto& rq = x->rq;
@@ -2424,11 +2430,14 @@ static int query_scratch(sptr_ctx* x, uint32_t n, bool sort, hipStream_t s) {
   return SPTR_OK;
 }
 
-// The sort phase on s: keys, radix sort; the trace then reads rq.order.
-static int query_sort(sptr_ctx* x, const SceneView& sv, const float4* rays, uint32_t n, hipStream_t s) {
+// launch_ray_keys / launch_point_keys
+using KeyLauncher = void (*)(const SceneView&, const float4*, uint32_t, uint64_t*, uint32_t*, hipStream_t);
+
+// The sort phase on s: the kind's keys, radix sort; the kind's launch then reads rq.order.
+static int query_sort(sptr_ctx* x, const SceneView& sv, KeyLauncher keys, const float4* in, uint32_t n, hipStream_t s) {
   Context& c = x->c;
   auto& rq = x->rq;
-  launch_ray_keys(sv, rays, n, static_cast<uint64_t*>(rq.keys.p), static_cast<uint32_t*>(rq.index.p), s);
+  keys(sv, in, n, static_cast<uint64_t*>(rq.keys.p), static_cast<uint32_t*>(rq.index.p), s);
   API_HIP(hipGetLastError());
   size_t tb = rq.temp.bytes;
   API_HIP(radix_sort_pairs_u64(rq.temp.p, tb, static_cast<const uint64_t*>(rq.keys.p),
@@ -2437,21 +2446,170 @@ static int query_sort(sptr_ctx* x, const SceneView& sv, const float4* rays, uint
   return SPTR_OK;
 }
 
+// The head of every enqueued batch (in: its n rays or points) on s: the run's events, created on first use; the order
+// (sort_default: the kind's choice for a query that sets neither sort flag); the shared scratch; the begin event;
+// and, for a sorted batch, the sort phase and its event.  *order is what the kind's view takes: null when unsorted.
+static int query_begin(sptr_ctx* x, sptr_ctx::QueryRun& run, const SceneView& sv, uint32_t flags, bool sort_default,
+                       KeyLauncher keys, const float4* in, uint32_t n, hipStream_t s, const uint32_t** order) {
+  Context& c = x->c;
+  const bool sort = (flags & SPTR_QUERY_SORT) != 0u ||
+                    ((flags & SPTR_QUERY_NO_SORT) == 0u && sv.lds_bytes == 0u && sort_default);
+  for (DevEvent& e : run.ev)
+    if (!e) API_HIP(hipEventCreate(e.put()));
+  const int rs = query_scratch(x, n, sort, s);
+  if (rs != SPTR_OK) return rs;
+  API_HIP(hipEventRecord(run.ev[0], s));
+  *order = nullptr;
+  if (sort) {
+    const int rk = query_sort(x, sv, keys, in, n, s);
+    if (rk != SPTR_OK) return rk;
+    API_HIP(hipEventRecord(run.ev[1], s));
+    *order = static_cast<const uint32_t*>(x->rq.order.p);
+  }
+  return SPTR_OK;
+}
+
+// The tail, right after the kind's launch: the run counts as issued only once its end event is recorded.
+static int query_end(sptr_ctx* x, sptr_ctx::QueryRun& run, bool sorted, hipStream_t s) {
+  Context& c = x->c;
+  API_HIP(hipGetLastError());
+  API_HIP(hipEventRecord(run.ev[2], s));
+  run.issued = true;
+  run.sorted = sorted;
+  ++run.count;
+  return SPTR_OK;
+}
+
+// The checks every kind makes, in three parts: a kind's own checks come between them, and the order is behaviour (a
+// call with several defects reports the first).  who: the function's name in the messages; noun: "rays" / "points".
+static int query_refuse(sptr_ctx* x, int code, const char* who, const std::string& what) {
+  return fail(x->c, code, std::string(who) + ": " + what);
+}
+
+static int check_query_flags(sptr_ctx* x, const char* who, uint32_t flags, uint32_t allowed, const char* unknown) {
+  if (x->is_lane) return query_refuse(x, SPTR_ERR_INVALID, who, "not on a lane context");
+  if (flags & ~allowed) return query_refuse(x, SPTR_ERR_INVALID, who, unknown);
+  if ((flags & SPTR_QUERY_SORT) && (flags & SPTR_QUERY_NO_SORT))
+    return query_refuse(x, SPTR_ERR_INVALID, who, "SPTR_QUERY_SORT and SPTR_QUERY_NO_SORT exclude each other");
+  return SPTR_OK;
+}
+
+static int check_query_batch(sptr_ctx* x, const char* who, const char* noun, uint32_t n, const void* in) {
+  if (n > kQueryMaxRays) return query_refuse(x, SPTR_ERR_INVALID, who, std::string("more than 2^28 ") + noun);
+  if (n && !in) return query_refuse(x, SPTR_ERR_INVALID, who, std::string("no ") + noun);
+  return SPTR_OK;
+}
+
+// misaligned: of the device pointers the kind checks; alignment: its rule, as the message states it
+static int check_query_placement(sptr_ctx* x, const char* who, bool dev, const void* stream, bool misaligned,
+                                 const char* alignment) {
+  if (!dev && stream) return query_refuse(x, SPTR_ERR_INVALID, who, "host pointers cannot be enqueued on a stream");
+  if (dev && misaligned) return query_refuse(x, SPTR_ERR_INVALID, who, alignment);
+  if (!x->c.have_scene) return query_refuse(x, SPTR_ERR_NO_SCENE, who, "no scene");
+  return SPTR_OK;
+}
+
+// One output of a host-pointer query: the caller's array, the pointer member of the device-side copy of the query
+// struct that takes the staged address, the array's bytes, and whether it is staged though the caller passes NULL.
+struct StageField {
+  void* host;
+  void* member;
+  size_t bytes;
+  bool always = false;
+};
+constexpr int kStageMaxFields = 10;
+
+// Host pointers: the input goes to rq.stage_in and every output that is taken gets its place in rq.stage_out
+// (query_stage.h); the members of the device-side copy point there afterwards, those of the other outputs stay NULL.
+static int stage_query(sptr_ctx* x, const void* in, void* in_member, size_t in_bytes, const StageField* f, int k) {
+  Context& c = x->c;
+  auto& rq = x->rq;
+  if (k > kStageMaxFields) return fail(c, SPTR_ERR_INVALID, "query: more staged fields than kStageMaxFields (internal error)");
+  size_t bytes[kStageMaxFields], offset[kStageMaxFields];
+  for (int i = 0; i < k; ++i) bytes[i] = f[i].host || f[i].always ? f[i].bytes : 0;
+  const size_t total = stage_layout(bytes, k, offset);
+  API_HIP(rq.stage_in.ensure(in_bytes));
+  API_HIP(rq.stage_out.ensure(total));
+  API_HIP(hipMemcpy(rq.stage_in.p, in, in_bytes, hipMemcpyHostToDevice));
+  std::memcpy(in_member, &rq.stage_in.p, sizeof(void*));
+  for (int i = 0; i < k; ++i) {
+    void* p = f[i].host || f[i].always ? static_cast<char*>(rq.stage_out.p) + offset[i] : nullptr;
+    std::memcpy(f[i].member, &p, sizeof p);
+  }
+  return SPTR_OK;
+}
+
+// ... and back, once the query completed: the outputs the caller takes
+static int stage_copy_back(sptr_ctx* x, const StageField* f, int k) {
+  Context& c = x->c;
+  for (int i = 0; i < k; ++i) {
+    if (!f[i].host) continue;
+    void* p = nullptr;
+    std::memcpy(&p, f[i].member, sizeof p);
+    API_HIP(hipMemcpy(f[i].host, p, f[i].bytes, hipMemcpyDeviceToHost));
+  }
+  return SPTR_OK;
+}
+
+// The synchronous call of every kind, after its checks: waits for the pending render and the last queries, stages
+// host pointers (in_member, f: into the copy of the query struct that `enqueue` passes on), enqueues on the
+// context's stream, waits, reports a traversal-stack overflow and copies the staged outputs back.
+extern "C++" {  // (a template, within this file's extern "C")
+template <class Enqueue>
+static int query_sync(sptr_ctx* x, bool dev, const void* in, void* in_member, size_t in_bytes, const StageField* f,
+                      int k, Enqueue enqueue) {
+  Context& c = x->c;
+  if (sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;
+  const int rw = query_wait(x);
+  if (rw != SPTR_OK) return rw;
+  if (!dev) {
+    const int rs = stage_query(x, in, in_member, in_bytes, f, k);
+    if (rs != SPTR_OK) return rs;
+  }
+  const int rc = enqueue();
+  if (rc != SPTR_OK) return rc;
+  API_HIP(hipStreamSynchronize(c.stream));
+  const int rf = query_check_flag(x);
+  if (rf != SPTR_OK) return rf;
+  return dev ? SPTR_OK : stage_copy_back(x, f, k);
+}
+}  // extern "C++"
+
+// What the info call of every kind reports of its last run, into the caller's outputs (each may be NULL): waits for
+// the run's end event; device ms of the sort phase (0 when unsorted) and of what followed it, sorted (0 / 1), runs.
+static int query_run_info(sptr_ctx* x, const sptr_ctx::QueryRun& run, double* ms_sort, double* ms_main,
+                          uint32_t* sorted, uint32_t* queries) {
+  Context& c = x->c;
+  double ms_s = 0.0, ms_m = 0.0;
+  if (run.issued) {
+    API_HIP(hipSetDevice(c.device));
+    API_HIP(hipEventSynchronize(run.ev[2]));
+    float ms = 0.0f;
+    if (run.sorted) {
+      API_HIP(hipEventElapsedTime(&ms, run.ev[0], run.ev[1]));
+      ms_s = ms;
+    }
+    API_HIP(hipEventElapsedTime(&ms, run.sorted ? run.ev[1] : run.ev[0], run.ev[2]));
+    ms_m = ms;
+  }
+  if (ms_sort) *ms_sort = ms_s;
+  if (ms_main) *ms_main = ms_m;
+  if (sorted) *sorted = run.issued && run.sorted ? 1u : 0u;
+  if (queries) *queries = run.count;
+  return SPTR_OK;
+}
+
 // One validated batch with device pointers, enqueued on s: [keys, radix sort,] trace.
 static int enqueue_query(sptr_ctx* x, const sptr_ray_query& q, hipStream_t s) {
   Context& c = x->c;
-  auto& rq = x->rq;
   const SceneView sv = scene_view(c);
   const bool any = (q.flags & SPTR_QUERY_ANY_HIT) != 0u;
-  const bool sort = (q.flags & SPTR_QUERY_SORT) != 0u ||
-                    ((q.flags & SPTR_QUERY_NO_SORT) == 0u && sv.lds_bytes == 0u && query_sorts_by_default(sv, q.n));
-  for (DevEvent& e : rq.ev)
-    if (!e) API_HIP(hipEventCreate(e.put()));
-  const int rs = query_scratch(x, q.n, sort, s);
-  if (rs != SPTR_OK) return rs;
   RayQueryView v{};
   v.rays = reinterpret_cast<const float4*>(q.rays);
   v.n = q.n;
+  const int rb = query_begin(x, x->rq.run, sv, q.flags, query_sorts_by_default(sv, q.n), launch_ray_keys, v.rays, q.n,
+                             s, &v.order);
+  if (rb != SPTR_OK) return rb;
   if (any) {
     v.occ = q.occluded;
   } else {
@@ -2463,122 +2621,56 @@ static int enqueue_query(sptr_ctx* x, const sptr_ray_query& q, hipStream_t s) {
   }
   v.tri_orig = static_cast<const uint32_t*>(c.tri_orig.p);
   v.geom_first = static_cast<const uint32_t*>(x->geom_first.p);
-  v.stack_overflow = static_cast<uint32_t*>(rq.flag.p);
-  API_HIP(hipEventRecord(rq.ev[0], s));
-  if (sort) {
-    const int rk = query_sort(x, sv, v.rays, q.n, s);
-    if (rk != SPTR_OK) return rk;
-    API_HIP(hipEventRecord(rq.ev[1], s));
-    v.order = static_cast<const uint32_t*>(rq.order.p);
-  }
+  v.stack_overflow = static_cast<uint32_t*>(x->rq.flag.p);
   launch_rayquery(sv, v, any, s);
-  API_HIP(hipGetLastError());
-  API_HIP(hipEventRecord(rq.ev[2], s));
-  rq.issued = true;
-  rq.sorted = sort;
-  ++rq.count;
-  return SPTR_OK;
+  return query_end(x, x->rq.run, v.order != nullptr, s);
 }
 
 int sptr_query_rays(sptr_ctx* x, const sptr_ray_query* q, void* stream) {
   if (!x || !q) return SPTR_ERR_INVALID;
   Context& c = x->c;
-  if (x->is_lane) return fail(c, SPTR_ERR_INVALID, "query_rays: not on a lane context");
+  const char* who = "query_rays";
   const bool any = (q->flags & SPTR_QUERY_ANY_HIT) != 0u, dev = (q->flags & SPTR_QUERY_DEVICE_PTRS) != 0u;
-  if (q->flags & ~kQueryFlags) return fail(c, SPTR_ERR_INVALID, "query_rays: unknown flags");
-  if ((q->flags & SPTR_QUERY_SORT) && (q->flags & SPTR_QUERY_NO_SORT))
-    return fail(c, SPTR_ERR_INVALID, "query_rays: SPTR_QUERY_SORT and SPTR_QUERY_NO_SORT exclude each other");
-  if (q->n > kQueryMaxRays) return fail(c, SPTR_ERR_INVALID, "query_rays: more than 2^28 rays");
-  if (q->n && !q->rays) return fail(c, SPTR_ERR_INVALID, "query_rays: no rays");
+  int rc = check_query_flags(x, who, q->flags, kQueryFlags, "unknown flags");
+  if (rc == SPTR_OK) rc = check_query_batch(x, who, "rays", q->n, q->rays);
+  if (rc != SPTR_OK) return rc;
   if (any && !q->occluded) return fail(c, SPTR_ERR_INVALID, "query_rays: SPTR_QUERY_ANY_HIT needs the occluded output");
-  if (!dev && stream) return fail(c, SPTR_ERR_INVALID, "query_rays: host pointers cannot be enqueued on a stream");
-  if (dev && (reinterpret_cast<uintptr_t>(q->rays) & 15u))
-    return fail(c, SPTR_ERR_INVALID, "query_rays: the device ray buffer must be 16-byte aligned");
-  if (!c.have_scene) return fail(c, SPTR_ERR_NO_SCENE, "query_rays: no scene");
+  rc = check_query_placement(x, who, dev, stream, (reinterpret_cast<uintptr_t>(q->rays) & 15u) != 0u,
+                             "the device ray buffer must be 16-byte aligned");
+  if (rc != SPTR_OK) return rc;
   if (q->n == 0u) return SPTR_OK;
   API_HIP(hipSetDevice(c.device));
   if (stream) return enqueue_query(x, *q, static_cast<hipStream_t>(stream));  // on a caller's stream the call only enqueues
-  if (sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;
-  const int rw = query_wait(x);
-  if (rw != SPTR_OK) return rw;
   sptr_ray_query d = *q;
   const size_t n = q->n;
-  // host pointers: rays in, then geom | prim | t | ng | uv | occluded out, staged in the context
-  const size_t off_prim = n * 4, off_t = n * 8, off_ng = n * 12, off_uv = n * 24, off_occ = n * 32;
-  if (!dev) {
-    auto& rq = x->rq;
-    API_HIP(rq.stage_in.ensure(n * 32));
-    API_HIP(rq.stage_out.ensure(n * 33));
-    API_HIP(hipMemcpy(rq.stage_in.p, q->rays, n * 32, hipMemcpyHostToDevice));
-    char* o = static_cast<char*>(rq.stage_out.p);
-    d.rays = static_cast<const float*>(rq.stage_in.p);
-    d.geom = q->geom ? reinterpret_cast<uint32_t*>(o) : nullptr;
-    d.prim = q->prim ? reinterpret_cast<uint32_t*>(o + off_prim) : nullptr;
-    d.t = q->t ? reinterpret_cast<float*>(o + off_t) : nullptr;
-    d.ng = q->ng ? reinterpret_cast<float*>(o + off_ng) : nullptr;
-    d.uv = q->uv ? reinterpret_cast<float*>(o + off_uv) : nullptr;
-    d.occluded = reinterpret_cast<uint8_t*>(o + off_occ);
-  }
-  const int rc = enqueue_query(x, d, c.stream);
-  if (rc != SPTR_OK) return rc;
-  API_HIP(hipStreamSynchronize(c.stream));
-  const int rf = query_check_flag(x);
-  if (rf != SPTR_OK) return rf;
-  if (!dev) {
-    if (any) {
-      API_HIP(hipMemcpy(q->occluded, d.occluded, n, hipMemcpyDeviceToHost));
-    } else {
-      if (q->geom) API_HIP(hipMemcpy(q->geom, d.geom, n * 4, hipMemcpyDeviceToHost));
-      if (q->prim) API_HIP(hipMemcpy(q->prim, d.prim, n * 4, hipMemcpyDeviceToHost));
-      if (q->t) API_HIP(hipMemcpy(q->t, d.t, n * 4, hipMemcpyDeviceToHost));
-      if (q->ng) API_HIP(hipMemcpy(q->ng, d.ng, n * 12, hipMemcpyDeviceToHost));
-      if (q->uv) API_HIP(hipMemcpy(q->uv, d.uv, n * 8, hipMemcpyDeviceToHost));
-    }
-  }
-  return SPTR_OK;
+  const StageField out[] = {{q->geom, &d.geom, n * 4}, {q->prim, &d.prim, n * 4},
+                            {q->t, &d.t, n * 4},       {q->ng, &d.ng, n * 12},
+                            {q->uv, &d.uv, n * 8},     {q->occluded, &d.occluded, n}};
+  return query_sync(x, dev, q->rays, &d.rays, n * 32, any ? out + 5 : out, any ? 1 : 5,
+                    [&] { return enqueue_query(x, d, c.stream); });
 }
 
 int sptr_query_info(sptr_ctx* x, double* ms_sort, double* ms_trace, uint32_t* sorted, uint32_t* queries) {
   if (!x) return SPTR_ERR_INVALID;
-  Context& c = x->c;
-  auto& rq = x->rq;
-  double ms_s = 0.0, ms_t = 0.0;
-  if (rq.issued) {
-    API_HIP(hipSetDevice(c.device));
-    API_HIP(hipEventSynchronize(rq.ev[2]));
-    float ms = 0.0f;
-    if (rq.sorted) {
-      API_HIP(hipEventElapsedTime(&ms, rq.ev[0], rq.ev[1]));
-      ms_s = ms;
-    }
-    API_HIP(hipEventElapsedTime(&ms, rq.sorted ? rq.ev[1] : rq.ev[0], rq.ev[2]));
-    ms_t = ms;
-  }
-  if (ms_sort) *ms_sort = ms_s;
-  if (ms_trace) *ms_trace = ms_t;
-  if (sorted) *sorted = rq.issued && rq.sorted ? 1u : 0u;
-  if (queries) *queries = rq.count;
-  return rq.issued ? query_check_flag(x) : SPTR_OK;
+  const int ri = query_run_info(x, x->rq.run, ms_sort, ms_trace, sorted, queries);
+  if (ri != SPTR_OK) return ri;
+  return x->rq.run.issued ? query_check_flag(x) : SPTR_OK;
 }
 
 // ---- multi-hit ray queries ----------------------------------------------------------------------------
 constexpr uint32_t kMultiHitFlags = SPTR_QUERY_DEVICE_PTRS | SPTR_QUERY_SORT | SPTR_QUERY_NO_SORT;
 
-// One validated batch with device pointers, enqueued on s: [keys, radix sort,] trace; enqueue_query's twin.
+// One validated batch with device pointers, enqueued on s: [keys, radix sort,] trace.
 static int enqueue_multi_hit(sptr_ctx* x, const sptr_multi_hit_query& q, hipStream_t s) {
   Context& c = x->c;
-  auto& rq = x->rq;
   auto& mh = x->mh;
   const SceneView sv = scene_view(c);
-  const bool sort = (q.flags & SPTR_QUERY_SORT) != 0u ||
-                    ((q.flags & SPTR_QUERY_NO_SORT) == 0u && sv.lds_bytes == 0u && query_sorts_by_default(sv, q.n));
-  for (DevEvent& e : mh.ev)
-    if (!e) API_HIP(hipEventCreate(e.put()));
-  const int rs = query_scratch(x, q.n, sort, s);
-  if (rs != SPTR_OK) return rs;
   RayMultiView v{};
   v.rays = reinterpret_cast<const float4*>(q.rays);
   v.n = q.n;
+  const int rb = query_begin(x, mh.run, sv, q.flags, query_sorts_by_default(sv, q.n), launch_ray_keys, v.rays, q.n, s,
+                             &v.order);
+  if (rb != SPTR_OK) return rb;
   v.k = q.max_hits;
   v.count = q.count;
   v.geom = q.geom;
@@ -2588,108 +2680,50 @@ static int enqueue_multi_hit(sptr_ctx* x, const sptr_multi_hit_query& q, hipStre
   v.uv = q.uv;
   v.tri_orig = static_cast<const uint32_t*>(c.tri_orig.p);
   v.geom_first = static_cast<const uint32_t*>(x->geom_first.p);
-  v.stack_overflow = static_cast<uint32_t*>(rq.flag.p);
-  API_HIP(hipEventRecord(mh.ev[0], s));
-  if (sort) {
-    const int rk = query_sort(x, sv, v.rays, q.n, s);
-    if (rk != SPTR_OK) return rk;
-    API_HIP(hipEventRecord(mh.ev[1], s));
-    v.order = static_cast<const uint32_t*>(rq.order.p);
-  }
+  v.stack_overflow = static_cast<uint32_t*>(x->rq.flag.p);
   launch_rayquery_multi(sv, v, s, &mh.list_capacity, &mh.lds_bytes);
-  API_HIP(hipGetLastError());
-  API_HIP(hipEventRecord(mh.ev[2], s));
-  mh.issued = true;
-  mh.sorted = sort;
-  ++mh.count;
-  return SPTR_OK;
+  return query_end(x, mh.run, v.order != nullptr, s);
 }
 
 int sptr_query_multi_hit(sptr_ctx* x, const sptr_multi_hit_query* q, void* stream) {
   if (!x || !q) return SPTR_ERR_INVALID;
   Context& c = x->c;
-  if (x->is_lane) return fail(c, SPTR_ERR_INVALID, "query_multi_hit: not on a lane context");
+  const char* who = "query_multi_hit";
   const bool dev = (q->flags & SPTR_QUERY_DEVICE_PTRS) != 0u;
-  if (q->flags & ~kMultiHitFlags) return fail(c, SPTR_ERR_INVALID, "query_multi_hit: SPTR_QUERY_ANY_HIT or unknown flags");
-  if ((q->flags & SPTR_QUERY_SORT) && (q->flags & SPTR_QUERY_NO_SORT))
-    return fail(c, SPTR_ERR_INVALID, "query_multi_hit: SPTR_QUERY_SORT and SPTR_QUERY_NO_SORT exclude each other");
+  int rc = check_query_flags(x, who, q->flags, kMultiHitFlags, "SPTR_QUERY_ANY_HIT or unknown flags");
+  if (rc != SPTR_OK) return rc;
   if (q->max_hits < 1u || q->max_hits > (uint32_t)SPTR_MULTI_HIT_MAX)
     return fail(c, SPTR_ERR_INVALID, "query_multi_hit: max_hits must be 1 .. SPTR_MULTI_HIT_MAX");
   if (q->n > kQueryMaxRays || (uint64_t)q->n * q->max_hits > kQueryMaxRays)
     return fail(c, SPTR_ERR_INVALID, "query_multi_hit: more than 2^28 rays or hit slots");
-  if (q->n && !q->rays) return fail(c, SPTR_ERR_INVALID, "query_multi_hit: no rays");
+  rc = check_query_batch(x, who, "rays", q->n, q->rays);
+  if (rc != SPTR_OK) return rc;
   if (q->n && !q->count) return fail(c, SPTR_ERR_INVALID, "query_multi_hit: the count output is required");
   if (q->pad || q->reserved[0] || q->reserved[1] || q->reserved[2] || q->reserved[3])
     return fail(c, SPTR_ERR_INVALID, "query_multi_hit: pad and reserved must be 0");
-  if (!dev && stream) return fail(c, SPTR_ERR_INVALID, "query_multi_hit: host pointers cannot be enqueued on a stream");
-  if (dev && (reinterpret_cast<uintptr_t>(q->rays) & 15u))
-    return fail(c, SPTR_ERR_INVALID, "query_multi_hit: the device ray buffer must be 16-byte aligned");
-  if (!c.have_scene) return fail(c, SPTR_ERR_NO_SCENE, "query_multi_hit: no scene");
+  rc = check_query_placement(x, who, dev, stream, (reinterpret_cast<uintptr_t>(q->rays) & 15u) != 0u,
+                             "the device ray buffer must be 16-byte aligned");
+  if (rc != SPTR_OK) return rc;
   if (q->n == 0u) return SPTR_OK;
   API_HIP(hipSetDevice(c.device));
   if (stream) return enqueue_multi_hit(x, *q, static_cast<hipStream_t>(stream));  // only enqueues
-  if (sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;
-  const int rw = query_wait(x);
-  if (rw != SPTR_OK) return rw;
   sptr_multi_hit_query d = *q;
   const size_t n = q->n, m = n * q->max_hits;
-  // host pointers: rays in, then count | geom | prim | t | ng | uv out, staged in the context
-  const size_t off_geom = n * 4, off_prim = off_geom + m * 4, off_t = off_prim + m * 4, off_ng = off_t + m * 4,
-               off_uv = off_ng + m * 12, total = off_uv + m * 8;
-  if (!dev) {
-    auto& rq = x->rq;
-    API_HIP(rq.stage_in.ensure(n * 32));
-    API_HIP(rq.stage_out.ensure(total));
-    API_HIP(hipMemcpy(rq.stage_in.p, q->rays, n * 32, hipMemcpyHostToDevice));
-    char* o = static_cast<char*>(rq.stage_out.p);
-    d.rays = static_cast<const float*>(rq.stage_in.p);
-    d.count = reinterpret_cast<uint32_t*>(o);
-    d.geom = q->geom ? reinterpret_cast<uint32_t*>(o + off_geom) : nullptr;
-    d.prim = q->prim ? reinterpret_cast<uint32_t*>(o + off_prim) : nullptr;
-    d.t = q->t ? reinterpret_cast<float*>(o + off_t) : nullptr;
-    d.ng = q->ng ? reinterpret_cast<float*>(o + off_ng) : nullptr;
-    d.uv = q->uv ? reinterpret_cast<float*>(o + off_uv) : nullptr;
-  }
-  const int rc = enqueue_multi_hit(x, d, c.stream);
-  if (rc != SPTR_OK) return rc;
-  API_HIP(hipStreamSynchronize(c.stream));
-  const int rf = query_check_flag(x);
-  if (rf != SPTR_OK) return rf;
-  if (!dev) {
-    API_HIP(hipMemcpy(q->count, d.count, n * 4, hipMemcpyDeviceToHost));
-    if (q->geom) API_HIP(hipMemcpy(q->geom, d.geom, m * 4, hipMemcpyDeviceToHost));
-    if (q->prim) API_HIP(hipMemcpy(q->prim, d.prim, m * 4, hipMemcpyDeviceToHost));
-    if (q->t) API_HIP(hipMemcpy(q->t, d.t, m * 4, hipMemcpyDeviceToHost));
-    if (q->ng) API_HIP(hipMemcpy(q->ng, d.ng, m * 12, hipMemcpyDeviceToHost));
-    if (q->uv) API_HIP(hipMemcpy(q->uv, d.uv, m * 8, hipMemcpyDeviceToHost));
-  }
-  return SPTR_OK;
+  const StageField out[] = {{q->count, &d.count, n * 4}, {q->geom, &d.geom, m * 4},
+                            {q->prim, &d.prim, m * 4},   {q->t, &d.t, m * 4},
+                            {q->ng, &d.ng, m * 12},      {q->uv, &d.uv, m * 8}};
+  return query_sync(x, dev, q->rays, &d.rays, n * 32, out, 6, [&] { return enqueue_multi_hit(x, d, c.stream); });
 }
 
 int sptr_multi_hit_info(sptr_ctx* x, double* ms_sort, double* ms_trace, uint32_t* sorted, uint32_t* queries,
                         uint32_t* list_capacity, uint32_t* lds_bytes) {
   if (!x) return SPTR_ERR_INVALID;
-  Context& c = x->c;
   auto& mh = x->mh;
-  double ms_s = 0.0, ms_t = 0.0;
-  if (mh.issued) {
-    API_HIP(hipSetDevice(c.device));
-    API_HIP(hipEventSynchronize(mh.ev[2]));
-    float ms = 0.0f;
-    if (mh.sorted) {
-      API_HIP(hipEventElapsedTime(&ms, mh.ev[0], mh.ev[1]));
-      ms_s = ms;
-    }
-    API_HIP(hipEventElapsedTime(&ms, mh.sorted ? mh.ev[1] : mh.ev[0], mh.ev[2]));
-    ms_t = ms;
-  }
-  if (ms_sort) *ms_sort = ms_s;
-  if (ms_trace) *ms_trace = ms_t;
-  if (sorted) *sorted = mh.issued && mh.sorted ? 1u : 0u;
-  if (queries) *queries = mh.count;
+  const int ri = query_run_info(x, mh.run, ms_sort, ms_trace, sorted, queries);
+  if (ri != SPTR_OK) return ri;
   if (list_capacity) *list_capacity = mh.list_capacity;
   if (lds_bytes) *lds_bytes = mh.lds_bytes;
-  return mh.issued ? query_check_flag(x) : SPTR_OK;
+  return mh.run.issued ? query_check_flag(x) : SPTR_OK;
 }
 
 // ---- closest-point queries ----------------------------------------------------------------------------
@@ -2698,19 +2732,12 @@ constexpr uint32_t kPointFlags = SPTR_QUERY_DEVICE_PTRS | SPTR_QUERY_SORT | SPTR
 // beat the unsorted walk by more than the spread has been measured, so the default never sorts.
 static bool points_sort_by_default(const SceneView&, uint32_t) { return false; }
 
-// One validated batch with device pointers, enqueued on s: [keys, radix sort,] walk; enqueue_query's twin.
+// One validated batch with device pointers, enqueued on s: [keys, radix sort,] walk.
 static int enqueue_points(sptr_ctx* x, const sptr_point_query& q, hipStream_t s) {
   Context& c = x->c;
-  auto& rq = x->rq;
   auto& pq = x->pq;
   const SceneView sv = scene_view(c);
-  const bool sort = (q.flags & SPTR_QUERY_SORT) != 0u ||
-                    ((q.flags & SPTR_QUERY_NO_SORT) == 0u && sv.lds_bytes == 0u && points_sort_by_default(sv, q.n));
   const bool count = (q.flags & SPTR_POINT_COUNT) != 0u;
-  for (DevEvent& e : pq.ev)
-    if (!e) API_HIP(hipEventCreate(e.put()));
-  const int rs = query_scratch(x, q.n, sort, s);
-  if (rs != SPTR_OK) return rs;
   if (count) {
     if (!pq.counters.p) {
       const int rw = query_wait(x);
@@ -2722,6 +2749,9 @@ static int enqueue_points(sptr_ctx* x, const sptr_point_query& q, hipStream_t s)
   PointQueryView v{};
   v.points = reinterpret_cast<const float4*>(q.points);
   v.n = q.n;
+  const int rb = query_begin(x, pq.run, sv, q.flags, points_sort_by_default(sv, q.n), launch_point_keys, v.points, q.n,
+                             s, &v.order);
+  if (rb != SPTR_OK) return rb;
   v.geom = q.geom;
   v.prim = q.prim;
   v.dist2 = q.dist2;
@@ -2731,89 +2761,55 @@ static int enqueue_points(sptr_ctx* x, const sptr_point_query& q, hipStream_t s)
   v.ng = q.ng;
   v.tri_orig = static_cast<const uint32_t*>(c.tri_orig.p);
   v.geom_first = static_cast<const uint32_t*>(x->geom_first.p);
-  v.stack_overflow = static_cast<uint32_t*>(rq.flag.p);
+  v.stack_overflow = static_cast<uint32_t*>(x->rq.flag.p);
   v.counters = count ? static_cast<unsigned long long*>(pq.counters.p) : nullptr;
-  API_HIP(hipEventRecord(pq.ev[0], s));
-  if (sort) {
-    launch_point_keys(sv, v.points, q.n, static_cast<uint64_t*>(rq.keys.p), static_cast<uint32_t*>(rq.index.p), s);
-    API_HIP(hipGetLastError());
-    size_t tb = rq.temp.bytes;
-    API_HIP(radix_sort_pairs_u64(rq.temp.p, tb, static_cast<const uint64_t*>(rq.keys.p),
-                                 static_cast<uint64_t*>(rq.keys_sorted.p), static_cast<const uint32_t*>(rq.index.p),
-                                 static_cast<uint32_t*>(rq.order.p), q.n, s));
-    API_HIP(hipEventRecord(pq.ev[1], s));
-    v.order = static_cast<const uint32_t*>(rq.order.p);
-  }
   launch_pointquery(sv, v, s, &pq.lds_bytes);
-  API_HIP(hipGetLastError());
-  API_HIP(hipEventRecord(pq.ev[2], s));
-  pq.issued = true;
-  pq.sorted = sort;
-  pq.counted = count;
-  ++pq.count;
-  return SPTR_OK;
+  const int re = query_end(x, pq.run, v.order != nullptr, s);
+  if (re == SPTR_OK) pq.counted = count;
+  return re;
+}
+
+// a device point query's input must be 16-byte aligned, its outputs 4-byte aligned
+static bool point_query_misaligned(const sptr_point_query& q) {
+  uintptr_t outs = 0;
+  for (const void* p : std::initializer_list<const void*>{q.geom, q.prim, q.dist2, q.dist, q.point, q.uv, q.ng})
+    outs |= reinterpret_cast<uintptr_t>(p);
+  return (reinterpret_cast<uintptr_t>(q.points) & 15u) != 0u || (outs & 3u) != 0u;
+}
+constexpr const char* kPointAlignment = "the device point buffer must be 16-byte aligned, the outputs 4-byte aligned";
+
+// the seven outputs of a point query (q: the caller's, d: the device-side copy); ids: staged whether or not taken
+static void point_stage_fields(const sptr_point_query& q, sptr_point_query& d, bool ids, StageField* f) {
+  const size_t n = q.n;
+  f[0] = {q.geom, &d.geom, n * 4, ids};
+  f[1] = {q.prim, &d.prim, n * 4, ids};
+  f[2] = {q.dist2, &d.dist2, n * 4};
+  f[3] = {q.dist, &d.dist, n * 4};
+  f[4] = {q.point, &d.point, n * 12};
+  f[5] = {q.uv, &d.uv, n * 8};
+  f[6] = {q.ng, &d.ng, n * 12};
 }
 
 int sptr_query_points(sptr_ctx* x, const sptr_point_query* q, void* stream) {
   if (!x || !q) return SPTR_ERR_INVALID;
   Context& c = x->c;
-  if (x->is_lane) return fail(c, SPTR_ERR_INVALID, "query_points: not on a lane context");
+  const char* who = "query_points";
   const bool dev = (q->flags & SPTR_QUERY_DEVICE_PTRS) != 0u;
-  if (q->flags & ~kPointFlags) return fail(c, SPTR_ERR_INVALID, "query_points: SPTR_QUERY_ANY_HIT or unknown flags");
-  if ((q->flags & SPTR_QUERY_SORT) && (q->flags & SPTR_QUERY_NO_SORT))
-    return fail(c, SPTR_ERR_INVALID, "query_points: SPTR_QUERY_SORT and SPTR_QUERY_NO_SORT exclude each other");
-  if (q->n > kQueryMaxRays) return fail(c, SPTR_ERR_INVALID, "query_points: more than 2^28 points");
-  if (q->n && !q->points) return fail(c, SPTR_ERR_INVALID, "query_points: no points");
+  int rc = check_query_flags(x, who, q->flags, kPointFlags, "SPTR_QUERY_ANY_HIT or unknown flags");
+  if (rc == SPTR_OK) rc = check_query_batch(x, who, "points", q->n, q->points);
+  if (rc != SPTR_OK) return rc;
   if (q->reserved[0] || q->reserved[1] || q->reserved[2] || q->reserved[3])
     return fail(c, SPTR_ERR_INVALID, "query_points: reserved must be 0");
-  if (!dev && stream) return fail(c, SPTR_ERR_INVALID, "query_points: host pointers cannot be enqueued on a stream");
-  if (dev && ((reinterpret_cast<uintptr_t>(q->points) & 15u) || (reinterpret_cast<uintptr_t>(q->geom) & 3u) ||
-              (reinterpret_cast<uintptr_t>(q->prim) & 3u) || (reinterpret_cast<uintptr_t>(q->dist2) & 3u) ||
-              (reinterpret_cast<uintptr_t>(q->dist) & 3u) || (reinterpret_cast<uintptr_t>(q->point) & 3u) ||
-              (reinterpret_cast<uintptr_t>(q->uv) & 3u) || (reinterpret_cast<uintptr_t>(q->ng) & 3u)))
-    return fail(c, SPTR_ERR_INVALID, "query_points: the device point buffer must be 16-byte aligned, the outputs 4-byte aligned");
-  if (!c.have_scene) return fail(c, SPTR_ERR_NO_SCENE, "query_points: no scene");
+  rc = check_query_placement(x, who, dev, stream, point_query_misaligned(*q), kPointAlignment);
+  if (rc != SPTR_OK) return rc;
   if (q->n == 0u) return SPTR_OK;
   API_HIP(hipSetDevice(c.device));
   if (stream) return enqueue_points(x, *q, static_cast<hipStream_t>(stream));  // only enqueues
-  if (sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;
-  const int rw = query_wait(x);
-  if (rw != SPTR_OK) return rw;
   sptr_point_query d = *q;
-  const size_t n = q->n;
-  // host pointers: points in, then geom | prim | dist2 | dist | point | uv | ng out, staged in the context
-  const size_t off_prim = n * 4, off_d2 = off_prim + n * 4, off_d = off_d2 + n * 4, off_pt = off_d + n * 4,
-               off_uv = off_pt + n * 12, off_ng = off_uv + n * 8, total = off_ng + n * 12;
-  if (!dev) {
-    auto& rq = x->rq;
-    API_HIP(rq.stage_in.ensure(n * 16));
-    API_HIP(rq.stage_out.ensure(total));
-    API_HIP(hipMemcpy(rq.stage_in.p, q->points, n * 16, hipMemcpyHostToDevice));
-    char* o = static_cast<char*>(rq.stage_out.p);
-    d.points = static_cast<const float*>(rq.stage_in.p);
-    d.geom = q->geom ? reinterpret_cast<uint32_t*>(o) : nullptr;
-    d.prim = q->prim ? reinterpret_cast<uint32_t*>(o + off_prim) : nullptr;
-    d.dist2 = q->dist2 ? reinterpret_cast<float*>(o + off_d2) : nullptr;
-    d.dist = q->dist ? reinterpret_cast<float*>(o + off_d) : nullptr;
-    d.point = q->point ? reinterpret_cast<float*>(o + off_pt) : nullptr;
-    d.uv = q->uv ? reinterpret_cast<float*>(o + off_uv) : nullptr;
-    d.ng = q->ng ? reinterpret_cast<float*>(o + off_ng) : nullptr;
-  }
-  const int rc = enqueue_points(x, d, c.stream);
-  if (rc != SPTR_OK) return rc;
-  API_HIP(hipStreamSynchronize(c.stream));
-  const int rf = query_check_flag(x);
-  if (rf != SPTR_OK) return rf;
-  if (!dev) {
-    if (q->geom) API_HIP(hipMemcpy(q->geom, d.geom, n * 4, hipMemcpyDeviceToHost));
-    if (q->prim) API_HIP(hipMemcpy(q->prim, d.prim, n * 4, hipMemcpyDeviceToHost));
-    if (q->dist2) API_HIP(hipMemcpy(q->dist2, d.dist2, n * 4, hipMemcpyDeviceToHost));
-    if (q->dist) API_HIP(hipMemcpy(q->dist, d.dist, n * 4, hipMemcpyDeviceToHost));
-    if (q->point) API_HIP(hipMemcpy(q->point, d.point, n * 12, hipMemcpyDeviceToHost));
-    if (q->uv) API_HIP(hipMemcpy(q->uv, d.uv, n * 8, hipMemcpyDeviceToHost));
-    if (q->ng) API_HIP(hipMemcpy(q->ng, d.ng, n * 12, hipMemcpyDeviceToHost));
-  }
-  return SPTR_OK;
+  StageField out[7];
+  point_stage_fields(*q, d, false, out);
+  return query_sync(x, dev, q->points, &d.points, (size_t)q->n * 16, out, 7,
+                    [&] { return enqueue_points(x, d, c.stream); });
 }
 
 int sptr_point_query_info(sptr_ctx* x, double* ms_sort, double* ms_walk, uint32_t* sorted, uint32_t* queries,
@@ -2821,27 +2817,13 @@ int sptr_point_query_info(sptr_ctx* x, double* ms_sort, double* ms_walk, uint32_
   if (!x) return SPTR_ERR_INVALID;
   Context& c = x->c;
   auto& pq = x->pq;
-  double ms_s = 0.0, ms_w = 0.0;
+  const int ri = query_run_info(x, pq.run, ms_sort, ms_walk, sorted, queries);
+  if (ri != SPTR_OK) return ri;
   uint64_t cnt[2] = {0, 0};
-  if (pq.issued) {
-    API_HIP(hipSetDevice(c.device));
-    API_HIP(hipEventSynchronize(pq.ev[2]));
-    float ms = 0.0f;
-    if (pq.sorted) {
-      API_HIP(hipEventElapsedTime(&ms, pq.ev[0], pq.ev[1]));
-      ms_s = ms;
-    }
-    API_HIP(hipEventElapsedTime(&ms, pq.sorted ? pq.ev[1] : pq.ev[0], pq.ev[2]));
-    ms_w = ms;
-    if (pq.counted) API_HIP(hipMemcpy(cnt, pq.counters.p, 16, hipMemcpyDeviceToHost));
-  }
-  if (ms_sort) *ms_sort = ms_s;
-  if (ms_walk) *ms_walk = ms_w;
-  if (sorted) *sorted = pq.issued && pq.sorted ? 1u : 0u;
-  if (queries) *queries = pq.count;
+  if (pq.run.issued && pq.counted) API_HIP(hipMemcpy(cnt, pq.counters.p, 16, hipMemcpyDeviceToHost));
   if (node_visits) *node_visits = cnt[0];
   if (prim_tests) *prim_tests = cnt[1];
-  return pq.issued ? query_check_flag(x) : SPTR_OK;
+  return pq.run.issued ? query_check_flag(x) : SPTR_OK;
 }
 
 // ---- signed distance queries ----------------------------------------------------------------------------
@@ -2859,7 +2841,7 @@ static int enqueue_signed(sptr_ctx* x, const sptr_signed_query& q, hipStream_t s
   const SignedState& g = c.sg;
   sptr_point_query d = q.q;
   d.flags &= ~(uint32_t)SPTR_SIGNED_FLIP_TRIANGLES;
-  for (DevEvent& e : sq.ev)
+  for (DevEvent& e : sq.run.ev)
     if (!e) API_HIP(hipEventCreate(e.put()));
   if (!d.geom || !d.prim) {  // the ids go into scratch
     const size_t nb = (size_t)d.n * 4;
@@ -2891,104 +2873,49 @@ static int enqueue_signed(sptr_ctx* x, const sptr_signed_query& q, hipStream_t s
   v.num_tris = g.num_tris;
   v.num_sph = g.num_sph;
   v.num_tri_geoms = g.num_tri_geoms;
-  API_HIP(hipEventRecord(sq.ev[0], s));
+  API_HIP(hipEventRecord(sq.run.ev[0], s));
   launch_point_sign(v, s);
-  API_HIP(hipGetLastError());
-  API_HIP(hipEventRecord(sq.ev[1], s));
-  sq.issued = true;
-  return SPTR_OK;
+  return query_end(x, sq.run, false, s);
 }
 
 int sptr_query_signed_distance(sptr_ctx* x, const sptr_signed_query* sq_in, void* stream) {
   if (!x || !sq_in) return SPTR_ERR_INVALID;
   Context& c = x->c;
   const sptr_point_query* q = &sq_in->q;
-  if (x->is_lane) return fail(c, SPTR_ERR_INVALID, "query_signed_distance: not on a lane context");
+  const char* who = "query_signed_distance";
   const bool dev = (q->flags & SPTR_QUERY_DEVICE_PTRS) != 0u;
-  if (q->flags & ~(kPointFlags | (uint32_t)SPTR_SIGNED_FLIP_TRIANGLES))
-    return fail(c, SPTR_ERR_INVALID, "query_signed_distance: SPTR_QUERY_ANY_HIT or unknown flags");
-  if ((q->flags & SPTR_QUERY_SORT) && (q->flags & SPTR_QUERY_NO_SORT))
-    return fail(c, SPTR_ERR_INVALID, "query_signed_distance: SPTR_QUERY_SORT and SPTR_QUERY_NO_SORT exclude each other");
-  if (q->n > kQueryMaxRays) return fail(c, SPTR_ERR_INVALID, "query_signed_distance: more than 2^28 points");
-  if (q->n && !q->points) return fail(c, SPTR_ERR_INVALID, "query_signed_distance: no points");
+  int rc = check_query_flags(x, who, q->flags, kPointFlags | (uint32_t)SPTR_SIGNED_FLIP_TRIANGLES,
+                             "SPTR_QUERY_ANY_HIT or unknown flags");
+  if (rc == SPTR_OK) rc = check_query_batch(x, who, "points", q->n, q->points);
+  if (rc != SPTR_OK) return rc;
   if (q->reserved[0] || q->reserved[1] || q->reserved[2] || q->reserved[3] || sq_in->reserved[0] || sq_in->reserved[1] ||
       sq_in->reserved[2] || sq_in->reserved[3])
     return fail(c, SPTR_ERR_INVALID, "query_signed_distance: reserved must be 0");
-  if (!dev && stream)
-    return fail(c, SPTR_ERR_INVALID, "query_signed_distance: host pointers cannot be enqueued on a stream");
-  if (dev && ((reinterpret_cast<uintptr_t>(q->points) & 15u) || (reinterpret_cast<uintptr_t>(q->geom) & 3u) ||
-              (reinterpret_cast<uintptr_t>(q->prim) & 3u) || (reinterpret_cast<uintptr_t>(q->dist2) & 3u) ||
-              (reinterpret_cast<uintptr_t>(q->dist) & 3u) || (reinterpret_cast<uintptr_t>(q->point) & 3u) ||
-              (reinterpret_cast<uintptr_t>(q->uv) & 3u) || (reinterpret_cast<uintptr_t>(q->ng) & 3u) ||
-              (reinterpret_cast<uintptr_t>(sq_in->signed_dist) & 3u) || (reinterpret_cast<uintptr_t>(sq_in->normal) & 3u) ||
-              (reinterpret_cast<uintptr_t>(sq_in->feature) & 3u)))
-    return fail(c, SPTR_ERR_INVALID,
-                "query_signed_distance: the device point buffer must be 16-byte aligned, the outputs 4-byte aligned");
-  if (!c.have_scene) return fail(c, SPTR_ERR_NO_SCENE, "query_signed_distance: no scene");
+  const uintptr_t outs = reinterpret_cast<uintptr_t>(sq_in->signed_dist) | reinterpret_cast<uintptr_t>(sq_in->normal) |
+                         reinterpret_cast<uintptr_t>(sq_in->feature);
+  rc = check_query_placement(x, who, dev, stream, point_query_misaligned(*q) || (outs & 3u) != 0u, kPointAlignment);
+  if (rc != SPTR_OK) return rc;
   if (!c.sg.valid)
     return fail(c, SPTR_ERR_INVALID, "query_signed_distance: the scene was not uploaded with sptr_set_signed_distance(1)");
   if (q->n == 0u) return SPTR_OK;
   API_HIP(hipSetDevice(c.device));
   if (stream) return enqueue_signed(x, *sq_in, static_cast<hipStream_t>(stream));  // only enqueues
-  if (sync_pending(c) != SPTR_OK) return SPTR_ERR_HIP;
-  const int rw = query_wait(x);
-  if (rw != SPTR_OK) return rw;
   sptr_signed_query d = *sq_in;
   const size_t n = q->n;
-  // host pointers: points in, then the point query's outputs and signed_dist | normal | feature out, staged
-  const size_t off_prim = n * 4, off_d2 = off_prim + n * 4, off_d = off_d2 + n * 4, off_pt = off_d + n * 4,
-               off_uv = off_pt + n * 12, off_ng = off_uv + n * 8, off_sd = off_ng + n * 12, off_nn = off_sd + n * 4,
-               off_ft = off_nn + n * 12, total = off_ft + n * 4;
-  if (!dev) {
-    auto& rq = x->rq;
-    API_HIP(rq.stage_in.ensure(n * 16));
-    API_HIP(rq.stage_out.ensure(total));
-    API_HIP(hipMemcpy(rq.stage_in.p, q->points, n * 16, hipMemcpyHostToDevice));
-    char* o = static_cast<char*>(rq.stage_out.p);
-    d.q.points = static_cast<const float*>(rq.stage_in.p);
-    d.q.geom = reinterpret_cast<uint32_t*>(o);  // (the sign pass reads the ids whether or not the caller takes them)
-    d.q.prim = reinterpret_cast<uint32_t*>(o + off_prim);
-    d.q.dist2 = q->dist2 ? reinterpret_cast<float*>(o + off_d2) : nullptr;
-    d.q.dist = q->dist ? reinterpret_cast<float*>(o + off_d) : nullptr;
-    d.q.point = q->point ? reinterpret_cast<float*>(o + off_pt) : nullptr;
-    d.q.uv = q->uv ? reinterpret_cast<float*>(o + off_uv) : nullptr;
-    d.q.ng = q->ng ? reinterpret_cast<float*>(o + off_ng) : nullptr;
-    d.signed_dist = sq_in->signed_dist ? reinterpret_cast<float*>(o + off_sd) : nullptr;
-    d.normal = sq_in->normal ? reinterpret_cast<float*>(o + off_nn) : nullptr;
-    d.feature = sq_in->feature ? reinterpret_cast<uint32_t*>(o + off_ft) : nullptr;
-  }
-  const int rc = enqueue_signed(x, d, c.stream);
-  if (rc != SPTR_OK) return rc;
-  API_HIP(hipStreamSynchronize(c.stream));
-  const int rf = query_check_flag(x);
-  if (rf != SPTR_OK) return rf;
-  if (!dev) {
-    if (q->geom) API_HIP(hipMemcpy(q->geom, d.q.geom, n * 4, hipMemcpyDeviceToHost));
-    if (q->prim) API_HIP(hipMemcpy(q->prim, d.q.prim, n * 4, hipMemcpyDeviceToHost));
-    if (q->dist2) API_HIP(hipMemcpy(q->dist2, d.q.dist2, n * 4, hipMemcpyDeviceToHost));
-    if (q->dist) API_HIP(hipMemcpy(q->dist, d.q.dist, n * 4, hipMemcpyDeviceToHost));
-    if (q->point) API_HIP(hipMemcpy(q->point, d.q.point, n * 12, hipMemcpyDeviceToHost));
-    if (q->uv) API_HIP(hipMemcpy(q->uv, d.q.uv, n * 8, hipMemcpyDeviceToHost));
-    if (q->ng) API_HIP(hipMemcpy(q->ng, d.q.ng, n * 12, hipMemcpyDeviceToHost));
-    if (sq_in->signed_dist) API_HIP(hipMemcpy(sq_in->signed_dist, d.signed_dist, n * 4, hipMemcpyDeviceToHost));
-    if (sq_in->normal) API_HIP(hipMemcpy(sq_in->normal, d.normal, n * 12, hipMemcpyDeviceToHost));
-    if (sq_in->feature) API_HIP(hipMemcpy(sq_in->feature, d.feature, n * 4, hipMemcpyDeviceToHost));
-  }
-  return SPTR_OK;
+  StageField out[10];
+  point_stage_fields(*q, d.q, true, out);  // (the sign pass reads the ids whether or not the caller takes them)
+  out[7] = {sq_in->signed_dist, &d.signed_dist, n * 4};
+  out[8] = {sq_in->normal, &d.normal, n * 12};
+  out[9] = {sq_in->feature, &d.feature, n * 4};
+  return query_sync(x, dev, q->points, &d.q.points, n * 16, out, 10, [&] { return enqueue_signed(x, d, c.stream); });
 }
 
 int sptr_signed_info(sptr_ctx* x, sptr_signed_info_t* out) {
   if (!x) return SPTR_ERR_INVALID;
-  Context& c = x->c;
-  const SignedState& g = c.sg;
+  const SignedState& g = x->c.sg;
   double ms_sign = 0.0;
-  if (x->sq.issued) {
-    API_HIP(hipSetDevice(c.device));
-    API_HIP(hipEventSynchronize(x->sq.ev[1]));
-    float ms = 0.0f;
-    API_HIP(hipEventElapsedTime(&ms, x->sq.ev[0], x->sq.ev[1]));
-    ms_sign = ms;
-  }
+  const int ri = query_run_info(x, x->sq.run, nullptr, &ms_sign, nullptr, nullptr);
+  if (ri != SPTR_OK) return ri;
   if (out) {
     out->welded_vertices = g.valid ? g.counts_h[0] : 0u;
     out->edges = g.valid ? g.counts_h[1] : 0u;

@@ -473,6 +473,74 @@ def host_query_signed_distance(scene: FlatScene, points, fields=None, flip_trian
     return res
 
 
+_QUERY_FIELDS = (("geom", 1, np.uint32), ("prim", 1, np.uint32), ("t", 1, np.float32), ("ng", 3, np.float32),
+                 ("uv", 2, np.float32))
+_QUERY_EMPTY = C.c_uint64(0)
+_QUERY_INPUT = {8: ("rays", ", ".join), 4: ("points", str)}  # by row width: the noun and how a message lists the fields
+
+
+def _query_flags(sort, device: bool) -> int:
+    return ((SPTR_QUERY_DEVICE_PTRS if device else 0)
+            | (0 if sort is None else SPTR_QUERY_SORT if sort else SPTR_QUERY_NO_SORT))
+
+
+def _query_arrays(x, width: int, who: str, table, fields, out, stream, per_row=None, always=()):
+    """What Renderer.query_rays, query_multi_hit, query_points and query_signed_distance (who) do before the call: x
+    is a numpy (n, width) array (host path) or a contiguous float32 device tensor of n x width (device path).  table:
+    (name, cols, dtype) of the outputs that fields (None: all) chooses from; always: such rows that every result
+    holds, before the chosen ones.  An output is out[name], checked, or a new array: numpy or torch, like x, of
+    (n,) or (n, cols), with per_row = K of (n, K) or (n, K, cols) (the rows of `always` stay (n,)).
+    Returns x as the call takes it, n, whether the device path is taken, {name: array} and the address function."""
+    noun, listing = _QUERY_INPUT[width]
+    device = hasattr(x, "data_ptr")
+    if device:
+        import torch
+
+        if x.element_size() != 4 or not x.is_floating_point() or not x.is_contiguous() or x.numel() % width:
+            raise SptrError(f"{who}: device {noun} must be a contiguous float32 tensor of n x {width}")
+        n = x.numel() // width
+        tdt = {np.uint32: torch.uint32, np.float32: torch.float32, np.uint8: torch.uint8}
+
+        def alloc(shape, dt):
+            return torch.empty(shape, dtype=tdt[dt], device=x.device)
+
+        def addr(a):
+            return a.data_ptr()
+
+        def ok(a, size, dt):
+            return a.is_contiguous() and a.numel() == size and a.dtype == tdt[dt] and a.device == x.device
+    else:
+        if stream is not None:
+            raise SptrError(f"{who}: a stream needs device tensors")
+        x = np.ascontiguousarray(x, np.float32).reshape(-1, width)
+        n = len(x)
+
+        def alloc(shape, dt):
+            return np.zeros(shape, dt)
+
+        def addr(a):
+            return a.ctypes.data
+
+        def ok(a, size, dt):
+            return isinstance(a, np.ndarray) and a.flags.c_contiguous and a.size == size and a.dtype == dt
+    known = [f for f, _, _ in table]
+    names = known if fields is None else list(fields)
+    if any(f not in known for f in names):
+        raise SptrError(f"{who}: fields must name some of {listing(known)} (got {names})")
+    rows = (n,) if per_row is None else (n, per_row)
+    res = {}
+    for lead, (name, cols, dt) in [((n,), f) for f in always] + [(rows, f) for f in table if f[0] in names]:
+        shape = lead + ((cols,) if cols > 1 else ())
+        a = (out or {}).get(name)
+        if a is None:
+            a = alloc(shape, dt)
+        elif not ok(a, int(np.prod(shape)), dt):
+            of = f"{n} x {cols}" if per_row is None else f"{shape}"
+            raise SptrError(f"{who}: out[{name!r}] must be contiguous, of {of} {np.dtype(dt).name}")
+        res[name] = a
+    return x, n, device, res, addr
+
+
 def camera_lookat(pos=(0.0, 3.0, 8.0), target=(0.0, 1.0, 0.0), fov=60.0, aspect=800 / 600) -> Camera:
     """Camera(pos, target, +Y, fov, aspect) as src/main.cpp:97-103 sets it up."""
     L = lib()
@@ -928,9 +996,22 @@ class Renderer:
         self._check(self._L.sptr_occluded(self._h, _f(rays), len(rays), _b(out)), "occluded")
         return out
 
-    _QUERY_FIELDS = (("geom", 1, np.uint32), ("prim", 1, np.uint32), ("t", 1, np.float32), ("ng", 3, np.float32),
-                     ("uv", 2, np.float32))
-    _QUERY_EMPTY = C.c_uint64(0)
+    def _query_call(self, who: str, q, flags: int, sort, stream, x, n: int, device: bool, res: dict, addr) -> dict:
+        """The call of a query method after _query_arrays: the input, n and the flags go into q (a SignedQuery holds
+        them in its PointQuery), the outputs' addresses into the members of their names."""
+        head = q.q if isinstance(q, SignedQuery) else q
+        put = _signed_query_set if isinstance(q, SignedQuery) else setattr
+        setattr(head, "points" if isinstance(head, PointQuery) else "rays", addr(x) if n else None)
+        head.n = n
+        head.flags = flags | _query_flags(sort, device)
+        for name, a in res.items():  # (an empty tensor has no address: n == 0 writes nothing, any non-NULL will do)
+            put(q, name, addr(a) or (C.addressof(_QUERY_EMPTY) if n == 0 else None))
+        if device and stream is None and n:
+            import torch
+
+            torch.cuda.current_stream(x.device).synchronize()  # the input's (and the outputs') producers
+        self._check(getattr(self._L, "sptr_" + who)(self._h, C.byref(q), C.c_void_p(stream) if stream else None), who)
+        return res
 
     def query_rays(self, rays, any_hit: bool = False, sort: bool | None = None, uv: bool = True,
                    stream: int | None = None, fields=None, out: dict | None = None) -> dict:
@@ -950,63 +1031,15 @@ class Renderer:
         tensors are valid once that stream is synchronised; the caller orders the stream after the rays'
         producer.  Without it a device-path call waits for torch's current stream first, runs on the
         context's stream and returns when the results are written."""
-        device = hasattr(rays, "data_ptr")
-        if device:
-            import torch
-
-            if rays.element_size() != 4 or not rays.is_floating_point() or not rays.is_contiguous() or rays.numel() % 8:
-                raise SptrError("query_rays: device rays must be a contiguous float32 tensor of n x 8")
-            n = rays.numel() // 8
-            tdt = {np.uint32: torch.uint32, np.float32: torch.float32, np.uint8: torch.uint8}
-
-            def alloc(cols, dt):
-                return torch.empty((n, cols) if cols > 1 else (n,), dtype=tdt[dt], device=rays.device)
-
-            def addr(a):
-                return a.data_ptr()
-
-            def ok(a, cols, dt):
-                return a.is_contiguous() and a.numel() == n * cols and a.dtype == tdt[dt] and a.device == rays.device
-        else:
-            if stream is not None:
-                raise SptrError("query_rays: a stream needs device tensors")
-            rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
-            n = len(rays)
-
-            def alloc(cols, dt):
-                return np.zeros((n, cols) if cols > 1 else (n,), dt)
-
-            def addr(a):
-                return a.ctypes.data
-
-            def ok(a, cols, dt):
-                return isinstance(a, np.ndarray) and a.flags.c_contiguous and a.size == n * cols and a.dtype == dt
         if any_hit:
-            want = (("occluded", 1, np.uint8),)
+            table, fields = (("occluded", 1, np.uint8),), None
         else:
-            names = [f for f, _, _ in self._QUERY_FIELDS if uv or f != "uv"] if fields is None else list(fields)
-            if not names or any(f not in [g for g, _, _ in self._QUERY_FIELDS] for f in names):
-                raise SptrError(f"query_rays: fields must name some of geom, prim, t, ng, uv (got {names})")
-            want = tuple(x for x in self._QUERY_FIELDS if x[0] in names)
-        res = {}
-        for name, cols, dt in want:
-            a = (out or {}).get(name)
-            if a is None:
-                a = alloc(cols, dt)
-            elif not ok(a, cols, dt):
-                raise SptrError(f"query_rays: out[{name!r}] must be contiguous, of {n} x {cols} {np.dtype(dt).name}")
-            res[name] = a
-        q = RayQuery()
-        q.rays = addr(rays) if n else None
-        q.n = n
-        q.flags = ((SPTR_QUERY_ANY_HIT if any_hit else 0) | (SPTR_QUERY_DEVICE_PTRS if device else 0)
-                   | (0 if sort is None else SPTR_QUERY_SORT if sort else SPTR_QUERY_NO_SORT))
-        for name, a in res.items():  # (an empty tensor has no address: n == 0 writes nothing, any non-NULL will do)
-            setattr(q, name, addr(a) or (C.addressof(self._QUERY_EMPTY) if n == 0 else None))
-        if device and stream is None and n:
-            torch.cuda.current_stream(rays.device).synchronize()  # the rays' (and the outputs') producers
-        self._check(self._L.sptr_query_rays(self._h, C.byref(q), C.c_void_p(stream) if stream else None), "query_rays")
-        return res
+            table = _QUERY_FIELDS
+            fields = [f for f, _, _ in table if uv or f != "uv"] if fields is None else list(fields)
+        arrays = _query_arrays(rays, 8, "query_rays", table, fields, out, stream)
+        if not arrays[3]:
+            raise SptrError(f"query_rays: fields must name some of geom, prim, t, ng, uv (got {fields})")
+        return self._query_call("query_rays", RayQuery(), SPTR_QUERY_ANY_HIT if any_hit else 0, sort, stream, *arrays)
 
     def query_info(self) -> dict:
         """sptr_query_info: waits for the last query; device ms of its sort phase (0 when unsorted) and of its
@@ -1026,65 +1059,11 @@ class Renderer:
         slots at and beyond a ray's count hold 0xFFFFFFFF ids, t = +inf and zeros.  numpy in, numpy out; device
         tensors in, torch tensors out."""
         K = int(max_hits)
-        device = hasattr(rays, "data_ptr")
-        if device:
-            import torch
-
-            if rays.element_size() != 4 or not rays.is_floating_point() or not rays.is_contiguous() or rays.numel() % 8:
-                raise SptrError("query_multi_hit: device rays must be a contiguous float32 tensor of n x 8")
-            n = rays.numel() // 8
-            tdt = {np.uint32: torch.uint32, np.float32: torch.float32}
-
-            def alloc(shape, dt):
-                return torch.empty(shape, dtype=tdt[dt], device=rays.device)
-
-            def addr(a):
-                return a.data_ptr()
-
-            def ok(a, size, dt):
-                return a.is_contiguous() and a.numel() == size and a.dtype == tdt[dt] and a.device == rays.device
-        else:
-            if stream is not None:
-                raise SptrError("query_multi_hit: a stream needs device tensors")
-            rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
-            n = len(rays)
-
-            def alloc(shape, dt):
-                return np.zeros(shape, dt)
-
-            def addr(a):
-                return a.ctypes.data
-
-            def ok(a, size, dt):
-                return isinstance(a, np.ndarray) and a.flags.c_contiguous and a.size == size and a.dtype == dt
-        known = [g for g, _, _ in self._QUERY_FIELDS]
-        names = known if fields is None else list(fields)
-        if any(f not in known for f in names):
-            raise SptrError(f"query_multi_hit: fields must name some of geom, prim, t, ng, uv (got {names})")
-        kk = max(K, 0)
-        want = (("count", (n,), np.uint32),) + tuple((f, (n, kk, cols) if cols > 1 else (n, kk), dt)
-                                                     for f, cols, dt in self._QUERY_FIELDS if f in names)
-        res = {}
-        for name, shape, dt in want:
-            a = (out or {}).get(name)
-            if a is None:
-                a = alloc(shape, dt)
-            elif not ok(a, int(np.prod(shape)), dt):
-                raise SptrError(f"query_multi_hit: out[{name!r}] must be contiguous, of {shape} {np.dtype(dt).name}")
-            res[name] = a
+        arrays = _query_arrays(rays, 8, "query_multi_hit", _QUERY_FIELDS, fields, out, stream, per_row=max(K, 0),
+                               always=(("count", 1, np.uint32),))
         q = MultiHitQuery()
-        q.rays = addr(rays) if n else None
-        q.n = n
         q.max_hits = K if 0 <= K < 2 ** 32 else 0
-        q.flags = ((SPTR_QUERY_DEVICE_PTRS if device else 0)
-                   | (0 if sort is None else SPTR_QUERY_SORT if sort else SPTR_QUERY_NO_SORT))
-        for name, a in res.items():  # (an empty tensor has no address: n == 0 writes nothing)
-            setattr(q, name, addr(a) or (C.addressof(self._QUERY_EMPTY) if n == 0 else None))
-        if device and stream is None and n:
-            torch.cuda.current_stream(rays.device).synchronize()  # the rays' (and the outputs') producers
-        self._check(self._L.sptr_query_multi_hit(self._h, C.byref(q), C.c_void_p(stream) if stream else None),
-                    "query_multi_hit")
-        return res
+        return self._query_call("query_multi_hit", q, 0, sort, stream, *arrays)
 
     def multi_hit_info(self) -> dict:
         """sptr_multi_hit_info: waits for the last multi-hit query; query_info's values for it, and the list
@@ -1106,64 +1085,8 @@ class Renderer:
         ng): geom, prim (n, uint32; 0xFFFFFFFF on a miss), dist2, dist (n; +inf on a miss), point (n, 3), uv (n, 2),
         ng (n, 3).  numpy in, numpy out; device tensors in, torch tensors out.  count=True (SPTR_POINT_COUNT) makes
         the kernel count node visits and primitive tests for point_query_info()."""
-        device = hasattr(points, "data_ptr")
-        if device:
-            import torch
-
-            if (points.element_size() != 4 or not points.is_floating_point() or not points.is_contiguous()
-                    or points.numel() % 4):
-                raise SptrError("query_points: device points must be a contiguous float32 tensor of n x 4")
-            n = points.numel() // 4
-            tdt = {np.uint32: torch.uint32, np.float32: torch.float32}
-
-            def alloc(cols, dt):
-                return torch.empty((n, cols) if cols > 1 else (n,), dtype=tdt[dt], device=points.device)
-
-            def addr(a):
-                return a.data_ptr()
-
-            def ok(a, cols, dt):
-                return a.is_contiguous() and a.numel() == n * cols and a.dtype == tdt[dt] and a.device == points.device
-        else:
-            if stream is not None:
-                raise SptrError("query_points: a stream needs device tensors")
-            points = np.ascontiguousarray(points, np.float32).reshape(-1, 4)
-            n = len(points)
-
-            def alloc(cols, dt):
-                return np.zeros((n, cols) if cols > 1 else (n,), dt)
-
-            def addr(a):
-                return a.ctypes.data
-
-            def ok(a, cols, dt):
-                return isinstance(a, np.ndarray) and a.flags.c_contiguous and a.size == n * cols and a.dtype == dt
-        known = [f for f, _, _ in _POINT_FIELDS]
-        names = known if fields is None else list(fields)
-        if any(f not in known for f in names):
-            raise SptrError(f"query_points: fields must name some of {known} (got {names})")
-        res = {}
-        for name, cols, dt in _POINT_FIELDS:
-            if name not in names:
-                continue
-            a = (out or {}).get(name)
-            if a is None:
-                a = alloc(cols, dt)
-            elif not ok(a, cols, dt):
-                raise SptrError(f"query_points: out[{name!r}] must be contiguous, of {n} x {cols} {np.dtype(dt).name}")
-            res[name] = a
-        q = PointQuery()
-        q.points = addr(points) if n else None
-        q.n = n
-        q.flags = ((SPTR_QUERY_DEVICE_PTRS if device else 0) | (SPTR_POINT_COUNT if count else 0)
-                   | (0 if sort is None else SPTR_QUERY_SORT if sort else SPTR_QUERY_NO_SORT))
-        for name, a in res.items():  # (an empty tensor has no address: n == 0 writes nothing)
-            setattr(q, name, addr(a) or (C.addressof(self._QUERY_EMPTY) if n == 0 else None))
-        if device and stream is None and n:
-            torch.cuda.current_stream(points.device).synchronize()  # the points' (and the outputs') producers
-        self._check(self._L.sptr_query_points(self._h, C.byref(q), C.c_void_p(stream) if stream else None),
-                    "query_points")
-        return res
+        arrays = _query_arrays(points, 4, "query_points", _POINT_FIELDS, fields, out, stream)
+        return self._query_call("query_points", PointQuery(), SPTR_POINT_COUNT if count else 0, sort, stream, *arrays)
 
     def set_signed_distance(self, on: bool = True) -> None:
         """sptr_set_signed_distance: the next upload keeps the triangles' corners and builds the pseudonormal tables
@@ -1177,67 +1100,9 @@ class Renderer:
         closest feature, unnormalised) and feature (n, uint32: 0 face, 1-3 edge, 4-6 vertex, 7 sphere, 0xFFFFFFFF
         miss).  flip_triangles (SPTR_SIGNED_FLIP_TRIANGLES) negates the sign of triangle results, for meshes whose
         stored normals point inward.  The scene must have been uploaded after set_signed_distance()."""
-        device = hasattr(points, "data_ptr")
-        if device:
-            import torch
-
-            if (points.element_size() != 4 or not points.is_floating_point() or not points.is_contiguous()
-                    or points.numel() % 4):
-                raise SptrError("query_signed_distance: device points must be a contiguous float32 tensor of n x 4")
-            n = points.numel() // 4
-            tdt = {np.uint32: torch.uint32, np.float32: torch.float32}
-
-            def alloc(cols, dt):
-                return torch.empty((n, cols) if cols > 1 else (n,), dtype=tdt[dt], device=points.device)
-
-            def addr(a):
-                return a.data_ptr()
-
-            def ok(a, cols, dt):
-                return a.is_contiguous() and a.numel() == n * cols and a.dtype == tdt[dt] and a.device == points.device
-        else:
-            if stream is not None:
-                raise SptrError("query_signed_distance: a stream needs device tensors")
-            points = np.ascontiguousarray(points, np.float32).reshape(-1, 4)
-            n = len(points)
-
-            def alloc(cols, dt):
-                return np.zeros((n, cols) if cols > 1 else (n,), dt)
-
-            def addr(a):
-                return a.ctypes.data
-
-            def ok(a, cols, dt):
-                return isinstance(a, np.ndarray) and a.flags.c_contiguous and a.size == n * cols and a.dtype == dt
-        table = _POINT_FIELDS + _SIGNED_FIELDS
-        known = [f for f, _, _ in table]
-        names = known if fields is None else list(fields)
-        if any(f not in known for f in names):
-            raise SptrError(f"query_signed_distance: fields must name some of {known} (got {names})")
-        res = {}
-        for name, cols, dt in table:
-            if name not in names:
-                continue
-            a = (out or {}).get(name)
-            if a is None:
-                a = alloc(cols, dt)
-            elif not ok(a, cols, dt):
-                raise SptrError(f"query_signed_distance: out[{name!r}] must be contiguous, of {n} x {cols} "
-                                f"{np.dtype(dt).name}")
-            res[name] = a
-        q = SignedQuery()
-        q.q.points = addr(points) if n else None
-        q.q.n = n
-        q.q.flags = ((SPTR_QUERY_DEVICE_PTRS if device else 0) | (SPTR_POINT_COUNT if count else 0)
-                     | (SPTR_SIGNED_FLIP_TRIANGLES if flip_triangles else 0)
-                     | (0 if sort is None else SPTR_QUERY_SORT if sort else SPTR_QUERY_NO_SORT))
-        for name, a in res.items():  # (an empty tensor has no address: n == 0 writes nothing)
-            _signed_query_set(q, name, addr(a) or (C.addressof(self._QUERY_EMPTY) if n == 0 else None))
-        if device and stream is None and n:
-            torch.cuda.current_stream(points.device).synchronize()  # the points' (and the outputs') producers
-        self._check(self._L.sptr_query_signed_distance(self._h, C.byref(q), C.c_void_p(stream) if stream else None),
-                    "query_signed_distance")
-        return res
+        arrays = _query_arrays(points, 4, "query_signed_distance", _POINT_FIELDS + _SIGNED_FIELDS, fields, out, stream)
+        flags = (SPTR_POINT_COUNT if count else 0) | (SPTR_SIGNED_FLIP_TRIANGLES if flip_triangles else 0)
+        return self._query_call("query_signed_distance", SignedQuery(), flags, sort, stream, *arrays)
 
     def signed_info(self) -> dict:
         """sptr_signed_info: the table's counts (welded vertices, edges, open and irregular edges), its bytes, the

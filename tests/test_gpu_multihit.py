@@ -449,25 +449,38 @@ def test_errors_leave_the_context_usable(renderer):
     shifted = torch.zeros(n * 8 + 4, dtype=torch.float32, device="cuda:0")[1:1 + n * 8]  # 4 bytes off 16-byte alignment
     assert shifted.data_ptr() % 16 == 4
     dcount = torch.zeros(n, dtype=torch.int32, device="cuda:0")
-    cases = {
-        "any-hit flag": dict(rays=host, n=n, flags=sptr.SPTR_QUERY_ANY_HIT, max_hits=K, **ptr),
-        "unknown flag": dict(rays=host, n=n, flags=16, max_hits=K, **ptr),
-        "both sort flags": dict(rays=host, n=n, flags=sptr.SPTR_QUERY_SORT | sptr.SPTR_QUERY_NO_SORT, max_hits=K, **ptr),
-        "max_hits 0": dict(rays=host, n=n, max_hits=0, **ptr),
-        "max_hits 17": dict(rays=host, n=n, max_hits=17, **ptr),
-        "more than 2^28 rays": dict(rays=host, n=(1 << 28) + 1, max_hits=1, **ptr),
-        "more than 2^28 slots": dict(rays=host, n=(1 << 24) + 1, max_hits=16, **ptr),
-        "NULL rays": dict(rays=None, n=n, max_hits=K, **ptr),
-        "NULL count": dict(rays=host, n=n, max_hits=K, **{k: v for k, v in ptr.items() if k != "count"}),
-        "pad": dict(rays=host, n=n, max_hits=K, pad=1, **ptr),
-        "reserved": dict(rays=host, n=n, max_hits=K, reserved=(0, 0, 0, 1), **ptr),
-        "host pointers on a stream": dict(rays=host, n=n, max_hits=K, stream=stream.cuda_stream, **ptr),
-        "misaligned device rays": dict(rays=shifted.data_ptr(), n=n, flags=sptr.SPTR_QUERY_DEVICE_PTRS, max_hits=K,
-                                       count=dcount.data_ptr()),
+    cases = {  # what is wrong: (sptr_last_error's text, the arguments)
+        "any-hit flag": (b"query_multi_hit: SPTR_QUERY_ANY_HIT or unknown flags",
+                         dict(rays=host, n=n, flags=sptr.SPTR_QUERY_ANY_HIT, max_hits=K, **ptr)),
+        "unknown flag": (b"query_multi_hit: SPTR_QUERY_ANY_HIT or unknown flags",
+                         dict(rays=host, n=n, flags=16, max_hits=K, **ptr)),
+        "both sort flags": (b"query_multi_hit: SPTR_QUERY_SORT and SPTR_QUERY_NO_SORT exclude each other",
+                            dict(rays=host, n=n, flags=sptr.SPTR_QUERY_SORT | sptr.SPTR_QUERY_NO_SORT, max_hits=K, **ptr)),
+        "max_hits 0": (b"query_multi_hit: max_hits must be 1 .. SPTR_MULTI_HIT_MAX",
+                       dict(rays=host, n=n, max_hits=0, **ptr)),
+        "max_hits 17": (b"query_multi_hit: max_hits must be 1 .. SPTR_MULTI_HIT_MAX",
+                        dict(rays=host, n=n, max_hits=17, **ptr)),
+        "more than 2^28 rays": (b"query_multi_hit: more than 2^28 rays or hit slots",
+                                dict(rays=host, n=(1 << 28) + 1, max_hits=1, **ptr)),
+        "more than 2^28 slots": (b"query_multi_hit: more than 2^28 rays or hit slots",
+                                 dict(rays=host, n=(1 << 24) + 1, max_hits=16, **ptr)),
+        "NULL rays": (b"query_multi_hit: no rays",
+                      dict(rays=None, n=n, max_hits=K, **ptr)),
+        "NULL count": (b"query_multi_hit: the count output is required",
+                       dict(rays=host, n=n, max_hits=K, **{k: v for k, v in ptr.items() if k != "count"})),
+        "pad": (b"query_multi_hit: pad and reserved must be 0",
+                dict(rays=host, n=n, max_hits=K, pad=1, **ptr)),
+        "reserved": (b"query_multi_hit: pad and reserved must be 0",
+                     dict(rays=host, n=n, max_hits=K, reserved=(0, 0, 0, 1), **ptr)),
+        "host pointers on a stream": (b"query_multi_hit: host pointers cannot be enqueued on a stream",
+                                      dict(rays=host, n=n, max_hits=K, stream=stream.cuda_stream, **ptr)),
+        "misaligned device rays": (b"query_multi_hit: the device ray buffer must be 16-byte aligned",
+                                   dict(rays=shifted.data_ptr(), n=n, flags=sptr.SPTR_QUERY_DEVICE_PTRS, max_hits=K,
+                                        count=dcount.data_ptr())),
     }
-    for what, kw in cases.items():
+    for what, (message, kw) in cases.items():
         assert _raw(r, **kw) == INVALID, what
-        assert r._L.sptr_last_error(r._h), what
+        assert r._L.sptr_last_error(r._h) == message, what
         assert _renders_golden(r) == before, what  # the same bytes as before the refused call
     # (a lane context is the library's own and has no handle a caller could pass)
     with pytest.raises(sptr.SptrError):

@@ -438,20 +438,29 @@ def test_errors_leave_the_context_usable(renderer):
     dbytes = ddist.view(torch.uint8)[2:2 + 4 * n]  # 2 bytes off 4-byte alignment
     assert dbytes.data_ptr() % 4 == 2
     DEV = sptr.SPTR_QUERY_DEVICE_PTRS
-    cases = {
-        "any-hit flag": dict(points=host, n=n, flags=sptr.SPTR_QUERY_ANY_HIT, **ptr),
-        "unknown flag": dict(points=host, n=n, flags=32, **ptr),
-        "both sort flags": dict(points=host, n=n, flags=sptr.SPTR_QUERY_SORT | sptr.SPTR_QUERY_NO_SORT, **ptr),
-        "more than 2^28 points": dict(points=host, n=(1 << 28) + 1, **ptr),
-        "NULL points": dict(points=None, n=n, **ptr),
-        "reserved": dict(points=host, n=n, reserved=(0, 1, 0, 0), **ptr),
-        "host pointers on a stream": dict(points=host, n=n, stream=stream.cuda_stream, **ptr),
-        "misaligned device points": dict(points=shifted.data_ptr(), n=n, flags=DEV, dist=ddist.data_ptr()),
-        "misaligned device output": dict(points=good.data_ptr(), n=n, flags=DEV, dist=dbytes.data_ptr()),
+    cases = {  # what is wrong: (sptr_last_error's text, the arguments)
+        "any-hit flag": (b"query_points: SPTR_QUERY_ANY_HIT or unknown flags",
+                         dict(points=host, n=n, flags=sptr.SPTR_QUERY_ANY_HIT, **ptr)),
+        "unknown flag": (b"query_points: SPTR_QUERY_ANY_HIT or unknown flags",
+                         dict(points=host, n=n, flags=32, **ptr)),
+        "both sort flags": (b"query_points: SPTR_QUERY_SORT and SPTR_QUERY_NO_SORT exclude each other",
+                            dict(points=host, n=n, flags=sptr.SPTR_QUERY_SORT | sptr.SPTR_QUERY_NO_SORT, **ptr)),
+        "more than 2^28 points": (b"query_points: more than 2^28 points",
+                                  dict(points=host, n=(1 << 28) + 1, **ptr)),
+        "NULL points": (b"query_points: no points",
+                        dict(points=None, n=n, **ptr)),
+        "reserved": (b"query_points: reserved must be 0",
+                     dict(points=host, n=n, reserved=(0, 1, 0, 0), **ptr)),
+        "host pointers on a stream": (b"query_points: host pointers cannot be enqueued on a stream",
+                                      dict(points=host, n=n, stream=stream.cuda_stream, **ptr)),
+        "misaligned device points": (b"query_points: the device point buffer must be 16-byte aligned, the outputs 4-byte aligned",
+                                     dict(points=shifted.data_ptr(), n=n, flags=DEV, dist=ddist.data_ptr())),
+        "misaligned device output": (b"query_points: the device point buffer must be 16-byte aligned, the outputs 4-byte aligned",
+                                     dict(points=good.data_ptr(), n=n, flags=DEV, dist=dbytes.data_ptr())),
     }
-    for what, kw in cases.items():
+    for what, (message, kw) in cases.items():
         assert _raw(r, **kw) == INVALID, what
-        assert r._L.sptr_last_error(r._h), what
+        assert r._L.sptr_last_error(r._h) == message, what
         assert _renders_golden(r) == before, what  # the same bytes as before the refused call
     # (a lane context is the library's own and has no handle a caller could pass)
     with pytest.raises(sptr.SptrError):

@@ -301,20 +301,28 @@ def test_errors_leave_the_context_usable(rays, rays_dev):
     stream = torch.cuda.Stream(torch.device("cuda", 0))
     shifted = torch.zeros(n * 8 + 4, dtype=torch.float32, device="cuda:0")[1:1 + n * 8]  # 4 bytes off 16-byte alignment
     assert shifted.data_ptr() % 16 == 4
-    cases = {
-        "both sort flags": dict(rays=host, n=n, flags=sptr.SPTR_QUERY_SORT | sptr.SPTR_QUERY_NO_SORT, **ptr),
-        "more than 2^28 rays": dict(rays=host, n=(1 << 28) + 1, flags=0, **ptr),
-        "NULL rays": dict(rays=None, n=n, flags=0, **ptr),
-        "any-hit without occluded": dict(rays=host, n=n, flags=sptr.SPTR_QUERY_ANY_HIT, **ptr),
-        "any-hit without occluded, n = 0": dict(rays=None, n=0, flags=sptr.SPTR_QUERY_ANY_HIT),
-        "host pointers on a stream": dict(rays=host, n=n, flags=0, stream=stream.cuda_stream, **ptr),
-        "misaligned device rays": dict(rays=shifted.data_ptr(), n=n, flags=sptr.SPTR_QUERY_DEVICE_PTRS,
-                                       t=rays_dev.data_ptr()),
-        "unknown flag": dict(rays=host, n=n, flags=16, **ptr),
+    cases = {  # what is wrong: (sptr_last_error's text, the arguments)
+        "both sort flags": (b"query_rays: SPTR_QUERY_SORT and SPTR_QUERY_NO_SORT exclude each other",
+                            dict(rays=host, n=n, flags=sptr.SPTR_QUERY_SORT | sptr.SPTR_QUERY_NO_SORT, **ptr)),
+        "more than 2^28 rays": (b"query_rays: more than 2^28 rays",
+                                dict(rays=host, n=(1 << 28) + 1, flags=0, **ptr)),
+        "NULL rays": (b"query_rays: no rays",
+                      dict(rays=None, n=n, flags=0, **ptr)),
+        "any-hit without occluded": (b"query_rays: SPTR_QUERY_ANY_HIT needs the occluded output",
+                                     dict(rays=host, n=n, flags=sptr.SPTR_QUERY_ANY_HIT, **ptr)),
+        "any-hit without occluded, n = 0": (b"query_rays: SPTR_QUERY_ANY_HIT needs the occluded output",
+                                            dict(rays=None, n=0, flags=sptr.SPTR_QUERY_ANY_HIT)),
+        "host pointers on a stream": (b"query_rays: host pointers cannot be enqueued on a stream",
+                                      dict(rays=host, n=n, flags=0, stream=stream.cuda_stream, **ptr)),
+        "misaligned device rays": (b"query_rays: the device ray buffer must be 16-byte aligned",
+                                   dict(rays=shifted.data_ptr(), n=n, flags=sptr.SPTR_QUERY_DEVICE_PTRS,
+                                        t=rays_dev.data_ptr())),
+        "unknown flag": (b"query_rays: unknown flags",
+                         dict(rays=host, n=n, flags=16, **ptr)),
     }
-    for what, kw in cases.items():
+    for what, (message, kw) in cases.items():
         assert _raw(r, **kw) == INVALID, what
-        assert r._L.sptr_last_error(r._h), what
+        assert r._L.sptr_last_error(r._h) == message, what
         _renders_golden(r)
     with pytest.raises(sptr.SptrError):
         r.query_rays(rays, stream=stream.cuda_stream)
